@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Gbases/s classified on MI355X (BASELINE.json's metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (N=1 default = BASELINE.json configs[2], the configuration the metric is quoted
 on): k = 21, two 300 M-entry synthetic unique-k-mer tables replicated in each GPU's HBM,
@@ -14,10 +14,15 @@ H2D on the side stream overlapped with the previous batch's kernel, probe kernel
 - and the host takes the A/B/U binning decision (the host part of step i-1 overlaps the device part of
 step i; every step's host part is inside the timed region).  `value` = bases classified by all ranks /
 wall time of K steps between two barriers (max over ranks): the host-fed, PCIe-inclusive rate.
-`kernel_resident` beside it is the same K steps with the batches already in HBM (no H2D): what the
-kernels alone sustain.  (`--timed-path resident` makes that one the `value`, as rounds 1-2 reported it.)
-A region of K steps that lasts less than --min-timed-s is repeated until that much time has been
-measured, and the median region is reported (`timed_regions` says how many).
+`ms_per_step` = the wall time of one timed step.  (`--timed-path resident` times the batches already in HBM instead.)
+
+A plain run is lean: it sets up, warms up W steps, times exactly K steps once, writes the last timed step's
+outputs when --dump-outputs DIR is given (`counts`, `score_a`, `score_b` and `bins` as DIR/<name>.npy: what a
+caller of the classify stage receives for the step's reads; `histogram` for --path count) and prints the line.
+Everything else the line can carry comes with `--full`: there a region of K steps that lasts less than
+--min-timed-s (10 s) is repeated until that much time has been measured and the median region is reported
+(`timed_regions` says how many), and `kernel_resident` beside `value` is the same K steps with the batches
+already in HBM (no H2D): what the kernels alone sustain.
 
 Scaling.  Default "weak": every rank classifies its own reads (the generator is indexed by
 read number, ranks take disjoint ranges), tables replicated, no collective on the data path; every rank
@@ -32,7 +37,7 @@ Nothing here imports torch: the barrier and the max/sum of the timing scalars go
 a run-private directory (the ranks of one node share /tmp); `TBK_BENCH_DIST=gloo` selects a
 torch.distributed gloo group instead (tests cover both).
 
-The JSON line also carries, at every N,
+With --full the JSON line also carries, at every N,
   roofline      the dominant kernel's (the single-read probe kernel's) algorithmic bytes per launch / its
                 HIP-event-timed average duration inside the timed region, against the 8 TB/s HBM peak.  `frac` is
                 SURVEY §8d's reading for this design - one paired table probed once per window, P = 1: 9 bytes
@@ -52,8 +57,8 @@ before the copy) and with ASCII over PCIe (the kernel packs), and `realistic_lis
 shaped like real find-unique-kmers output (`--lists haplotypes`), in the same run.
 
 `--path count` benches the k-mer counting kernel of the find-unique-kmers step instead
-(SURVEY §8f N4): Gbases/s counted, atomic adds per second against the chip's measured ceiling,
-a CPU datum and a histogram parity check.
+(SURVEY §8f N4): Gbases/s counted and the counting kernel's time; with --full also atomic adds per
+second against the chip's measured ceiling, a CPU datum and a histogram parity check.
 """
 import argparse
 import ctypes as C
@@ -82,9 +87,17 @@ def parse(argv=None):
     ap.add_argument("--path", choices=["classify", "count"], default="classify")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--strong-reads", type=int, default=6_000_000, help="strong scaling: reads of the fixed set (configs[3]: 6 M x 15 kb = 90 Gbp)")
-    ap.add_argument("--min-timed-s", type=float, default=10.0,
-                    help="repeat the K-step region until this much time has been measured (10 s: a sustained-clock number the driver's "
-                         "utilisation sampler can see)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the resident leg, parity against the oracle, roofline, sweep, CPU baseline, "
+                         "pipeline variants, sub-records and counter passes.  Without it a run sets up, warms up, times --steps steps "
+                         "once and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32/float64, at most 64 MB in all; a fixed seeded sample of the reads when the step is larger)")
+    ap.add_argument("--min-timed-s", type=float, default=None,
+                    help="repeat the K-step region until this much time has been measured and report the median region (--full default "
+                         "10 s: a sustained-clock number the driver's utilisation sampler can see; default without --full: 0, one "
+                         "region of exactly --steps steps)")
     ap.add_argument("--no-realistic", action="store_true",
                     help="N = 1: skip the `realistic_lists` sub-record (the same bench on haplotype-shaped lists, a second table build and a few seconds of timing)")
     ap.add_argument("--no-strong-leg", action="store_true",
@@ -141,7 +154,51 @@ def parse(argv=None):
     ap.add_argument("--count-genome", type=int, default=200_000_000)
     ap.add_argument("--count-read-len", type=int, default=150)
     ap.add_argument("--count-batch-bases", type=int, default=1_000_000_000)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.min_timed_s is None:
+        args.min_timed_s = 10.0 if args.full else 0.0
+    return args
+
+
+DUMP_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0x5EED0007
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1, rows=None):
+    """Write `arrays` (name -> array, float32/float64) as out_dir/<name>.npy; ranks past 0 add `_rank<r>` to the name.
+    When they hold more than this rank's share of DUMP_BYTES, the same fixed seeded sample of their first axis (`rows`
+    long) is kept of every array and its indices are written as `read_index`."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // max(1, world) - 4096   # (room for the .npy headers)
+    total = sum(a.nbytes for a in arrays.values())
+    if rows and total > budget:
+        keep = max(1, int(budget // (total / rows + 8)))   # (8 bytes a row for the index array itself)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, size=min(rows, keep), replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["read_index"] = idx.astype(np.float64)
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+
+def build_lock():
+    """An open file the ranks serialise their builds on: .build.lock in the tree or, where the tree is not writable (a
+    checkout another user built), a lock named after the tree in the temporary directory.  flock needs only a descriptor,
+    so an existing lock file that is not ours is opened for reading.  None when neither can be opened."""
+    import hashlib
+    import tempfile
+
+    spare = os.path.join(tempfile.gettempdir(), "tbk_build_%s.lock" % hashlib.sha256(ROOT.encode()).hexdigest()[:16])
+    for path in (os.path.join(ROOT, ".build.lock"), spare):
+        for mode in ("a", "r"):
+            try:
+                return open(path, mode)
+            except OSError:
+                pass
+    return None
 
 
 # ---- ranks ------------------------------------------------------------------------------------------
@@ -308,10 +365,14 @@ def main():
 
     # every rank makes sure the library is built (make is a no-op when it is), one at a time
     if os.environ.get("TBK_SKIP_BUILD") != "1":  # skipped under rocprofv3 (no child processes there)
-        with open(os.path.join(ROOT, ".build.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
+        lock = build_lock()
+        try:
+            if lock:
+                fcntl.flock(lock, fcntl.LOCK_EX)
             entry.build()
-            fcntl.flock(lock, fcntl.LOCK_UN)
+        finally:
+            if lock:
+                lock.close()   # (closing releases the lock)
     from trio_binning_amd import _lib, kmers
     from trio_binning_amd._lib import check, lib
 
@@ -333,15 +394,16 @@ def main():
         dist.close()
         return
     out = run_classify(args, np, kmers, lib, check, _lib, dev, dist, world, rank, placement)
-    if rank == 0 and world == 1:
-        note = live_traffic(args, out)
-        if note:
-            out["roofline"]["live_counter_pass"] = note
-    out["roofline"].pop("_pricing", None)
-    if rank == 0 and world == 1 and not args.no_realistic and args.lists == "uniform" and args.scaling == "weak":
-        out["realistic_lists"] = realistic_lists(args, np, kmers, lib, check, _lib, dev, dist, placement)
-    if rank == 0 and world == 1 and not args.no_strong_leg and args.lists == "uniform" and args.scaling == "weak" and args.read_lengths == "fixed":
-        out["strong_90gbp"] = strong_leg(args, np, kmers, lib, check, _lib, dev, dist, placement, out)
+    if args.full:
+        if rank == 0 and world == 1:
+            note = live_traffic(args, out)
+            if note:
+                out["roofline"]["live_counter_pass"] = note
+        out["roofline"].pop("_pricing", None)
+        if rank == 0 and world == 1 and not args.no_realistic and args.lists == "uniform" and args.scaling == "weak":
+            out["realistic_lists"] = realistic_lists(args, np, kmers, lib, check, _lib, dev, dist, placement)
+        if rank == 0 and world == 1 and not args.no_strong_leg and args.lists == "uniform" and args.scaling == "weak" and args.read_lengths == "fixed":
+            out["strong_90gbp"] = strong_leg(args, np, kmers, lib, check, _lib, dev, dist, placement, out)
     dist.barrier()
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -357,6 +419,7 @@ def strong_leg(args, np, kmers, lib, check, _lib, dev, dist, placement, headline
     a = copy.copy(args)
     a.scaling = "strong"
     a.steps, a.warmup = 1, 1
+    a.dump_outputs = None
     a.min_timed_s = args.strong_leg_timed_s
     a.no_streaming = True
     a.calibrate = False
@@ -384,6 +447,7 @@ def realistic_lists(args, np, kmers, lib, check, _lib, dev, dist, placement):
 
     a = copy.copy(args)
     a.lists = "haplotypes"
+    a.dump_outputs = None
     a.min_timed_s = args.realistic_timed_s
     a.no_streaming = True
     a.calibrate = False
@@ -577,7 +641,8 @@ def live_traffic(args, out, extra_child_args=()):
     if not exe:
         return "no live counter pass: rocprofv3 not found"
     skip, child_args, it = {"--gpus": 1, "--steps": 1, "--warmup": 1, "--min-timed-s": 1, "--live-pmc": 1, "--cpu-seconds": 1,
-                            "--no-cpu-baseline": 0, "--no-streaming": 0, "--no-realistic": 0, "--no-sweep": 0, "--no-strong-leg": 0, "--calibrate": 0, "--lists": 1}, [], iter(sys.argv[1:])
+                            "--no-cpu-baseline": 0, "--no-streaming": 0, "--no-realistic": 0, "--no-sweep": 0, "--no-strong-leg": 0, "--calibrate": 0, "--lists": 1,
+                            "--full": 0, "--dump-outputs": 1}, [], iter(sys.argv[1:])
     for a in it:
         name = a.split("=", 1)[0]
         if name in skip:
@@ -586,7 +651,7 @@ def live_traffic(args, out, extra_child_args=()):
             continue
         child_args.append(a)
     child_args += list(extra_child_args)   # (the realistic_lists sub-record's pass: --lists haplotypes)
-    child_args += ["--steps", "4", "--warmup", "1", "--min-timed-s", "0", "--no-cpu-baseline", "--no-streaming", "--no-realistic", "--no-sweep", "--no-strong-leg",
+    child_args += ["--full", "--steps", "4", "--warmup", "1", "--min-timed-s", "0", "--no-cpu-baseline", "--no-streaming", "--no-realistic", "--no-sweep", "--no-strong-leg",
                    "--live-pmc", "off"]   # (the timed path stays the parent's: host-fed batches are read packed, resident ones as ASCII)
     tmp = tempfile.mkdtemp(prefix="tbk_live_pmc_", dir="/tmp")
     t0 = time.time()
@@ -673,6 +738,7 @@ def price_traffic(roofline, traffic):
 
 def run_classify(args, np, kmers, lib, check, _lib, dev, dist, world, rank, placement):
     k, n_list, L, R = args.k, args.kmers_per_list, args.read_len, args.reads_per_step
+    full = args.full
 
     def dalloc(nbytes):
         p = C.c_void_p()
@@ -716,7 +782,7 @@ def run_classify(args, np, kmers, lib, check, _lib, dev, dist, world, rank, plac
         assert stats["distinct_a"] == n_list and stats["distinct_b"] == n_list, stats
 
     sweep_rec = None
-    if args.sweep and rank == 0:
+    if full and args.sweep and rank == 0:
         from trio_binning_amd.sweep import full_membership_sweep
 
         t_sw = time.time()
@@ -726,7 +792,7 @@ def run_classify(args, np, kmers, lib, check, _lib, dev, dist, world, rank, plac
         sweep_rec["what"] = ("every key of both lists as a read of k bases and packed 512 to a long read, as many non-members, every key with one base "
                              "substituted: counts compared on the device with what the lists say (c/kmers.c:112-122, 245-268)")
 
-    want_cpu = rank == 0 and not args.no_cpu_baseline
+    want_cpu = full and rank == 0 and not args.no_cpu_baseline
     h_keys = None
     if want_cpu:
         h_keys = np.empty(2 * n_list, dtype=np.uint64)
@@ -807,22 +873,30 @@ def run_classify(args, np, kmers, lib, check, _lib, dev, dist, world, rank, plac
     num_a, num_b = hap_a.num_kmers, hap_b.num_kmers
     bins_total = {"A": 0, "B": 0, "U": 0}
 
-    def finish(waiter, ticket, slot, n_r, tally):
+    last_step = []  # --dump-outputs: (counts, score_a, score_b, bins) of every launch of the last timed step
+
+    def finish(waiter, ticket, slot, n_r, tally, keep=False):
         """Host side of a step: wait for its counts, take the A/B/U decision."""
         waiter(ticket)
-        _, _, bins = kmers.score_and_bin(counts_ring[slot][:n_r], num_a, num_b)
+        sa, sb, bins = kmers.score_and_bin(counts_ring[slot][:n_r], num_a, num_b)
         if tally:
             for name, ch in (("A", b"A"), ("B", b"B"), ("U", b"U")):
                 bins_total[name] += bins.count(ch)
+        if keep:
+            last_step.append((counts_ring[slot][:n_r].copy(), sa, sb, bins))
 
     # a step: weak = one batch (cycled); strong = every batch of the shard
     launches_per_step = len(batches) if strong else 1
     bases_per_step = sum(b[3] for b in batches) if strong else batches[0][3]
 
-    def run(n_steps, tally, fed):
+    def run(n_steps, tally, fed, keep_last=False):
         """n_steps steps, pipelined: the host finishes step i-1 while the device works on step i.
-        fed: through the pipeline from pinned host memory; else: batches resident in HBM."""
+        fed: through the pipeline from pinned host memory; else: batches resident in HBM.
+        keep_last: hold on to what the last step computed (last_step)."""
         pending = []
+        first_of_last = (n_steps - 1) * launches_per_step
+        if keep_last:
+            del last_step[:]
         waiter = pipe.wait if fed else cls.wait
         # host-fed: as many batches submitted as the ring holds (the third one's copy runs beside the first one's
         # kernel); resident: one fewer is enough to keep the compute stream busy
@@ -831,21 +905,21 @@ def run_classify(args, np, kmers, lib, check, _lib, dev, dist, world, rank, plac
             d_b, d_o, n_r, tot, packed = batches[i % len(batches)]
             slot = i % depth
             if len(pending) == ahead:
-                finish(waiter, *pending.pop(0), tally)
+                finish(waiter, *pending.pop(0))
             if fed:
                 t = pipe.submit_packed(packed, counts_ring[slot][:n_r])
             else:
                 t = cls.submit_device(d_b, d_o, n_r, tot, counts_ring[slot][:n_r])
-            pending.append((t, slot, n_r))
+            pending.append((t, slot, n_r, tally, keep_last and i >= first_of_last))
         while pending:
-            finish(waiter, *pending.pop(0), tally)
+            finish(waiter, *pending.pop(0))
 
     def region_of(fed, tally):
         def region():
             check(lib.tbk_device_sync(dev))
             dist.barrier()
             t0 = time.perf_counter()
-            run(args.steps, tally, fed)
+            run(args.steps, tally, fed, keep_last=tally and args.dump_outputs is not None)
             check(lib.tbk_device_sync(dev))
             dist.barrier()
             return time.perf_counter() - t0
@@ -865,7 +939,16 @@ def run_classify(args, np, kmers, lib, check, _lib, dev, dist, world, rank, plac
     elapsed = statistics.median(region_s)
     value = bases_all / elapsed / 1e9
     other = None
-    if keep_resident and host_fed:
+    if args.dump_outputs is not None:
+        counts = np.concatenate([c for c, _, _, _ in last_step])
+        codes = np.frombuffer(b"".join(b for _, _, _, b in last_step), dtype=np.uint8)
+        dump_outputs(args.dump_outputs, {
+            "counts": counts.astype(np.float64),                                           # (reads, 2): k-mers found in hapA, hapB
+            "score_a": np.concatenate([a for _, a, _, _ in last_step]),                     # float64 scores, as the CLI's TSV
+            "score_b": np.concatenate([b for _, _, b, _ in last_step]),
+            "bins": np.searchsorted(np.frombuffer(b"ABU", dtype=np.uint8), codes).astype(np.float32),   # 0 = A, 1 = B, 2 = U
+        }, rank, world, rows=counts.shape[0])
+    if full and keep_resident and host_fed:
         o_region_s, o_l, o_probe_ms, o_single_ms = timed(False, False)
         o_el = statistics.median(o_region_s)
         other = {"gbases_per_s": round(bases_all / o_el / 1e9, 3), "ms_per_step": round(o_el / args.steps * 1e3, 3),
@@ -875,7 +958,7 @@ def run_classify(args, np, kmers, lib, check, _lib, dev, dist, world, rank, plac
     # the ceiling of the window loop's line rate on THIS table (where its pages lie moves the rate by +-2 %: EXPERIMENTS.md): a pure
     # gather in the loop's own request shape over the table the timed legs have just used - 2^28 random lines (5 ms) per shape
     same_table = None
-    if rank == 0 and hasattr(lib, "tbk_classifier_calibrate_pairs"):
+    if full and rank == 0 and hasattr(lib, "tbk_classifier_calibrate_pairs"):
         try:
             shapes = {f"waves8_inflight{inf}": round(max(cls.calibrate_pairs(inf, 8) for _ in range(2)) / 1e9, 2) for inf in (2, 4, 8)}
             same_table = {"best": max(shapes.values()), **shapes}
@@ -899,94 +982,96 @@ def run_classify(args, np, kmers, lib, check, _lib, dev, dist, world, rank, plac
     else:
         bucket_select = "minimizer w=%d m=%d" % (stats["minimizer_w"], stats["minimizer_m"])
 
-    # ---- parity: every rank classifies the generator's first reads through the host-fed path ------------
-    n_par = max(1, min(args.parity_reads, 1 << 16))
-    par_offs = lengths_of(0, n_par)
-    par_total = int(par_offs[-1])
-    d_pb, d_po = dalloc((par_total + 15) // 16 * 16 + 16), dalloc((n_par + 1) * 8)
-    synth_reads(0, n_par, d_pb, d_po, par_offs)
-    par_bases = kmers.pinned_empty((par_total,), np.uint8)
-    check(lib.tbk_memcpy_d2h(dev, par_bases.ctypes.data, C.c_void_p(d_pb), par_bases.nbytes))
-    par_counts = pipe.wait(pipe.submit(par_bases, par_offs)).copy()                      # ASCII in, packed by the feeder
-    par_counts2 = pipe.wait(pipe.submit_packed(kmers.pack_bases(par_bases, par_offs)))   # packed ahead, as the reader does
-    import zlib
-
-    mine = {"rank": rank, "device_index": dev, "device": _lib.device_identity(dev), "placement": placement, "sum_a": int(par_counts[:, 0].sum()), "sum_b": int(par_counts[:, 1].sum()),
-            "crc32": zlib.crc32(par_counts.tobytes()), "transfers_agree": bool(np.array_equal(par_counts, par_counts2))}
-    everyone = dist.gather_obj(mine)
-    parity = {"reads_checked_per_rank": n_par, "bases_checked_per_rank": par_total, "count_checksum": [mine["sum_a"], mine["sum_b"], mine["crc32"]],
-              "all_ranks_equal": all((e["sum_a"], e["sum_b"], e["crc32"]) == (mine["sum_a"], mine["sum_b"], mine["crc32"]) for e in everyone),
-              "packed_and_ascii_transfers_agree": all(e["transfers_agree"] for e in everyone)}
-    devices = [{"rank": e["rank"], "device_index": e["device_index"], "id": e["device"], **e["placement"]} for e in everyone]
-
-    # ---- roofline of the dominant kernel (rank 0's device) ----------------------------------------------
-    # The probe is four kernels: pass index, the multi-read and two-read kernels (passes that touch several reads) and the
-    # single-read kernel (passes inside one read: on 15 kb reads 86 % of the passes).  The roofline is the
-    # single-read kernel's: its windows x the algorithmic bytes per window (1 read byte + 8 B for
-    # the hapA slot + 8 B for the hapB slot when hapA missed; P = 1 reading: 1 + 8) / its HIP-event time.
-    hit_a_frac = float(par_counts[:, 0].sum()) / max(1, int(np.maximum(np.diff(par_offs).astype(np.int64) - k + 1, 0).sum()))
-    reads_per_launch = sum(b[2] for b in batches) / len(batches)
-    bases_per_launch = sum(b[3] for b in batches) / len(batches)
-    windows = sum(windows_of) / len(batches)
-    single_frac = 1.0 - multi_passes / max(1, n_passes)
-    windows_single = windows * single_frac
-    # "a merged single-table implementation must report with P = 1 (B_alg = 9 B)".  The design is one paired
-    # table probed once per window, so `frac` is the P = 1 reading; the two-probe reading
-    # (1 + 8 + 8 per window that misses hapA) is printed beside it.
-    b_alg = 9.0
-    b_alg_p2 = 9 + 8 * (1 - hit_a_frac)
-    alg_bytes = windows_single * b_alg
-    single_s = single_ms / max(1, launches) * 1e-3
-    probe_s = probe_ms / max(1, launches) * 1e-3
-    achieved = alg_bytes / single_s / 1e9 if single_s > 0 else 0.0
     table_load = n_list / (stats["n_buckets"] * 8)
-    traffic = traffic_src = None
-    for tname in ("pmc_traffic.json", "pmc_traffic_haplotypes.json"):
-        tfile = os.path.join(ROOT, "profiles", tname)
-        if not os.path.isfile(tfile):
-            continue
-        try:
-            t = json.load(open(tfile))
-            same = (t.get("read_len") == L and t.get("kmers_per_list") == n_list
-                    and t.get("k") == k and t.get("bucket_select") == bucket_select and t.get("lists", "uniform") == args.lists
-                    and abs(t.get("table_load", 0) - table_load) < 2e-3
-                    and bool(t.get("front_layout", False)) == bool(stats.get("front_layout"))
-                    and bool(t.get("entry_layout", False)) == bool(stats.get("entry_layout"))
-                    and bool(t.get("short_keys", False)) == bool(stats.get("short_keys"))
-                    and bool(t.get("full_keys", False)) == bool(stats.get("full_keys"))
-                    and t.get("kernel") == "tbk_probe_kernel<single-read>")
-            if same and t.get("kernel_sha256") != kernel_fingerprint():
-                # taken on other kernels than the ones in this tree: stale bytes are not reported
-                traffic_src = ("profiles/" + tname + " is STALE: its PMC passes ran on kernels " + str(t.get("kernel_sha256"))[:17]
-                               + ", this tree's are " + kernel_fingerprint()[:17] + " - re-run tools/gpu_profile.sh; traffic withheld")
-            elif same:  # measured in separate rocprofv3 --pmc passes on this configuration (not in this run); scaled to this launch's windows
-                traffic = t["hbm_bytes_per_window"] * windows_single
-                traffic_src = ("profiles/" + tname + " (rocprofv3 --pmc passes of this configuration on these very kernels, machine code sha256 "
-                               + kernel_fingerprint()[5:17] + ", replayed per window; not measured in this run)")
-        except Exception:
-            pass
-    roofline = {
-        "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-        "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": None if traffic is None else int(traffic), "traffic_source": traffic_src,
-        "kernel": ("tbk_probe_entry_kernel<W, MULTI=false, TWO=false>" if stats.get("entry_layout") else "tbk_probe_entry_kernel<W, MULTI=false, TWO=false, KIND=2: short keys>" if stats.get("short_keys")
-                   else "tbk_probe_entry_kernel<W, MULTI=false, TWO=false, KIND=3: full keys>" if stats.get("full_keys")
-                   else "tbk_probe_kernel<..., MULTI=false, TWO=false>") + " (single-read passes)", "kernel_ms_avg": round(single_s * 1e3, 4), "launches": int(launches),
-        "timed_in": "the timed region of `value` (HIP events on the compute stream)",
-        "alg_bytes_per_launch": int(alg_bytes), "alg_bytes_per_window": round(b_alg, 3), "windows_per_launch": int(windows_single),
-        "share_of_the_batch_windows": round(single_frac, 4), "passes": int(n_passes), "multi_read_passes": int(multi_passes),
-        "reading": "P = 1 (SURVEY 8d's merged-table rule: 1 read byte + one 8-byte slot per window)",
-        "frac_P2_two_probe_reading": round(windows_single * b_alg_p2 / single_s / 1e9 / HBM_PEAK_GBPS, 4) if single_s > 0 else None,
-        "alg_bytes_per_window_P2": round(b_alg_p2, 3),
-        "whole_probe_ms_avg": round(probe_s * 1e3, 4),
-        "whole_probe": {"what": "pass index + multi-read, two-read and single-read kernels, per batch", "alg_bytes": int(windows * b_alg),
-                        "achieved": round(windows * b_alg / probe_s / 1e9, 1) if probe_s > 0 else None,
-                        "frac": round(windows * b_alg / probe_s / 1e9 / HBM_PEAK_GBPS, 4) if probe_s > 0 else None},
-        "kernel_only_gbases_per_s": round(bases_per_launch / probe_s / 1e9, 2) if probe_s > 0 else None,
-    }
-    roofline["kernel_resources"] = kernel_resources(stats)
-    roofline["_pricing"] = {"single_s": single_s, "alg_bytes": alg_bytes, "table_bytes": stats["table_bytes"], "same_table": same_table,
-                            "stream_bytes": bases_per_launch * single_frac * (sum(b[4].nbytes for b in batches) / max(1, sum(b[3] for b in batches)) if host_fed else 1.0)}   # (price_traffic's inputs; main() drops it)
-    price_traffic(roofline, traffic)
+    parity = devices = roofline = None
+    if full:
+        # ---- parity: every rank classifies the generator's first reads through the host-fed path ------------
+        n_par = max(1, min(args.parity_reads, 1 << 16))
+        par_offs = lengths_of(0, n_par)
+        par_total = int(par_offs[-1])
+        d_pb, d_po = dalloc((par_total + 15) // 16 * 16 + 16), dalloc((n_par + 1) * 8)
+        synth_reads(0, n_par, d_pb, d_po, par_offs)
+        par_bases = kmers.pinned_empty((par_total,), np.uint8)
+        check(lib.tbk_memcpy_d2h(dev, par_bases.ctypes.data, C.c_void_p(d_pb), par_bases.nbytes))
+        par_counts = pipe.wait(pipe.submit(par_bases, par_offs)).copy()                      # ASCII in, packed by the feeder
+        par_counts2 = pipe.wait(pipe.submit_packed(kmers.pack_bases(par_bases, par_offs)))   # packed ahead, as the reader does
+        import zlib
+
+        mine = {"rank": rank, "device_index": dev, "device": _lib.device_identity(dev), "placement": placement, "sum_a": int(par_counts[:, 0].sum()), "sum_b": int(par_counts[:, 1].sum()),
+                "crc32": zlib.crc32(par_counts.tobytes()), "transfers_agree": bool(np.array_equal(par_counts, par_counts2))}
+        everyone = dist.gather_obj(mine)
+        parity = {"reads_checked_per_rank": n_par, "bases_checked_per_rank": par_total, "count_checksum": [mine["sum_a"], mine["sum_b"], mine["crc32"]],
+                  "all_ranks_equal": all((e["sum_a"], e["sum_b"], e["crc32"]) == (mine["sum_a"], mine["sum_b"], mine["crc32"]) for e in everyone),
+                  "packed_and_ascii_transfers_agree": all(e["transfers_agree"] for e in everyone)}
+        devices = [{"rank": e["rank"], "device_index": e["device_index"], "id": e["device"], **e["placement"]} for e in everyone]
+
+        # ---- roofline of the dominant kernel (rank 0's device) ----------------------------------------------
+        # The probe is four kernels: pass index, the multi-read and two-read kernels (passes that touch several reads) and the
+        # single-read kernel (passes inside one read: on 15 kb reads 86 % of the passes).  The roofline is the
+        # single-read kernel's: its windows x the algorithmic bytes per window (1 read byte + 8 B for
+        # the hapA slot + 8 B for the hapB slot when hapA missed; P = 1 reading: 1 + 8) / its HIP-event time.
+        hit_a_frac = float(par_counts[:, 0].sum()) / max(1, int(np.maximum(np.diff(par_offs).astype(np.int64) - k + 1, 0).sum()))
+        reads_per_launch = sum(b[2] for b in batches) / len(batches)
+        bases_per_launch = sum(b[3] for b in batches) / len(batches)
+        windows = sum(windows_of) / len(batches)
+        single_frac = 1.0 - multi_passes / max(1, n_passes)
+        windows_single = windows * single_frac
+        # "a merged single-table implementation must report with P = 1 (B_alg = 9 B)".  The design is one paired
+        # table probed once per window, so `frac` is the P = 1 reading; the two-probe reading
+        # (1 + 8 + 8 per window that misses hapA) is printed beside it.
+        b_alg = 9.0
+        b_alg_p2 = 9 + 8 * (1 - hit_a_frac)
+        alg_bytes = windows_single * b_alg
+        single_s = single_ms / max(1, launches) * 1e-3
+        probe_s = probe_ms / max(1, launches) * 1e-3
+        achieved = alg_bytes / single_s / 1e9 if single_s > 0 else 0.0
+        traffic = traffic_src = None
+        for tname in ("pmc_traffic.json", "pmc_traffic_haplotypes.json"):
+            tfile = os.path.join(ROOT, "profiles", tname)
+            if not os.path.isfile(tfile):
+                continue
+            try:
+                t = json.load(open(tfile))
+                same = (t.get("read_len") == L and t.get("kmers_per_list") == n_list
+                        and t.get("k") == k and t.get("bucket_select") == bucket_select and t.get("lists", "uniform") == args.lists
+                        and abs(t.get("table_load", 0) - table_load) < 2e-3
+                        and bool(t.get("front_layout", False)) == bool(stats.get("front_layout"))
+                        and bool(t.get("entry_layout", False)) == bool(stats.get("entry_layout"))
+                        and bool(t.get("short_keys", False)) == bool(stats.get("short_keys"))
+                        and bool(t.get("full_keys", False)) == bool(stats.get("full_keys"))
+                        and t.get("kernel") == "tbk_probe_kernel<single-read>")
+                if same and t.get("kernel_sha256") != kernel_fingerprint():
+                    # taken on other kernels than the ones in this tree: stale bytes are not reported
+                    traffic_src = ("profiles/" + tname + " is STALE: its PMC passes ran on kernels " + str(t.get("kernel_sha256"))[:17]
+                                   + ", this tree's are " + kernel_fingerprint()[:17] + " - re-run tools/gpu_profile.sh; traffic withheld")
+                elif same:  # measured in separate rocprofv3 --pmc passes on this configuration (not in this run); scaled to this launch's windows
+                    traffic = t["hbm_bytes_per_window"] * windows_single
+                    traffic_src = ("profiles/" + tname + " (rocprofv3 --pmc passes of this configuration on these very kernels, machine code sha256 "
+                                   + kernel_fingerprint()[5:17] + ", replayed per window; not measured in this run)")
+            except Exception:
+                pass
+        roofline = {
+            "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": None if traffic is None else int(traffic), "traffic_source": traffic_src,
+            "kernel": ("tbk_probe_entry_kernel<W, MULTI=false, TWO=false>" if stats.get("entry_layout") else "tbk_probe_entry_kernel<W, MULTI=false, TWO=false, KIND=2: short keys>" if stats.get("short_keys")
+                       else "tbk_probe_entry_kernel<W, MULTI=false, TWO=false, KIND=3: full keys>" if stats.get("full_keys")
+                       else "tbk_probe_kernel<..., MULTI=false, TWO=false>") + " (single-read passes)", "kernel_ms_avg": round(single_s * 1e3, 4), "launches": int(launches),
+            "timed_in": "the timed region of `value` (HIP events on the compute stream)",
+            "alg_bytes_per_launch": int(alg_bytes), "alg_bytes_per_window": round(b_alg, 3), "windows_per_launch": int(windows_single),
+            "share_of_the_batch_windows": round(single_frac, 4), "passes": int(n_passes), "multi_read_passes": int(multi_passes),
+            "reading": "P = 1 (SURVEY 8d's merged-table rule: 1 read byte + one 8-byte slot per window)",
+            "frac_P2_two_probe_reading": round(windows_single * b_alg_p2 / single_s / 1e9 / HBM_PEAK_GBPS, 4) if single_s > 0 else None,
+            "alg_bytes_per_window_P2": round(b_alg_p2, 3),
+            "whole_probe_ms_avg": round(probe_s * 1e3, 4),
+            "whole_probe": {"what": "pass index + multi-read, two-read and single-read kernels, per batch", "alg_bytes": int(windows * b_alg),
+                            "achieved": round(windows * b_alg / probe_s / 1e9, 1) if probe_s > 0 else None,
+                            "frac": round(windows * b_alg / probe_s / 1e9 / HBM_PEAK_GBPS, 4) if probe_s > 0 else None},
+            "kernel_only_gbases_per_s": round(bases_per_launch / probe_s / 1e9, 2) if probe_s > 0 else None,
+        }
+        roofline["kernel_resources"] = kernel_resources(stats)
+        roofline["_pricing"] = {"single_s": single_s, "alg_bytes": alg_bytes, "table_bytes": stats["table_bytes"], "same_table": same_table,
+                                "stream_bytes": bases_per_launch * single_frac * (sum(b[4].nbytes for b in batches) / max(1, sum(b[3] for b in batches)) if host_fed else 1.0)}   # (price_traffic's inputs; main() drops it)
+        price_traffic(roofline, traffic)
 
     if want_cpu and L > 2_000_000:
         # the CPU sample works in whole reads; one read of this length is minutes of oracle time
@@ -1036,28 +1121,31 @@ def run_classify(args, np, kmers, lib, check, _lib, dev, dist, world, rank, plac
         "timed_regions": len(region_s), "timed_total_s": round(sum(region_s), 3),
         "region_s_min_median_max": [round(min(region_s), 4), round(elapsed, 4), round(max(region_s), 4)],
         ("kernel_resident" if host_fed else "host_fed"): other,
-        "roofline": roofline, "parity": parity, "devices": devices, "distinct_devices": len({d["id"] for d in devices}),
+        "roofline": roofline, "parity": parity, "devices": devices, "distinct_devices": len({d["id"] for d in devices}) if devices else None,
         "bins": bins_total, "setup_s": round(t_setup, 2), "table_build_s": round(t_build, 2),
         "device": _lib.device_name(dev),
     }
+    if not full:   # what only --full measures or checks
+        for key in ("kernel_resident" if host_fed else "host_fed", "roofline", "parity", "devices", "distinct_devices"):
+            del out[key]
     if args.share_device:
         out["devices_note"] = "--share-device: every rank uses device 0 (a plumbing run, not a scaling result)"
 
     # ---- the same stage fed differently (rank 0, N = 1) ----------------------------------------------
-    if rank == 0 and world == 1 and not args.no_streaming and not ragged:
+    if full and rank == 0 and world == 1 and not args.no_streaming and not ragged:
         out["pipeline_variants"] = pipeline_variants(args, np, kmers, lib, check, dev, pipe, par_bases, par_offs, par_counts, batches[0], L)
-    if rank == 0 and world == 1 and not args.no_streaming and not ragged and not hap and hasattr(lib, "tbk_gzip_bench_device"):
+    if full and rank == 0 and world == 1 and not args.no_streaming and not ragged and not hap and hasattr(lib, "tbk_gzip_bench_device"):
         try:
             out["bins_gzip_encoder"] = gzip_encoder_leg(np, kmers, lib, check, dev, par_bases, par_offs)
         except Exception as e:  # (a side record: it must not cost the bench line)
             print(f"bench: bins_gzip_encoder leg failed: {e}", file=sys.stderr)
-    if rank == 0 and world == 1 and not args.no_streaming and not ragged and not hap and hasattr(lib, "tbk_bgzf_bench_device"):
+    if full and rank == 0 and world == 1 and not args.no_streaming and not ragged and not hap and hasattr(lib, "tbk_bgzf_bench_device"):
         try:
             out["input_bgzf_inflater"] = bgzf_inflater_leg(np, lib, check, dev, par_bases, par_offs)
         except Exception as e:
             print(f"bench: input_bgzf_inflater leg failed: {e}", file=sys.stderr)
 
-    if args.calibrate and rank == 0:
+    if full and args.calibrate and rank == 0:
         out["calibration"] = calibrate(lib, check, dev, stats["table_bytes"])
 
     # ---- CPU baseline + read-for-read parity on a bounded sample (rank 0, every N) ---------------------
@@ -1354,6 +1442,8 @@ def bench_count(args, np, kmers, lib, check, dev, dist, world, rank):
     bases_all = dist.reduce(args.steps * total, "SUM")
     value = bases_all / elapsed / 1e9
     hist = ctr.histogram()
+    if args.dump_outputs is not None:   # what a caller of the counter receives: the histogram of the table after the last step
+        dump_outputs(args.dump_outputs, {"histogram": hist.astype(np.float64)}, rank, world)
     st = ctr.stats()
     # algorithmic bytes per window start: 1 read byte + the 8-byte key it is compared with + the
     # 32-bit counter read and written back
@@ -1381,7 +1471,7 @@ def bench_count(args, np, kmers, lib, check, dev, dist, world, rank):
     out["roofline"]["launches_per_step"] = round(launches / max(1, args.steps), 2)
     out["roofline"]["kernel_ms_per_step"] = round(kernel_ms / max(1, args.steps), 3)
     out["roofline"]["step_ms_outside_the_kernel"] = round(elapsed / args.steps * 1e3 - kernel_ms / max(1, args.steps), 3)
-    if rank == 0:
+    if args.full and rank == 0:
         # The yardstick: the chip's rate for the adds the kernel really issues - 64-bit atomic adds that count two
         # neighbouring 32-bit counters at once, one or two per line visited - measured by tbk_calib_atomics64 over the
         # same footprint; the kernel's adds are counted on the device (tbk_counter_adds_issued).  (Round 3 priced
@@ -1401,7 +1491,7 @@ def bench_count(args, np, kmers, lib, check, dev, dist, world, rank):
         out["roofline"]["atomic_ceiling"] = f"64-bit adds, {run_len} per random line (tbk_calib_atomics64)"
         out["roofline"]["atomic_frac"] = round(adds_timed / k_s / aps.value, 3) if k_s > 0 else None
         out["roofline"]["atomic_adds32_ceiling_Gps"] = round(aps32.value / 1e9, 2)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle
 
         orc = oracle.load()

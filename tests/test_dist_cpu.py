@@ -127,3 +127,29 @@ def test_bench_source_never_imports_torch_by_default():
     # the only torch imports sit in the opt-in gloo backend of Dist
     assert lines == ["import torch.distributed as dist"]
     assert src.count("import torch") == 1
+
+
+def test_build_lock_outside_a_tree_it_cannot_write(monkeypatch, tmp_path):
+    """bench.py serialises its ranks' builds on a lock file; a checkout it may not write to (built by another user) must
+    not stop it - the lock then lives in the temporary directory, and a lock file another user made there still locks."""
+    import fcntl
+    import tempfile
+
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path / "no_such_tree"))
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))
+    lock = bench.build_lock()
+    assert lock is not None and os.path.dirname(lock.name) == str(tmp_path) and lock.name.endswith(".lock")
+    fcntl.flock(lock, fcntl.LOCK_EX)
+    lock.close()
+    os.chmod(lock.name, 0o444)   # (read-only: how another user's lock file looks to this one)
+
+    def open_as_another_user(path, mode="r"):   # (root may write anything: refuse writing the way the file's mode would)
+        if mode != "r":
+            raise PermissionError(path)
+        return open(path, mode)
+
+    monkeypatch.setattr(bench, "open", open_as_another_user, raising=False)
+    again = bench.build_lock()
+    assert again is not None and again.name == lock.name
+    fcntl.flock(again, fcntl.LOCK_EX)
+    again.close()

@@ -1,17 +1,19 @@
-"""bench.py as the driver runs it, at test size: one JSON line with the contract's keys, and `roofline.traffic` taken from
-counters of the run itself (the child pass under rocprofv3 --pmc FETCH_SIZE), not replayed from profiles/."""
+"""bench.py as the driver runs it, at test size: one JSON line with the contract's keys, the plain run's timed steps and the
+outputs it dumps, and (--full) `roofline.traffic` taken from counters of the run itself (the child pass under rocprofv3 --pmc
+FETCH_SIZE), not replayed from profiles/."""
 import json
 import os
 import shutil
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
-SMALL = ["--kmers-per-list", "3000000", "--reads-per-step", "8192", "--steps", "3", "--warmup", "1", "--min-timed-s", "0",
+SMALL = ["--full", "--kmers-per-list", "3000000", "--reads-per-step", "8192", "--steps", "3", "--warmup", "1", "--min-timed-s", "0",
          "--no-cpu-baseline", "--no-streaming", "--no-realistic", "--no-strong-leg", "--parity-reads", "256"]
 
 
@@ -24,6 +26,36 @@ def run_bench(extra, base=None):
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
     return json.loads(lines[0])
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full: exactly --steps timed steps, the headline keys, none of what --full adds, and the last timed step's
+    counts, scores and bins under --dump-outputs - the same from one run to the next (the inputs are seeded)."""
+    plain = ["--kmers-per-list", "3000000", "--reads-per-step", "8192", "--steps", "3", "--warmup", "1"]
+    dumps = []
+    for run in range(2):
+        dumps.append(tmp_path / ("out%d" % run))
+        out = run_bench(["--dump-outputs", str(dumps[-1])], plain)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+            assert key in out, key
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["timed_regions"] == 1 and out["value"] > 0
+        assert abs(out["timed_total_s"] - 3 * out["ms_per_step"] / 1e3) < 2e-3
+        assert out["metric"].startswith("Gbases/sec classified") and out["unit"] == "Gbases/s" and out["higher_is_better"] is True
+        for key in ("roofline", "parity", "kernel_resident", "cpu_baseline", "sweep", "pipeline_variants", "realistic_lists", "strong_90gbp"):
+            assert key not in out, key
+    got = [{f.name: np.load(f) for f in d.iterdir()} for d in dumps]
+    assert sorted(got[0]) == ["bins.npy", "counts.npy", "score_a.npy", "score_b.npy"]
+    assert sum(f.stat().st_size for f in dumps[0].iterdir()) <= 64 << 20
+    for name, a in got[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, got[1][name]), name
+    counts, bins = got[0]["counts.npy"], got[0]["bins.npy"]
+    assert counts.shape == (8192, 2) and counts.sum() > 0 and set(np.unique(bins)) <= {0.0, 1.0, 2.0}
+    # the dumped bins are the CLI's decision on the dumped counts
+    from trio_binning_amd import kmers
+
+    sa, sb, b = kmers.score_and_bin(counts.astype(np.int32), 3000000, 3000000)
+    assert np.array_equal(sa, got[0]["score_a.npy"]) and np.array_equal(sb, got[0]["score_b.npy"])
+    assert np.array_equal(np.frombuffer(b, dtype=np.uint8), np.frombuffer(b"ABU", dtype=np.uint8)[bins.astype(np.int64)])
 
 
 def test_bench_line_contract():

@@ -9,7 +9,7 @@ for lib in $(ls $V/*.so); do
   for e in "${ENVS[@]}"; do
   for lists in uniform haplotypes; do
     echo -n "$(basename $lib) $e $lists: "
-    env $e TBK_LIBRARY=$lib timeout 600 python bench.py --lists $lists --steps 10 --warmup 2 --no-cpu-baseline --no-streaming $AB_FLAGS 2>&1 | tail -1 | python -c "
+    env $e TBK_LIBRARY=$lib timeout 600 python bench.py --full --lists $lists --steps 10 --warmup 2 --no-cpu-baseline --no-streaming $AB_FLAGS 2>&1 | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print(d['roofline']['kernel_ms_avg'], d['roofline']['kernel_only_gbases_per_s'], d['value'], d['config']['table_load'], d['config']['bucket_select'], d['config'].get('keys_in_other_half_of_home_line'), d['config'].get('keys_outside_home_line'))"
   done

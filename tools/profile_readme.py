@@ -132,15 +132,15 @@ full = [t for t in trace if "tbk_probe_kernel" in t["kernel"] or "tbk_probe_entr
 out = [f"# Reference profile of round {rnd[1:].lstrip('0')} ({rnd})", "",
        "Made by `tools/gpu_profile.sh` on one MI355X box (ROCm 7.2), condensed by `tools/profile_summary.py`, and this file by",
        "`tools/profile_readme.py` from the JSON lines beside it - no number here is typed by hand.  Box-to-box spread of the pool: +-4 %.", "",
-       "    python bench.py                                  -> bench_default.json (host-fed value, kernel_resident, pipeline variants, cpu_baseline, parity)",
-       "    python bench.py --lists haplotypes               -> bench_haplotypes.json (lists shaped like real find-unique-kmers output)",
-       "    python bench.py --gpus 2 --share-device          -> bench_2ranks_shared_device.json (two ranks on the one GPU: plumbing of the N > 1 line)",
-       "    python -m torch.distributed.run ... bench.py --gpus 2 --share-device   -> bench_2ranks_torchrun.json (the driver's launcher)",
-       "    python bench.py --gpus 8 --share-device --kmers-per-list 30000000 ...  -> bench_8ranks_shared_device.json (eight ranks, eight tables, one GPU)",
-       "    python bench.py --scaling strong --strong-reads 6000000 --steps 2      -> bench_strong.json (BASELINE configs[2]: the 90 Gbp set, host-fed, one rank)",
-       "    python bench.py --path count                     -> bench_count.json",
-       "    rocprofv3 --kernel-trace --stats -- python3 bench.py                   -> kernel_stats.csv, kernel_trace_by_launch_size.json",
-       "    rocprofv3 --kernel-trace --pmc <one set per run> -- python3 bench.py [--lists haplotypes] --steps 4 --warmup 1 ...   -> pmc_summary_<lists>.json", "",
+       "    python bench.py --full                                  -> bench_default.json (host-fed value, kernel_resident, pipeline variants, cpu_baseline, parity)",
+       "    python bench.py --full --lists haplotypes               -> bench_haplotypes.json (lists shaped like real find-unique-kmers output)",
+       "    python bench.py --full --gpus 2 --share-device          -> bench_2ranks_shared_device.json (two ranks on the one GPU: plumbing of the N > 1 line)",
+       "    python -m torch.distributed.run ... bench.py --full --gpus 2 --share-device   -> bench_2ranks_torchrun.json (the driver's launcher)",
+       "    python bench.py --full --gpus 8 --share-device --kmers-per-list 30000000 ...  -> bench_8ranks_shared_device.json (eight ranks, eight tables, one GPU)",
+       "    python bench.py --full --scaling strong --strong-reads 6000000 --steps 2      -> bench_strong.json (BASELINE configs[2]: the 90 Gbp set, host-fed, one rank)",
+       "    python bench.py --full --path count                     -> bench_count.json",
+       "    rocprofv3 --kernel-trace --stats -- python3 bench.py --full                   -> kernel_stats.csv, kernel_trace_by_launch_size.json",
+       "    rocprofv3 --kernel-trace --pmc <one set per run> -- python3 bench.py --full [--lists haplotypes] --steps 4 --warmup 1 ...   -> pmc_summary_<lists>.json", "",
        "Workload: bench.py defaults = k = 21, 2 x 3e8 keys, 262144 x 15 kb reads (3.932 Gbases) per step, 20 steps per timed region.", "",
        "| | uniform lists (BASELINE) | haplotype-shaped lists |", "|---|---|---|"]
 out += [f"| {r} | {a} | {b} |" for r, a, b in zip(rows, cu, ch)]
