@@ -3,6 +3,7 @@ the GPU path): stdout TSV and decompressed bins must equal what the real referen
 produced (tests/golden/toy_cli.json, diff_vectors.json)."""
 import gzip
 import hashlib
+import io
 import os
 from unittest.mock import patch
 
@@ -193,3 +194,105 @@ def readfq_names(path):
     with gzip.open(path, "rt") as fh:
         for rec in readfq(fh):
             yield rec.name
+
+
+def _rc(s: bytes) -> bytes:
+    return s[::-1].translate(bytes.maketrans(b"ACGT", b"TGCA"))
+
+
+@pytest.fixture(scope="module")
+def uneven_workload(tmp_path_factory):
+    """k = 21; two 5 Mb haplotypes (B is A with 1 % of its positions changed) and 2 x 10^5 k-mers of each that the other lacks;
+    ~3000 FASTQ reads with HiFi-like qualities from either haplotype (either strand) or from neither: log-normal lengths around
+    8 kb, four of 2-5 Mb, some shorter than k.  Written as bgzf, as one ordinary gzip member and plain.  Expected: the oracle's
+    counts, scores and bins, the TSV the reference prints from them, and each bin's text as the Python mirror writes it."""
+    import numpy as np
+
+    import oracle
+    from trio_binning_amd import seq
+    from test_gpu_inflate import bgzf
+
+    d = tmp_path_factory.mktemp("uneven")
+    rng = np.random.default_rng(2024)
+    k, G = 21, 5_000_000
+    lut = np.frombuffer(b"ACGT", dtype=np.uint8)
+    ha = rng.integers(0, 4, G).astype(np.uint8)
+    hb = ha.copy()
+    snp = np.unique(rng.integers(0, G, G // 100))
+    hb[snp] = (hb[snp] + rng.integers(1, 4, snp.size)) % 4
+    A, B = lut[ha].tobytes(), lut[hb].tobytes()
+    near = np.zeros(G, dtype=bool)   # k-mer starts whose window holds a changed position: present in one haplotype only
+    for o in range(k):
+        near[np.clip(snp - o, 0, G - k)] = True
+    starts = np.flatnonzero(near)
+    for name, hap in (("la.txt", A), ("lb.txt", B)):
+        pick = np.sort(rng.choice(starts, 200_000, replace=False))
+        (d / name).write_bytes(b"".join(hap[p:p + k] + b"\n" for p in pick))
+    lens = np.clip(rng.lognormal(np.log(8000), 0.6, 3000), 1, 60_000).astype(np.int64)
+    short = rng.random(lens.size) < 0.02
+    lens[short] = rng.integers(1, k, int(short.sum()))
+    lens[[400, 1100, 1900, 2600]] = [2_000_000, 4_900_000, 3_100_000, 2_500_000]
+    recs = []
+    for i, L in enumerate(lens):
+        L = int(L)
+        src = rng.integers(0, 3)
+        if src == 2:
+            s = lut[rng.integers(0, 4, L)].tobytes()
+        else:
+            p = int(rng.integers(0, G - L))
+            s = (A, B)[src][p:p + L]
+            if rng.random() < 0.5:
+                s = _rc(s)
+        qv = np.clip(rng.normal(60, 15, L), 2, 93).astype(np.uint8)
+        qv[rng.random(L) < 0.6] = 93
+        recs.append(b"@r%d/ccs len=%d\n" % (i, L) + s + b"\n+\n" + (qv + 33).tobytes() + b"\n")
+    text = b"".join(recs)
+    del recs
+    (d / "reads.fastq").write_bytes(text)
+    (d / "reads.fastq.gz").write_bytes(gzip.compress(text, 1))
+    (d / "reads.bgzf.fastq.gz").write_bytes(bgzf(text, level=1))
+    del text
+    reads = list(seq.open_fastx_read(str(d / "reads.fastq")))
+    assert len(reads) == 3000 and 30e6 < sum(len(r.seq) for r in reads) < 50e6
+    orc = oracle.load()
+    ta, tb = orc.table_from_file(str(d / "la.txt")), orc.table_from_file(str(d / "lb.txt"))
+    bases = np.frombuffer(b"".join(r.seq.encode() for r in reads), dtype=np.uint8)
+    offsets = np.zeros(len(reads) + 1, dtype=np.uint64)
+    np.cumsum([len(r.seq) for r in reads], out=offsets[1:])
+    counts = orc.count_batch(bases, offsets, ta, tb, threads=16)
+    sa, sb, bins = orc.score_and_bin(counts, ta.num_kmers, tb.num_kmers)
+    assert {"A", "B", "U"} <= set(bins) and bins.count("A") > 500 and bins.count("B") > 500
+    tsv = "".join("\t".join(map(str, [r.name, c, float(x), float(y)])) + "\n" for r, c, x, y in zip(reads, bins, sa, sb))
+    want = {}
+    for letter, fn in (("A", "hapA.fastq.gz"), ("B", "hapB.fastq.gz"), ("U", "unc.fastq.gz")):
+        buf = io.StringIO()
+        for r, c in zip(reads, bins):
+            if c == letter:
+                r.print(file=buf)
+        want[fn] = buf.getvalue().encode()
+    return d, tsv, want
+
+
+@pytest.mark.parametrize("encoder", ["gpu", "cpu"])
+@pytest.mark.parametrize("sizes", ["default", "small"])
+@pytest.mark.parametrize("reads_name", ["reads.bgzf.fastq.gz", "reads.fastq.gz", "reads.fastq"])
+def test_default_cli_on_uneven_reads(gpu, capsys, tmp_path, monkeypatch, uneven_workload, reads_name, sizes, encoder):
+    """The default command line (gzip'ed bins) on ~42 Mbases of uneven reads, from bgzf (the device inflater), one gzip member (the
+    host inflater) and plain text; with the default sizes and with small inflater windows and batches (remnant batches, flushes of
+    changing size); the members coded on the device or on the host.  stdout and the decompressed bins equal the oracle's."""
+    import trio_binning_amd.classify_by_kmers as cbk
+
+    d, tsv, want = uneven_workload
+    monkeypatch.setenv("TBK_GZIP_ENCODER", encoder)
+    if sizes == "small":
+        monkeypatch.setenv("TBK_BGZF_GPU_WINDOW", str(1 << 20))
+        monkeypatch.setattr(cbk, "_BATCH_BASES", 1_500_000)
+        monkeypatch.setattr(cbk, "_BATCH_READS", 300)
+    od = tmp_path / "out"
+    od.mkdir()
+    out = _run([str(d / reads_name), str(d / "la.txt"), str(d / "lb.txt"), "--haplotype-a-out-prefix", str(od / "hapA"),
+                "--haplotype-b-out-prefix", str(od / "hapB"), "--unclassified-out-prefix", str(od / "unc")], capsys)
+    assert out == tsv
+    assert sorted(os.listdir(od)) == sorted(want)
+    for fn, body in want.items():
+        assert gzip.open(od / fn, "rb").read() == body, fn

@@ -63,6 +63,18 @@ def test_members_inflate_to_their_text(gpu):
     while len(fib) < 24:
         fib.append(fib[-1] + fib[-2])
     pieces.append(b"".join(bytes([33 + i]) * c for i, c in enumerate(fib))[:30000])
+    # lengths around the 32-byte text word and the 8 KiB block (and its multiples), each starting at an odd offset in the job's text
+    blob = fastq(rng, 40, 3000, "hifi")
+    for L in (31, 32, 33, 8191, 8192, 8193, 16383, 16384, 16385, 32767, 32768, 32769, 65535, 65536, 65537):
+        at = sum(map(len, pieces))
+        pieces.append(blob[7:7 + (3 if at % 2 == 0 else 2) + L % 5 * 2])   # (odd, whatever the lengths so far)
+        assert (at + len(pieces[-1])) % 2 == 1
+        o = int(rng.integers(0, len(blob) - L))
+        pieces.append(blob[o:o + L])
+    # FASTQ whose lines are 8190-8194 bytes with their newline: the block cutter decides right at a line end
+    for L in (8189, 8190, 8191, 8192, 8193):
+        pieces.append(fastq(rng, 6, L, "hifi"))
+        pieces.append(fastq(rng, 6, L, "const"))
     members = seq.gzip_members_device(pieces)
     check_members(pieces, members)
     # the encoder shrinks what can be shrunk: 2 bits a base + the qualities' entropy, a few bits per 128-byte stretch of a run
@@ -193,3 +205,202 @@ def test_bin_writer_on_the_device_equals_the_python_writer(gpu, tmp_path):
         assert got_n == len(parsed)
         for py_name, nat_name in zip(seq.output_names(str(tmp_path / f"pa{trial}"), str(tmp_path / f"pb{trial}"), str(tmp_path / f"pu{trial}"), ".fq", True), w.names):
             assert gzip.open(nat_name, "rb").read() == gzip.open(py_name, "rb").read(), nat_name
+
+
+# ---- the ring around the encoder: uneven flushes, sinks that fall behind or go away ------------------------------------------------
+# The bin writer's device path (tbk_fastx.cpp, flush_bins_gpu) keeps three jobs in flight; a collected job's members are written by
+# one thread per bin (the lanes) straight from the job's pinned buffer, and that buffer is the one the job three submits later uses
+# (and grows, when it needs more room).  Bins that are FIFOs drained slowly keep the lanes behind the writer.
+
+def _uneven_records(rng, seq):
+    """~32 Mbases of FASTQ (and some FASTA) records: log-normal lengths, a few of 2-4 MB (longer than a 1 MiB member: members are
+    cut inside them and what is left over moves across the text buffers' swap), and a run of ordinary ones first."""
+    lut = np.frombuffer(b"ACGT", dtype=np.uint8)
+    lens = np.clip(rng.lognormal(np.log(6000), 0.7, 3400), 0, 80_000).astype(np.int64)
+    lens[rng.random(lens.size) < 0.01] = 0
+    long_at = {900: 2_100_000, 1400: 3_900_000, 2300: 2_700_000, 3000: 3_300_000}
+    recs = []
+    for i, L in enumerate(lens):
+        L = long_at.get(i, int(L))
+        s = lut[rng.integers(0, 4, L)].tobytes().decode()
+        if i % 23 == 5:
+            q = None
+        else:
+            qv = np.clip(rng.normal(60, 15, L), 2, 93).astype(np.uint8)
+            qv[rng.random(L) < 0.6] = 93
+            q = (qv + 33).tobytes().decode()
+        recs.append(seq.Read(f"r{i}/ccs", s, q))
+    return recs
+
+
+# (max_bases per batch, which bins its records go to): four whole batches of ~3 MB of text to one bin each (every one a job of two
+# members: the slots' first buffers), then ~12 MB (slot 1 must grow while the lanes still write job 1), two small ones that code
+# nothing for A, ~30 MB all to A (growing again), then the rest in 2 Mbase batches; U stays empty throughout
+_UNEVEN = [(1_500_000, "A"), (1_500_000, "B"), (1_500_000, "A"), (1_500_000, "B"), (6_000_000, "ab"), (150_000, "B"), (150_000, "B"),
+           (15_000_000, "A")]
+
+
+def _uneven_letters(bi, n):
+    how = _UNEVEN[bi][1] if bi < len(_UNEVEN) else "ab"
+    if how in ("A", "B"):
+        return how * n
+    r = np.random.default_rng(500 + bi)
+    return "".join(np.where(r.random(n) < 0.7, "A", "B"))
+
+
+def _write_uneven(seq, src, prefixes):
+    """The records of `src` through seq.BinWriter(device=0) in the batches of _UNEVEN; returns the bins' letters, record by record."""
+    w = seq.BinWriter(*prefixes, ".fq", True, device=0)
+    letters = []
+    try:
+        assert w.gpu_encoder
+        with seq.BatchReader(str(src)) as r:
+            b = seq.Batch()
+            bi = 0
+            while r.next_batch(b, _UNEVEN[bi][0] if bi < len(_UNEVEN) else 2_000_000, 0):
+                x = _uneven_letters(bi, b.n_reads)
+                w.write(b, x.encode())
+                letters.append(x)
+                bi += 1
+        assert bi > len(_UNEVEN)
+    finally:
+        w.close()
+    return "".join(letters)
+
+
+class _SlowDrains:
+    """A reader thread per FIFO that takes `chunk` bytes every `pause` seconds (`stop_after`: closes its end after that many bytes).
+    Whatever happens to the test, `finish()` lets the threads read at full speed, unblocks any still waiting for a writer and joins
+    them with a time limit."""
+
+    def __init__(self, paths, chunk=16 << 10, pause=0.005, stop_after=None):
+        import threading
+
+        self.paths, self.got, self.errors = list(paths), {}, []
+        self.hurry = threading.Event()
+        self.opened = [threading.Event() for _ in self.paths]
+        self.threads = []
+        for i, p in enumerate(self.paths):
+            os.mkfifo(p)
+            t = threading.Thread(target=self._drain, args=(i, chunk, pause, (stop_after or {}).get(i)), daemon=True)
+            t.start()
+            self.threads.append(t)
+
+    def _drain(self, i, chunk, pause, stop_after):
+        buf = bytearray()
+        try:
+            with open(self.paths[i], "rb", buffering=0) as fh:
+                self.opened[i].set()
+                while stop_after is None or len(buf) < stop_after:
+                    piece = fh.read(chunk)
+                    if not piece:
+                        break
+                    buf += piece
+                    self.hurry.wait(pause)
+        except Exception as e:  # noqa: BLE001  (reported by finish())
+            self.errors.append(e)
+        self.got[i] = bytes(buf)
+
+    def finish(self, limit=60):
+        self.hurry.set()
+        for i, p in enumerate(self.paths):
+            if not self.opened[i].is_set():   # (the writer never opened this one: a writer end of our own lets the reader go)
+                try:
+                    os.close(os.open(p, os.O_WRONLY | os.O_NONBLOCK))
+                except OSError:
+                    pass
+        for t in self.threads:
+            t.join(limit)
+        assert not any(t.is_alive() for t in self.threads), "a drain thread did not end"
+        assert not self.errors, self.errors
+
+
+def _python_bins(seq, tmp_path, src, letters, tag):
+    """What the Python mirror of the reference's writer (seq.open_outfiles + Read.print) puts in each bin, as text."""
+    names = [str(tmp_path / f"{tag}{x}") for x in ("a", "b", "u")]
+    outs = seq.open_outfiles(*names, ".fq", False)
+    n = 0
+    for r, c in zip(seq.open_fastx_read(str(src)), letters):
+        r.print(file=outs["ABU".index(c)])
+        n += 1
+    for fh in outs:
+        fh.close()
+    assert n == len(letters)
+    return [open(nm, "rb").read() for nm in seq.output_names(*names, ".fq", False)]
+
+
+def test_uneven_flushes_into_slow_fifos(gpu, tmp_path):
+    """Bins that are FIFOs read slowly (16 KiB every 5 ms), fed by flushes of very different sizes: a job slot must grow while the lanes
+    still write the members collected from it.  Each bin's decompressed stream equals the Python mirror's bytes; then the same
+    sequence into regular files, the control."""
+    from trio_binning_amd import seq
+
+    recs = _uneven_records(np.random.default_rng(23), seq)
+    src = tmp_path / "in.fq"
+    with open(src, "w") as fh:
+        for r in recs:
+            r.print(file=fh)
+    del recs
+    prefixes = [str(tmp_path / f"f{x}") for x in ("a", "b", "u")]
+    drains = _SlowDrains(seq.output_names(*prefixes, ".fq", True))
+    try:
+        letters = _write_uneven(seq, src, prefixes)
+    finally:
+        drains.finish()
+    assert "U" not in letters and letters.count("A") > 100 and letters.count("B") > 100
+    want = _python_bins(seq, tmp_path, src, letters, "p")
+    assert want[2] == b"" and len(want[0]) > 30_000_000
+    for i in range(3):
+        assert gzip.decompress(drains.got[i]) == want[i], "ABU"[i]
+    control = [str(tmp_path / f"c{x}") for x in ("a", "b", "u")]
+    assert _write_uneven(seq, src, control) == letters
+    for i, nm in enumerate(seq.output_names(*control, ".fq", True)):
+        assert gzip.open(nm, "rb").read() == want[i], nm
+
+
+def test_a_sink_that_goes_away_fails_the_writer(gpu, tmp_path):
+    """The reader of bin B closes its end after ~200 kB: the lane's write gets EPIPE (Python ignores SIGPIPE), and BinWriter.write or
+    close raises the library's I/O error (OSError) naming it - promptly, with nothing hanging; the device is left usable (a later
+    job round-trips)."""
+    import time
+
+    from trio_binning_amd import seq
+
+    recs = _uneven_records(np.random.default_rng(29), seq)[:2000]
+    src = tmp_path / "in.fq"
+    with open(src, "w") as fh:
+        for r in recs:
+            r.print(file=fh)
+    prefixes = [str(tmp_path / f"f{x}") for x in ("a", "b", "u")]
+    drains = _SlowDrains(seq.output_names(*prefixes, ".fq", True), pause=0.001, stop_after={1: 200_000})
+    failed, w = None, None
+    t0 = time.monotonic()
+    try:
+        w = seq.BinWriter(*prefixes, ".fq", True, device=0)
+        assert w.gpu_encoder
+        try:
+            with seq.BatchReader(str(src)) as r:
+                b = seq.Batch()
+                while r.next_batch(b, 1_000_000, 0):
+                    w.write(b, ("AB" * b.n_reads)[:b.n_reads].encode())
+        except OSError as e:
+            failed = e
+        t1 = time.monotonic()
+        try:
+            w.close()
+        except OSError as e:
+            failed = failed or e
+        assert time.monotonic() - t1 < 30, "close() took too long"
+    finally:
+        if w is not None:   # (the readers see the end of their FIFOs only once the writer has closed them)
+            try:
+                w.close()
+            except OSError:
+                pass
+        drains.finish()
+    assert failed is not None, "the writer returned as if the bin had been written"
+    assert "write" in str(failed) and "Broken pipe" in str(failed), str(failed)
+    assert time.monotonic() - t0 < 120
+    assert len(drains.got[1]) >= 200_000
+    pieces = [b"@x\nACGT\n+\nIIII\n" * 5000, b"", bytes(range(256)) * 100]
+    check_members(pieces, seq.gzip_members_device(pieces))

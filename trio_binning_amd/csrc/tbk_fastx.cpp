@@ -1934,6 +1934,7 @@ struct BinFile {
     uint64_t file_off = 0;  // bytes written so far (this descriptor's own offset: plain output is written with pwrite)
     bool positional = false;  // a regular file no other bin names: slices may go out with pwrite from several threads;
                               // anything else (FIFO, /dev/stdout, two prefixes naming one file) gets sequential write()
+    bool shared = false;      // another bin names the same file
     TextBuf text;           // records not yet written
     TextBuf alt;            // the GPU encoder's second buffer: `text` and `alt` change places at every flush, so that the next batch is gathered
                             // while the device is still fetching this one's text
@@ -2050,12 +2051,21 @@ struct Piece { int bin; const char *src; size_t n; std::vector<char> out; bool o
 
 static inline double wall_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// finished members to their bins' files: each bin's are handed to its lane in order (the lanes of the three bins run side by side)
-static int hand_to_lanes(tbk_bin_writer *w, const std::vector<tbk_gdeflate_out> &outs) {
+// until the lanes have written all they were handed; then a lane's failed write is the caller's error
+static int wait_for_lanes(tbk_bin_writer *w) {
     const double t0 = wall_now();
-    for (IoLane &l : w->lane) l.idle();  // (the bytes handed over last time are on their way to being reused)
+    for (IoLane &l : w->lane) l.idle();
     w->gpu_io_wait_s += wall_now() - t0;
     for (IoLane &l : w->lane) if (!l.err.empty()) return ffail(TBK_ERR_IO, "%s", l.err.c_str());
+    return TBK_OK;
+}
+
+// finished members to their bins' files: each bin's are handed to its lane in order (the lanes of the three bins run side by side).
+// The lanes write them from the encoder's pinned memory (tbk_gdeflate_collect's bytes): they must be idle before the next
+// tbk_gdeflate_submit, which may reuse or free that memory (flush_bins_gpu waits there).
+static int hand_to_lanes(tbk_bin_writer *w, const std::vector<tbk_gdeflate_out> &outs) {
+    const int rc = wait_for_lanes(w);
+    if (rc) return rc;
     for (size_t i = 0; i < outs.size();) {
         size_t k = i;
         size_t n = outs[i].n;
@@ -2075,6 +2085,10 @@ static int flush_bins_gpu(tbk_bin_writer *w, bool final, std::vector<Piece> &pie
     int rc = TBK_OK;
     bool swapped = false;
     if (!pieces.empty()) {
+        // the members the lanes were handed last time lie in the job slot this submit takes over, and a submit that needs more room
+        // there frees that memory: the lanes finish them first (the device is still coding the job before, meanwhile)
+        rc = wait_for_lanes(w);
+        if (rc) return rc;
         double t0 = wall_now();
         std::vector<tbk_gdeflate_member> members;
         members.reserve(pieces.size());
@@ -2127,8 +2141,8 @@ static int flush_bins_gpu(tbk_bin_writer *w, bool final, std::vector<Piece> &pie
             if (rc) return rc;
             if (!outs.empty()) { rc = hand_to_lanes(w, outs); if (rc) return rc; }
         }
-        for (IoLane &l : w->lane) l.idle();
-        for (IoLane &l : w->lane) if (!l.err.empty()) return ffail(TBK_ERR_IO, "%s", l.err.c_str());
+        rc = wait_for_lanes(w);
+        if (rc) return rc;
     }
     if (!swapped)
         for (int b = 0; b < 3; b++) {
@@ -2247,7 +2261,7 @@ extern "C" int tbk_bin_writer_open(const char *path_a, const char *path_b, const
     }
     for (int b = 0; b < 3; b++)
         for (int c = 0; c < 3; c++)
-            if (c != b && have[b] && have[c] && st[b].st_dev == st[c].st_dev && st[b].st_ino == st[c].st_ino) w->bin[b].positional = false;
+            if (c != b && have[b] && have[c] && st[b].st_dev == st[c].st_dev && st[b].st_ino == st[c].st_ino) w->bin[b].positional = false, w->bin[b].shared = true;
     *out = w;
     return TBK_OK;
 }
@@ -2413,8 +2427,9 @@ extern "C" int tbk_bin_writer_use_device(tbk_bin_writer *w, int device) {
     const char *enc = getenv("TBK_GZIP_ENCODER");
     if ((enc && (strcmp(enc, "cpu") == 0 || strcmp(enc, "zlib") == 0)) || getenv("TBK_GZIP_STRATEGY") || w->level == 0) return TBK_OK;
     for (int b = 0; b < 3; b++) if (w->bin[b].text.size()) return ffail(TBK_ERR_STATE, "tbk_bin_writer_use_device after the first write");
-    // (two prefixes naming one file: the lanes would interleave their writes where the reference's handles do not)
-    for (int b = 0; b < 3; b++) if (!w->bin[b].positional) return TBK_OK;
+    // (two prefixes naming one file: the lanes would interleave their writes where the reference's handles do not; a FIFO or
+    // another target that cannot seek is fine, a lane writes its bin in order)
+    for (int b = 0; b < 3; b++) if (w->bin[b].shared) return TBK_OK;
     int rc = tbk_gdeflate_create(device, &w->gpu);
     if (rc) return rc;
     for (int b = 0; b < 3; b++) { w->bin[b].text.release(); w->bin[b].text.pinned = true; w->lane[b].start(w->bin[b].fd); }

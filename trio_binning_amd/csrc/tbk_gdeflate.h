@@ -15,8 +15,9 @@ void tbk_gdeflate_destroy(tbk_gdeflate *g);
 int tbk_gdeflate_submit(tbk_gdeflate *g, const tbk_gdeflate_member *members, size_t n_members);
 void tbk_gdeflate_set_crc(tbk_gdeflate *g, size_t member, uint32_t crc);
 int tbk_gdeflate_text_done(tbk_gdeflate *g, int back = 0);   // back: how many jobs before the newest
-// Move the pipeline on and take the oldest finished job's members (none when nothing is ready and !drain); the bytes stay valid
-// until the call after the next one.
+// Move the pipeline on and take the oldest finished job's members (none when nothing is ready and !drain).  The bytes lie in the
+// job's pinned buffer and stay valid until the next tbk_gdeflate_submit, which may take over that job's slot and grow (free) the
+// buffer; further collects leave them alone.
 int tbk_gdeflate_collect(tbk_gdeflate *g, bool drain, std::vector<tbk_gdeflate_out> &out);
 int tbk_gdeflate_in_flight(const tbk_gdeflate *g);
 void tbk_gdeflate_stats(const tbk_gdeflate *g, uint64_t *text_bytes, uint64_t *member_bytes, uint64_t *blocks, uint64_t *members);

@@ -956,7 +956,7 @@ void tbk_gdeflate_set_crc(tbk_gdeflate *g, size_t member, uint32_t crc) {
 }
 
 // Moves the pipeline on: the job before the newest starts its members' journey home; the oldest job in flight (if it has
-// come that far, or `drain`) is handed out.  *out: its members in order - (tag, bytes, length) - valid until the next call.
+// come that far, or `drain`) is handed out.  *out: its members in order - (tag, bytes, length) - valid until the next submit.
 int tbk_gdeflate_collect(tbk_gdeflate *g, bool drain, std::vector<tbk_gdeflate_out> &out) {
     out.clear();
     if (!g) return TBK_OK;
