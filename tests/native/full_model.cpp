@@ -104,10 +104,11 @@ int main(int argc, char **argv) {
     const int w_want = argc > 2 ? atoi(argv[2]) : 8;
     const uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 10) : 1;
     const double per_line = argc > 4 ? atof(argv[4]) : 2.0;   // keys per line the table is sized for
+    const int m_force = argc > 5 ? atoi(argv[5]) : 0;         // the m-mer length pinned (0: what a table of 1e9 keys gets)
     std::mt19937_64 rng(seed);
     Table t;
     t.k = k;
-    t.z = tbk_mz_params(k, w_want, 1000000000ull, 0, 1);
+    t.z = tbk_mz_params(k, w_want, 1000000000ull, m_force, 1);
     if (!tbk_full_geom(k, t.z) || t.z.t != t.z.m - t.z.w) { printf("k=%d w=%d: no full keys (w=%d m=%d o=%d t=%d)\n", k, w_want, t.z.w, t.z.m, t.z.o, t.z.t); return 0; }
     const uint64_t kmask = (1ull << (2 * k)) - 1ull;
     const int G = 50000;

@@ -79,9 +79,22 @@ def test_full_key_model_equals_set_membership(full_model, k, w, per_line):
     tbk_next_bucket; tbk_full_lookup_one(..., as_window = 0 and 1) must both equal set membership - at crowded loads too (up to
     twelve keys per line asked for: lines fill and keys walk), list keys through every tied position, near misses that share
     a line with them, windows of both strands."""
+    _run_full_model(full_model, k, w, per_line)
+
+
+@pytest.mark.parametrize("k,w,m,per_line", [(31, 8, 20, 2.0), (31, 8, 22, 6.0), (31, 8, 24, 12.0), (31, 2, 18, 6.0), (31, 3, 19, 2.0), (29, 8, 22, 12.0), (30, 8, 23, 6.0), (25, 6, 20, 12.0)])
+def test_full_key_model_at_pinned_m_mers(full_model, k, w, m, per_line):
+    """The same claims with m pinned: m-mers of 20 to 24 bases (a table of 1e9 keys gets 18 at k = 31) and t = m - w = 16,
+    where the t-mer rank takes the whole 32-bit t-mer (tbk_tmer_rank)."""
+    _run_full_model(full_model, k, w, per_line, m)
+
+
+def _run_full_model(full_model, k, w, per_line, m=0):
     for seed in (1, 2):
-        r = subprocess.run([full_model, str(k), str(w), str(seed), str(per_line)], capture_output=True, text=True)
+        r = subprocess.run([full_model, str(k), str(w), str(seed), str(per_line)] + ([str(m)] if m else []), capture_output=True, text=True)
         assert r.returncode == 0, (r.stdout, r.stderr)
         assert r.stdout.startswith("full ") and "mismatches 0" in r.stdout and "as_window disagreements 0" in r.stdout, r.stdout
+        if m:
+            assert r.stdout.startswith(f"full k={k} w={w} m={m} ") and f" t={m - w}:" in r.stdout, r.stdout   # the span asked for, not a shorter one
         if per_line >= 6:
             assert " 0 walks past a line" not in r.stdout, r.stdout

@@ -674,6 +674,35 @@ def test_lists_choose_the_line_layout(gpu, orc, monkeypatch):
         monkeypatch.delenv("TBK_FRONT")
 
 
+def _boundary_case(rng, k):
+    """Lists and reads whose cuts test passes that touch exactly two reads (test_two_read_passes_at_every_boundary_offset):
+    the keys of both lists (canonical) and reads that are consecutive pieces of one genome."""
+    from trio_binning_amd import kmers
+
+    genome = "".join("ACGT"[c] for c in rng.integers(0, 4, 400_000))
+    # every other k-mer of the genome is in a list: reads cut from it hit in nearly every window
+    starts = rng.permutation(len(genome) - k)[:60_000]
+    la = [genome[p:p + k] for p in starts[:30_000]]
+    lb = [genome[p:p + k] for p in starts[30_000:]]
+    canon = lambda x: min(x, _rc(x))
+    ka = np.array([kmers.kmer_to_int(canon(x)) for x in la], dtype=np.uint64)
+    kb = np.array([kmers.kmer_to_int(canon(x)) for x in lb], dtype=np.uint64)
+    # consecutive pieces of the genome: cut where one read ends the next begins, so a window over the cut would be a
+    # genome k-mer (a hit) if the kernel let it through.  Piece lengths put the cuts on every offset mod 32, at
+    # distance 1 .. k from both ends of a pass, and leave passes with exactly two reads between longer reads.
+    lengths = []
+    for d in list(range(0, 34)) + [2048 - 1, 2048 - k, 2048 - k + 1, 1, k - 1, k, k + 1]:
+        lengths += [2048 + 700 + d, 2048 * 2 - 700]
+    lengths += [15000] * 6 + [2048] * 3 + [4096 + 5, 2043, 33, 2048 * 3 - 38]
+    reads, at = [], 0
+    for n in lengths:
+        if at + n > len(genome):
+            at = int(rng.integers(0, 1000))
+        reads.append(genome[at:at + n])
+        at += n
+    return ka, kb, reads
+
+
 @pytest.mark.parametrize("k,front", [(21, 1), (21, 0), (31, 1), (16, 1)])
 def test_two_read_passes_at_every_boundary_offset(gpu, orc, monkeypatch, k, front):
     """Passes that touch exactly two reads run through a kernel of their own: the boundary is folded into the lanes'
@@ -688,29 +717,9 @@ def test_two_read_passes_at_every_boundary_offset(gpu, orc, monkeypatch, k, fron
         monkeypatch.delenv(v, raising=False)
     monkeypatch.setenv("TBK_FRONT", str(front))
     rng = np.random.default_rng(100 * k + front)
-    genome = "".join("ACGT"[c] for c in rng.integers(0, 4, 400_000))
-    # every other k-mer of the genome is in a list: reads cut from it hit in nearly every window
-    starts = rng.permutation(len(genome) - k)[:60_000]
-    la = [genome[p:p + k] for p in starts[:30_000]]
-    lb = [genome[p:p + k] for p in starts[30_000:]]
-    canon = lambda x: min(x, _rc(x))
-    ka = np.array([kmers.kmer_to_int(canon(x)) for x in la], dtype=np.uint64)
-    kb = np.array([kmers.kmer_to_int(canon(x)) for x in lb], dtype=np.uint64)
+    ka, kb, reads = _boundary_case(rng, k)
     oa, ob = orc.table_from_keys(ka, k), orc.table_from_keys(kb, k)
     a, b = kmers.HashSet.from_keys(ka, k), kmers.HashSet.from_keys(kb, k)
-    # consecutive pieces of the genome: cut where one read ends the next begins, so a window over the cut would be a
-    # genome k-mer (a hit) if the kernel let it through.  Piece lengths put the cuts on every offset mod 32, at
-    # distance 1 .. k from both ends of a pass, and leave passes with exactly two reads between longer reads.
-    lengths = []
-    for d in list(range(0, 34)) + [2048 - 1, 2048 - k, 2048 - k + 1, 1, k - 1, k, k + 1]:
-        lengths += [2048 + 700 + d, 2048 * 2 - 700]
-    lengths += [15000] * 6 + [2048] * 3 + [4096 + 5, 2043, 33, 2048 * 3 - 38]
-    reads, at = [], 0
-    for n in lengths:
-        if at + n > len(genome):
-            at = int(rng.integers(0, 1000))
-        reads.append(genome[at:at + n])
-        at += n
     for slice_bases in ("2048", str(1 << 30)):   # an empty ring takes the batch slice by slice / in one piece
         monkeypatch.setenv("TBK_SLICE_BASES", slice_bases)
         for order in (reads, reads[::-1]):
