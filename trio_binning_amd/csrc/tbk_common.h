@@ -37,6 +37,7 @@
 // c/kmers.c:255).
 #pragma once
 #include <stdint.h>
+#include "tbk_tmer_order.h"
 
 #ifdef __HIPCC__
 #define TBK_HD __host__ __device__ __forceinline__
@@ -93,6 +94,10 @@
 //     layouts and short keys take t = m - 2w where that leaves t >= 4 (tbk_mz_span3), l = 3w
 //     positions, density 4/(3w+1) = 0.211 at w = 6; the mirror of position x is l-1-x, and
 //     (l-1-x) mod w = w-1-(x mod w) still.
+//     Any order of the canonical t-mers works as long as every inserter and probe uses the same.
+//     t = 4 (k = 21 at w = 6) ranks its 136 canonical 4-mers in a searched order (tbk_tmer_order.h,
+//     written by tools/tmer_order_search.cpp) that switches buckets ~3 % less often than the hash
+//     order; every other t ranks by tbk_mmer_hash (tbk_tmer_order).
 //
 // Mode "plain" (w = 0): bucket = reduce(mix32(key)), one random line per window.
 struct TbkMz {
@@ -245,13 +250,20 @@ TBK_HD TbkMz tbk_mz_span3(TbkMz z) {
     return z;
 }
 
-// rank of the span's t-mer at position i: the hash with its low 4 (5) bits cleared (they carry a
+// order of a t-mer read as x on one strand and y on the other: for t = 4 the searched order of
+// tbk_tmer_order.h (looked up by x; it already gives x and its reverse complement one rank), for
+// every other t the hash of the canonical t-mer
+TBK_HD uint32_t tbk_tmer_order(uint32_t x, uint32_t y, int t) {
+    return t == 4 ? tbk_tmer4_ranks[x & 0xFFu] : tbk_mmer_hash(x < y ? x : y);
+}
+
+// rank of the span's t-mer at position i: its order with the low 4 (5) bits cleared (they carry a
 // position tag in the probe kernel)
 TBK_HD uint32_t tbk_tmer_rank(uint64_t key, TbkMz z, int i) {
     const uint32_t tmask = z.t == 16 ? 0xFFFFFFFFu : ((1u << (2 * z.t)) - 1u);
     const uint32_t x = (uint32_t)(key >> (2 * (z.o + i))) & tmask;
     const uint32_t y = tbk_revcomp32(x, z.t);
-    return tbk_mmer_hash(x < y ? x : y) & ~tbk_mz_tagmask(z);
+    return tbk_tmer_order(x, y, z.t) & ~tbk_mz_tagmask(z);
 }
 
 // All buckets a lookup of `key` may select: one per position that attains the smallest t-mer

@@ -1627,7 +1627,7 @@ __device__ __forceinline__ void probe_pass_entry(const ProbeArgs &p, const uint6
                                                  const uint64_t P0, const uint64_t r_first, const uint64_t r_first_end, const uint32_t lane,
                                                  uint4 *walkq, uint4 *backq, uint16_t *walkr, uint16_t *backr, uint32_t *rcnt, const uint32_t *tlut) {
     constexpr bool WIDE = KIND == 1, SHORT = KIND == 2, FULL = KIND == 3;
-    constexpr bool TLUT = TBK_TMER_LUT && LW == 3 && W == 6 && !TWO && !MULTI;  // t = 4: a t-mer's rank is a table look-up (tbk_probe_entry_kernel fills the table; the two-read and multi-read kernels, at their register limits, compute)
+    constexpr bool TLUT = TBK_TMER_LUT && LW == 3 && W == 6;  // t = 4: a t-mer's rank is a table look-up (tbk_probe_entry_kernel fills the table)
     const int k = p.k;
     const uint64_t kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1ull);
     const uint32_t sub = lane & 1u;
@@ -1683,9 +1683,9 @@ __device__ __forceinline__ void probe_pass_entry(const ProbeArgs &p, const uint6
     const uint64_t mmask = m >= 32 ? ~0ull : ((1ull << (2 * m)) - 1ull);
     const uint32_t tmask = tlen >= 16 ? 0xFFFFFFFFu : ((1u << (2 * tlen)) - 1u);
     auto tmer_rank = [&](uint64_t fwd64, uint64_t rc64, uint32_t fsh, uint32_t bsh, uint32_t pos) -> uint32_t {
-        if constexpr (TLUT) return tlut[(uint32_t)(fwd64 >> fsh) & 0xFFu] | pos;  // (canonical form, hash and tag mask are in the table)
+        if constexpr (TLUT) return tlut[(uint32_t)(fwd64 >> fsh) & 0xFFu] | pos;  // (canonical form, order and tag mask are in the table)
         const uint32_t x = (uint32_t)(fwd64 >> fsh) & tmask, y = (uint32_t)(rc64 >> bsh) & tmask;
-        return (tbk_mmer_hash(x < y ? x : y) & ~TAGM) | pos;
+        return (tbk_tmer_order(x, y, LW == 3 ? tlen : 0) & ~TAGM) | pos;  // (t = 4 only with 3w positions: tbk_mz_span3)
     };
     {
         const uint64_t fs = ((uint64_t)s1 << 32) | s0, bs = ((uint64_t)t3 << 32) | t2;
@@ -2162,20 +2162,20 @@ tbk_probe_entry_kernel(const ProbeArgs p) {
         const uint64_t e0 = stage[wave][2 * lane], e1 = stage[wave][2 * lane + 1], e2 = stage[wave][2 * lane + 2],
                        e3 = stage[wave][2 * lane + 3];
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if constexpr (TBK_TMER_LUT && LW == 3 && W == 6 && !TWO && !MULTI) {
+        constexpr bool TLUT = TBK_TMER_LUT && LW == 3 && W == 6;
+        if constexpr (TLUT) {
             // The staged tile is in registers: its LDS now holds the ranks of all 256 t-mers (W = 6 with 3w positions: t = m - 12 = 4) -
-            // canonical form, hash and tag mask folded in - so that a window's new t-mer costs the loop one LDS read instead of eleven
-            // vector instructions, one of them a multiply.  The loop runs at 90 % of the vector units' issue rate (EXPERIMENTS.md).
+            // canonical form, searched order (tbk_tmer_order.h) and tag mask folded in - so that a window's new t-mer costs the loop one
+            // LDS read instead of eleven vector instructions or a global load.  The loop runs at 90 % of the vector units' issue rate
+            // (EXPERIMENTS.md).
             uint32_t *lut = reinterpret_cast<uint32_t *>(stage[wave]);
 #pragma unroll
-            for (uint32_t i = 0; i < 4; i++) {
-                const uint32_t x = 4u * lane + i, y = tbk_revcomp32(x, 4);
-                lut[x] = tbk_mmer_hash(x < y ? x : y) & ~31u;
-            }
+            for (uint32_t i = 0; i < 4; i++) lut[lane + 64u * i] = tbk_tmer4_ranks[lane + 64u * i];
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         }
         probe_pass_entry<W, MULTI, TWO, KIND, LW>(p, e0, e1, e2, e3, P0, r_first, r_end, lane, walkq[wave], backq[wave], walkr[wave], backr[wave], rcnt[wave],
                                                   reinterpret_cast<const uint32_t *>(stage[wave]));
+        if (TLUT && MULTI) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the next pass stages its tile over the table)
         if (!MULTI) return;  // one pass per block
     }
 }
