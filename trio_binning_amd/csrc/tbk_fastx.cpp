@@ -296,8 +296,8 @@ struct LineSource {
             if (bs < 26) { err = "corrupt BGZF block"; return -1; }
             if (p + bs > avail) break;
             const uint8_t *b = zbase + p;
-            const size_t xlen = b[10] | ((size_t)b[11] << 8), hdr = 12 + xlen;
-            if (hdr + 8 > bs) { err = "corrupt BGZF block"; return -1; }
+            const size_t hdr = tbk_gzip_header_len(b, bs);   // (FNAME, FCOMMENT and FHCRC may follow the extra field)
+            if (!hdr) { err = "corrupt BGZF block"; return -1; }
             const uint32_t crc = (uint32_t)b[bs - 8] | ((uint32_t)b[bs - 7] << 8) | ((uint32_t)b[bs - 6] << 16) | ((uint32_t)b[bs - 5] << 24);
             const uint32_t isize = (uint32_t)b[bs - 4] | ((uint32_t)b[bs - 3] << 8) | ((uint32_t)b[bs - 2] << 16) | ((uint32_t)b[bs - 1] << 24);
             if (isize > (1u << 16)) { err = "corrupt BGZF block"; return -1; }
@@ -825,8 +825,8 @@ struct LineSource {
                 if (bs == 0) break;            // not a BGZF block (or its header is cut off)
                 if (bs < 26 || p + bs > zin_end) { if (bs < 26) { err = "corrupt BGZF block"; return -1; } break; }
                 const uint8_t *b = zbase + p;
-                const size_t xlen = b[10] | ((size_t)b[11] << 8), hdr = 12 + xlen;
-                if (hdr + 8 > bs) { err = "corrupt BGZF block"; return -1; }
+                const size_t hdr = tbk_gzip_header_len(b, bs);
+                if (!hdr) { err = "corrupt BGZF block"; return -1; }
                 const uint32_t crc = (uint32_t)b[bs - 8] | ((uint32_t)b[bs - 7] << 8) | ((uint32_t)b[bs - 6] << 16) | ((uint32_t)b[bs - 5] << 24);
                 const size_t isize = (size_t)b[bs - 4] | ((size_t)b[bs - 3] << 8) | ((size_t)b[bs - 2] << 16) | ((size_t)b[bs - 1] << 24);
                 if (isize > (1u << 16)) { err = "corrupt BGZF block"; return -1; }
@@ -863,19 +863,22 @@ struct LineSource {
                 TbkInflate blk_inf;
                 for (size_t i; (i = next.fetch_add(1)) < blks.size() && ok.load();) {
                     const Blk &k = blks[i];
+                    // Every block is inflated, an empty one (the end-of-file marker) too: a trailer that says ISIZE 0 over a stream that
+                    // holds text is refused, as gzip refuses it.  So is a stream that ends before the trailer does.
                     bool good;
-                    if (own && k.out_len) {
+                    if (own) {
                         blk_inf.reset(zbase + k.whole, k.whole_len);
                         size_t pos = 0;
                         const TbkInflate::Status st = blk_inf.run(scratch.data(), &pos, scratch.size(), 0);
-                        good = st == TbkInflate::MEMBER_DONE && pos == k.out_len;
+                        good = st == TbkInflate::MEMBER_DONE && pos == k.out_len && blk_inf.bit_position() == (uint64_t)k.whole_len * 8;
                         if (good) memcpy(out + k.out, scratch.data(), k.out_len);
                     } else {
+                        uint8_t none;
                         inflateReset(&z);
                         z.next_in = const_cast<uint8_t *>(zbase + k.in); z.avail_in = (uInt)k.in_len;
-                        z.next_out = out + k.out; z.avail_out = (uInt)k.out_len;
-                        const int rc = k.out_len ? inflate(&z, Z_FINISH) : Z_STREAM_END;  // an empty block (the end-of-file marker) has nothing to inflate
-                        good = rc == Z_STREAM_END && z.avail_out == 0;
+                        z.next_out = k.out_len ? out + k.out : &none; z.avail_out = (uInt)k.out_len;
+                        const int rc = inflate(&z, Z_FINISH);
+                        good = rc == Z_STREAM_END && z.avail_out == 0 && z.avail_in == 0;
                     }
                     if (!good || tbk_crc32(0u, out + k.out, k.out_len) != k.crc) ok.store(false);
                 }

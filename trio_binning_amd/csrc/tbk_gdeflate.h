@@ -22,6 +22,24 @@ int tbk_gdeflate_collect(tbk_gdeflate *g, bool drain, std::vector<tbk_gdeflate_o
 int tbk_gdeflate_in_flight(const tbk_gdeflate *g);
 void tbk_gdeflate_stats(const tbk_gdeflate *g, uint64_t *text_bytes, uint64_t *member_bytes, uint64_t *blocks, uint64_t *members);
 
+// Bytes of the header of the gzip member at p, whose first `bs` bytes are its own (a bgzf member's BSIZE + 1): the fixed ten, FEXTRA,
+// FNAME and FCOMMENT (zero-terminated) and FHCRC (RFC 1952 2.3.1); 0 when they and the 8-byte trailer do not fit in bs.  What the
+// host's bgzf parsers and the GPU inflater's take the member's deflate stream to start behind.
+inline size_t tbk_gzip_header_len(const uint8_t *p, size_t bs) {
+    if (bs < 18) return 0;
+    const int flg = p[3];
+    size_t h = 10;
+    if (flg & 4) h = 12 + (p[10] | ((size_t)p[11] << 8));
+    for (int f = 8; f <= 16; f <<= 1)
+        if (flg & f) {
+            while (h < bs && p[h]) h++;
+            if (h >= bs) return 0;
+            h++;
+        }
+    if (flg & 2) h += 2;
+    return h + 8 <= bs ? h : 0;
+}
+
 // ---- the other direction: bgzf blocks inflated on the device (tbk_gdeflate.hip, second half) -------------------------------------------
 struct tbk_ginflate;
 struct tbk_ginflate_block { uint64_t in_off; uint32_t in_len, out_len, crc; uint32_t pad_; };   // a raw deflate stream in the window's input; its text's length and CRC-32 (the bgzf trailer's)

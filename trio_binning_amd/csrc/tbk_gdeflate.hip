@@ -1080,11 +1080,17 @@ struct GiBits {
 };
 
 // canonical order and counts of a code (one lane; n <= 288), then the fast table by all lanes.  kind 0: literal/length code, 1: distance
-// code, 2: the code-length code (entry = the symbol in bits 16.., length in bits 0..3)
-__device__ void gi_build(const uint8_t *len, int n, uint16_t *count, uint16_t *symbol, uint32_t *fast, int fast_bits, int kind, int lane) {
+// code, 2: the code-length code (entry = the symbol in bits 16.., length in bits 0..3).  Returns whether zlib would take the lengths
+// (inftrees.c): not over-subscribed, and complete - but for a code of no codes at all and, except the code-length code, one code of
+// length 1.  (The Kraft sum on the lane that counts, once per code.)
+__device__ bool gi_build(const uint8_t *len, int n, uint16_t *count, uint16_t *symbol, uint32_t *fast, int fast_bits, int kind, int lane) {
+    int ok = 1;
     if (lane == 0) {
         for (int l = 0; l < 16; l++) count[l] = 0;
         for (int s = 0; s < n; s++) count[len[s]]++;
+        int left = 1, longest = 0;
+        for (int l = 1; l < 16; l++) { left = (left << 1) - (int)count[l]; if (count[l]) longest = l; if (left < 0) break; }
+        ok = left == 0 || (left > 0 && (longest == 0 || (longest == 1 && kind != 2)));
         uint16_t offs[16];
         offs[1] = 0;
         for (int l = 1; l < 15; l++) offs[l + 1] = (uint16_t)(offs[l] + count[l]);
@@ -1110,6 +1116,7 @@ __device__ void gi_build(const uint8_t *len, int n, uint16_t *count, uint16_t *s
         for (uint32_t j = rev; j < (1u << fast_bits); j += 1u << L) fast[j] = e;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    return __builtin_amdgcn_readfirstlane(ok) != 0;
 }
 
 // one symbol bit by bit along the canonical order (puff.c's decode): codes longer than the fast table's index
@@ -1156,8 +1163,7 @@ gi_inflate_kernel(const uint8_t *__restrict__ in, const tbk_ginflate_block *__re
     if (lane == 0) next = atomicAdd(bad + 2, 1u);
     const uint32_t bi = (uint32_t)__builtin_amdgcn_readfirstlane((int)next);
     if (bi >= n_blks) break;
-    const tbk_ginflate_block blk = blks[bi];
-    if (blk.out_len == 0) continue;   // (the end-of-file marker: a final empty block, nothing to write)
+    const tbk_ginflate_block blk = blks[bi];   // (an empty one - the end-of-file marker - is decoded too: its stream must hold no text)
     GiBits b;
     b.init(in + blk.in_off, in + blk.in_off + blk.in_len);
     uint8_t *dst = out + out_offs[bi];
@@ -1168,6 +1174,7 @@ gi_inflate_kernel(const uint8_t *__restrict__ in, const tbk_ginflate_block *__re
     for (bool last = false; !last && !fail;) {
         if (fuel < 8u) { fail = true; break; }
         fuel -= 8u;   // (a deflate block is at least ten bits of input, and its end-of-block symbol one more step)
+        if (b.p > b.end + 8) { fail = true; break; }   // (the header loops below stay within the input as the symbol loop does)
         b.refill();
         last = b.take(1) != 0;
         const uint32_t type = b.take(2);
@@ -1177,6 +1184,7 @@ gi_inflate_kernel(const uint8_t *__restrict__ in, const tbk_ginflate_block *__re
             b.p -= b.cnt >> 3; b.buf = 0; b.cnt = 0;
             if (b.p + 4 > b.end) { fail = true; break; }
             const uint32_t n = b.p[0] | ((uint32_t)b.p[1] << 8);
+            if ((n ^ (b.p[2] | ((uint32_t)b.p[3] << 8))) != 0xFFFFu) { fail = true; break; }   // NLEN: the complement of LEN
             b.p += 4;
             if (b.p + n > b.end || pos + n > blk.out_len) { fail = true; break; }
             for (uint32_t i = lane; i < n; i += 64) dst[pos + i] = b.p[i];
@@ -1192,23 +1200,25 @@ gi_inflate_kernel(const uint8_t *__restrict__ in, const tbk_ginflate_block *__re
         } else {
             nlit = (int)b.take(5) + 257; ndist = (int)b.take(5) + 1;
             const int ncl = (int)b.take(4) + 4;
+            if (nlit > 286 || ndist > 30) { fail = true; break; }
             // the code-length code: lengths into T.len[0..19), its tables into the dist tables' space (built before those)
             if (lane < 19) T.len[lane] = 0;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             for (int i = 0; i < ncl; i++) { if (b.cnt < 3) b.refill(); const uint32_t v = b.take(3); if (lane == 0) T.len[GI_CLORD[i]] = (uint8_t)v; }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            gi_build(T.len, 19, T.dcount, T.dsym, T.dfast, 7, 2, lane);
+            if (!gi_build(T.len, 19, T.dcount, T.dsym, T.dfast, 7, 2, lane)) { fail = true; break; }
             uint8_t prev = 0;
             int i = 0;
             const int want = nlit + ndist;
             while (i < want && !fail) {
+                if (b.p > b.end + 8) { fail = true; break; }
                 b.refill();
                 const uint32_t e = gi_lookup(b, T.dfast, 7, T.dcount, T.dsym, 2);
                 const int sym = (int)(e >> 16);
                 if (sym > 18) { fail = true; break; }
                 if (sym < 16) { if (lane == 0) T.len[i] = (uint8_t)sym; prev = (uint8_t)sym; i++; continue; }
                 int rep; uint8_t val = 0;
-                if (sym == 16) { val = prev; rep = 3 + (int)b.take(2); }
+                if (sym == 16) { if (i == 0) { fail = true; break; } val = prev; rep = 3 + (int)b.take(2); }
                 else if (sym == 17) rep = 3 + (int)b.take(3);
                 else rep = 11 + (int)b.take(7);
                 if (i + rep > want) { fail = true; break; }
@@ -1217,9 +1227,12 @@ gi_inflate_kernel(const uint8_t *__restrict__ in, const tbk_ginflate_block *__re
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             if (fail) break;
+            if (__builtin_amdgcn_readfirstlane((int)T.len[256]) == 0) { fail = true; break; }   // no end-of-block code
         }
-        gi_build(T.len, nlit, T.lcount, T.lsym, T.fast, GI_FAST_BITS, 0, lane);
-        gi_build(T.len + nlit, ndist, T.dcount, T.dsym, T.dfast, GI_DFAST_BITS, 1, lane);
+        // (the fixed codes pass: 288 literal/length codes are complete, 30 distance codes of 5 bits are not - zlib builds those as 32)
+        const bool lit_ok = gi_build(T.len, nlit, T.lcount, T.lsym, T.fast, GI_FAST_BITS, 0, lane);
+        const bool dist_ok = gi_build(T.len + nlit, ndist, T.dcount, T.dsym, T.dfast, GI_DFAST_BITS, 1, lane);
+        if (type == 2 && !(lit_ok && dist_ok)) { fail = true; break; }
         // ---- the symbols ----
         for (;;) {
             if (b.cnt < 32) { if (b.p > b.end + 8) { fail = true; break; } b.refill(); }   // (a corrupt stream must not walk out of its input)
@@ -1246,6 +1259,8 @@ gi_inflate_kernel(const uint8_t *__restrict__ in, const tbk_ginflate_block *__re
             pos += len;
         }
     }
+    // the stream must end where the member's trailer begins (bytes read, less the whole bytes still in the bit buffer)
+    if (!fail && (uint64_t)(b.p - (in + blk.in_off)) - (uint64_t)(b.cnt >> 3) != blk.in_len) fail = true;
     if (fail || pos != blk.out_len) {   // the window is refused as a whole: this wave is done
         if (lane == 0) atomicAdd(bad, 1u);
         break;
@@ -1258,7 +1273,7 @@ gi_inflate_kernel(const uint8_t *__restrict__ in, const tbk_ginflate_block *__re
 __global__ void __launch_bounds__(GD_T)
 gi_check_kernel(const tbk_ginflate_block *__restrict__ blks, const uint32_t *__restrict__ crc, uint32_t n_blks, uint32_t *__restrict__ bad) {
     const uint32_t i = blockIdx.x * GD_T + threadIdx.x;
-    if (i < n_blks && blks[i].out_len && crc[i] != blks[i].crc) atomicAdd(bad + 1, 1u);
+    if (i < n_blks && crc[i] != blks[i].crc) atomicAdd(bad + 1, 1u);   // (an empty block's CRC-32 is 0: the zeroed sum)
 }
 
 namespace {
@@ -1590,8 +1605,9 @@ static int bgzf_blocks_of(const uint8_t *data, uint64_t size, std::vector<tbk_gi
         if (size - p < 18 || data[p] != 0x1f || data[p + 1] != 0x8b || data[p + 2] != 8 || !(data[p + 3] & 4)) { tbk_set_error_(TBK_ERR_FORMAT, "not a BGZF block"); return TBK_ERR_FORMAT; }
         const uint64_t xlen = data[p + 10] | ((uint64_t)data[p + 11] << 8);
         if (xlen < 6 || data[p + 12] != 'B' || data[p + 13] != 'C' || data[p + 14] != 2 || data[p + 15] != 0) { tbk_set_error_(TBK_ERR_FORMAT, "not a BGZF block"); return TBK_ERR_FORMAT; }
-        const uint64_t bs = ((uint64_t)data[p + 16] | ((uint64_t)data[p + 17] << 8)) + 1, hdr = 12 + xlen;
-        if (bs < 26 || hdr + 8 > bs || p + bs > size) { tbk_set_error_(TBK_ERR_FORMAT, "corrupt BGZF block"); return TBK_ERR_FORMAT; }
+        const uint64_t bs = ((uint64_t)data[p + 16] | ((uint64_t)data[p + 17] << 8)) + 1;
+        const uint64_t hdr = bs >= 26 && p + bs <= size ? tbk_gzip_header_len(data + p, bs) : 0;
+        if (!hdr) { tbk_set_error_(TBK_ERR_FORMAT, "corrupt BGZF block"); return TBK_ERR_FORMAT; }
         const uint8_t *b = data + p;
         const uint32_t crc = (uint32_t)b[bs - 8] | ((uint32_t)b[bs - 7] << 8) | ((uint32_t)b[bs - 6] << 16) | ((uint32_t)b[bs - 5] << 24);
         const uint32_t isize = (uint32_t)b[bs - 4] | ((uint32_t)b[bs - 3] << 8) | ((uint32_t)b[bs - 2] << 16) | ((uint32_t)b[bs - 1] << 24);
