@@ -591,10 +591,10 @@ int tbk_classifier_verified(const tbk_classifier *c, uint64_t *lines, double *se
  * k-mers of all reads, both strands, k-mers holding a symbol outside ACGT skipped, lower case
  * counted as upper case; k-mers seen once are not in the database; counters saturate at 255.
  * KMC itself is not part of the reference checkout: parity with it is unpinned.
- * Limit: the table's counters are 32-bit and neighbours share a 64-bit atomic add, so a k-mer that occurs
- * 2^32 times or more in one library (a satellite k-mer of a very deep read set) would carry into the
- * neighbouring slot's counter; readers cap at 255 long before, but the neighbour's count would be off by
- * the carry.  Not reachable below 4.3e9 occurrences of ONE k-mer; split such a library over two counters. */
+ * The table's counters are 32-bit and neighbours share a 64-bit atomic add, so a counter that passed 2^32 (a
+ * satellite k-mer of a very deep read set) would carry into the neighbouring slot's; before 2^31 more window
+ * starts can have been added, every counter above 2^31 is therefore set back to 2^31 - readers cap at 255 long
+ * before, and no count is ever off by a carry (tests/test_gpu_counter_shapes.py takes poly-A past 2^32). */
 typedef struct tbk_counter tbk_counter;
 /* Table for `capacity_kmers` distinct k-mers to start with (16 bytes per slot at load <= 0.6: a
  * bucket is one 128-byte line holding 8 keys and their 8 counters).  Before a batch that could
@@ -617,6 +617,10 @@ int tbk_counter_histogram(tbk_counter *c, uint64_t hist[256]);
 /* Distinct k-mers met so far (slots taken). */
 int tbk_counter_distinct(const tbk_counter *c, uint64_t *distinct);
 int tbk_counter_stats(const tbk_counter *c, uint64_t *n_slots, uint64_t *table_bytes, uint64_t *bases_added, uint64_t *reads_added);
+/* Bucket selection of the table as it stands (it is chosen again whenever the table is rebuilt): w m-mers of m bases
+ * from base o of the k-mer, t as in the classifier (always 0 here); w = 0 is plain mode.  m > 16 runs the counting
+ * kernel's 64-bit m-mer path.  Any pointer may be NULL. */
+int tbk_counter_params(const tbk_counter *c, int *w, int *m, int *o, int *t);
 /* kmers_subtract + kmc_dump: write to out_path, one k-mer per line in lexicographic order, the
  * k-mers of `a` seen at least twice whose counter lies in [min_count, max_count] and that `b` has
  * seen at most once. */

@@ -86,6 +86,60 @@ def test_oracle_c_counter_equals_python_restatement():
         assert int(h[0]) == len(c) and [int(x) for x in h[1:]] == [want.get(i, 0) for i in range(1, 256)], k
 
 
+@pytest.mark.parametrize("k", [1, 2, 5, 15, 16, 21, 31, 32])
+def test_numpy_counter_equals_python_restatement(tmp_path, k):
+    """The vectorised counter the GPU counter tests check against (a few Mbases per second) gives the pure-Python
+    restatement's keys, counts and order - on reads with N, lower case, empty and short reads, repeats and palindromes,
+    in one chunk and in many - and so do its histogram, its A-minus-B list and its list-file reader."""
+    import numpy as np
+
+    from oracle import unique_oracle as uo
+
+    rng = np.random.default_rng(40 + k)
+    g = "".join("ACGT"[c] for c in rng.integers(0, 4, 2500))
+    comp = str.maketrans("ACGT", "TGCA")
+
+    def lib(n):
+        reads = []
+        for p in rng.integers(0, 2300, n):
+            r = g[p:p + int(rng.integers(0, 200))]
+            if rng.random() < 0.5:
+                r = r.translate(comp)[::-1]
+            if rng.random() < 0.2:
+                r = r.lower()
+            if r and rng.random() < 0.3:
+                q = int(rng.integers(0, len(r)))
+                r = r[:q] + "Nn-*"[int(rng.integers(0, 4))] + r[q + 1:]
+            reads.append(r)
+        return reads + ["", "N", "A" * 300, "AC" * 150, "ACGT" * 80, "AAT" * 90, "acgt" * 10 + "N" + "ACGT" * 10, g[:k], g[:max(k - 1, 0)],
+                        "N" + g[:k], g[:k] + "N", "", g[5:5 + k].lower()]
+
+    reads_a, reads_b = lib(300), lib(150)
+    want_a, want_b = uo.count_kmers(reads_a, k), uo.count_kmers(reads_b, k)
+    for chunk in (1 << 23, 997):
+        keys, counts = uo.count_kmers_np(*uo.pack(reads_a), k, chunk=chunk)
+        assert keys.dtype == np.uint64 and (keys[1:] > keys[:-1]).all()
+        names = uo.kmer_strings(keys, k)
+        assert names == sorted(want_a) and [int(c) for c in counts] == [want_a[n] for n in names]
+    a, b = (keys, counts), uo.count_kmers_np(*uo.pack(reads_b), k)
+    halves = uo.add_counts_np(uo.count_kmers_np(*uo.pack(reads_a[:100]), k), uo.count_kmers_np(*uo.pack(reads_a[100:]), k))
+    assert np.array_equal(halves[0], keys) and np.array_equal(halves[1], counts)
+    dba, dbb = uo.database(want_a), uo.database(want_b)
+    hist = uo.histogram_np(counts)
+    assert int(hist[0]) == len(want_a) and int(hist[1]) == sum(1 for n in want_a.values() if n == 1)
+    assert [(c, int(hist[c])) for c in range(2, 256)] == uo.histogram_rows(dba)[1:]
+    assert len(dba) > 0
+    for lo, hi in ((2, 255), (1, 4), (3, 9), (255, 255), (0, 1000), (5, 3)):
+        got = uo.unique_np(a, b, lo, hi)
+        assert uo.kmer_strings(got, k) == uo.unique_kmers(dba, dbb, lo, hi), (lo, hi)
+    path = tmp_path / "list.txt"
+    path.write_text("".join(n + "\n" for n in names))
+    assert np.array_equal(uo.read_list_np(str(path), k), keys)
+    path.write_text("".join(n + "\n" for n in names)[:-2] + "\n")
+    with pytest.raises(AssertionError):
+        uo.read_list_np(str(path), k)
+
+
 def test_cli_arguments_mirror_the_reference(built):
     from trio_binning_amd import find_unique_kmers as fu
 

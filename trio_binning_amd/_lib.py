@@ -178,6 +178,7 @@ _sig("tbk_counter_kernel_timing", C.c_int, _vp, _u64p, _u64p, _dp, C.c_int)
 _sig("tbk_counter_histogram", C.c_int, _vp, _u64p)
 _sig("tbk_counter_distinct", C.c_int, _vp, _u64p)
 _sig("tbk_counter_stats", C.c_int, _vp, _u64p, _u64p, _u64p, _u64p)
+_sig("tbk_counter_params", C.c_int, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
 _sig("tbk_counter_unique", C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, C.c_char_p, _u64p)
 _sig("tbk_calib_gather", C.c_int, C.c_int, _u64, C.c_int, C.c_int, C.c_int, _u64, C.c_int, _dp, _dp)
 _sig("tbk_calib_atomics", C.c_int, C.c_int, _u64, C.c_int, C.c_int, _dp)

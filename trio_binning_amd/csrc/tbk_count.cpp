@@ -183,7 +183,8 @@ static int counter_run(tbk_counter *c, const uint8_t *d_bases, const uint64_t *d
     const uint64_t sep_total = total + n_reads, passes = tbk_probe_passes(sep_total);
     for (uint64_t p0 = 0; p0 < passes;) {
         uint64_t slots = (uint64_t)c->n_buckets * TBK_SLOTS_PER_BUCKET;
-        const uint64_t piece = std::max<uint64_t>(32768, slots / 4 / 2048);
+        // (at most 2^30 window starts however large the table: a piece on top of counters just set back to 2^31 must stay below 2^32 - see below)
+        const uint64_t piece = std::min<uint64_t>(std::max<uint64_t>(32768, slots / 4 / 2048), (1u << 19));
         const uint64_t np = std::min(piece, passes - p0), windows = np * 2048;
         if ((double)(c->used + windows) > 0.85 * (double)slots) {
             uint64_t want = (uint64_t)((double)slots * c->load) * 2;  // twice the present capacity
@@ -305,6 +306,15 @@ extern "C" int tbk_counter_stats(const tbk_counter *c, uint64_t *n_slots, uint64
     if (table_bytes) *table_bytes = (uint64_t)c->n_buckets * 128;
     if (bases_added) *bases_added = c->bases_added;
     if (reads_added) *reads_added = c->reads_added;
+    return TBK_OK;
+}
+
+extern "C" int tbk_counter_params(const tbk_counter *c, int *w, int *m, int *o, int *t) {
+    if (!c) return cfail(TBK_ERR_INVALID, "counter is NULL");
+    if (w) *w = c->mz.w;
+    if (m) *m = c->mz.m;
+    if (o) *o = c->mz.o;
+    if (t) *t = c->mz.t;
     return TBK_OK;
 }
 

@@ -848,7 +848,10 @@ class KmerCounter:
         check(lib.tbk_counter_stats(self._h, *[C.byref(x) for x in v]))
         d = C.c_uint64()
         check(lib.tbk_counter_distinct(self._h, C.byref(d)))
-        return dict(zip(("n_slots", "table_bytes", "bases_added", "reads_added", "distinct"), [x.value for x in v] + [d.value]))
+        p = [C.c_int() for _ in range(4)]
+        check(lib.tbk_counter_params(self._h, *[C.byref(x) for x in p]))
+        return dict(zip(("n_slots", "table_bytes", "bases_added", "reads_added", "distinct", "w", "m", "o", "t"),
+                        [x.value for x in v] + [d.value] + [x.value for x in p]))
 
     def unique(self, other: "KmerCounter", min_count: int, max_count: int, out_path: str) -> int:
         """Write the k-mers this library saw at least twice, with a counter in [min_count,
