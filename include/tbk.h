@@ -419,6 +419,10 @@ int tbk_fastx_set_packing(tbk_fastx_reader *r, int on);
  * or destroyed.  When the pinned memory for two windows cannot be had, the host's threads inflate after all. */
 int tbk_fastx_set_device(tbk_fastx_reader *r, int device);
 int tbk_fastx_inflates_on_device(const tbk_fastx_reader *r);
+/* An ordinary (non-bgzf) gzip file goes to the device as well when TBK_GZIP_INFLATE=gpu is set, the file is mapped and holds
+ * TBK_PINFLATE_MIN bytes (default 16 MB) or more: tbk_gzip_inflate_device's passes, window after window, each window's text copied
+ * to the parser.  tbk_fastx_gzip_stats: tbk_gzip_inflate_stats's six counts for this reader so far. */
+void tbk_fastx_gzip_stats(const tbk_fastx_reader *r, uint64_t out[6]);
 int tbk_fastx_batch_packed(const tbk_fastx_batch *b, const uint32_t **codes, const uint32_t **exc_chunk, const uint16_t **exc_mask,
                            uint64_t *n_exc);
 /* on != 0 (and packing on): batches taken from a plain FASTQ file by the chunk-parallel scan do not copy their
@@ -474,6 +478,31 @@ int tbk_bgzf_inflate_device(int device, const uint8_t *data, uint64_t size, uint
  * input resident (HIP events around inflate, CRC-32 and check), *ring_s per window through the ring as the reader drives it (staging
  * copy, copy in, kernels, text home; two windows in flight); *text_bytes: a window's text. */
 int tbk_bgzf_bench_device(int device, const uint8_t *data, uint64_t size, int reps, double *ring_s, double *kernels_s, uint64_t *text_bytes);
+/* Ordinary gzip input - one member or several, any header fields, any block types; what gzip.open reads (seq.py:86-92) and bgzf is
+ * not - inflated on `device` in two passes (csrc/tbk_gdeflate.hip, last part; csrc/tbk_gzplan.cpp): the host guesses block starts, one
+ * wave per chunk decodes into 16-bit symbols (a byte, or a marker for a byte of the 32 KiB window the chunk does not have), the chunks
+ * whose predecessor ended exactly on their start are kept, their windows filled in front to back, the markers resolved, and every
+ * member's CRC-32 and ISIZE compared with its trailer.  *text_len: bytes of text - also when dst is NULL or too small (TBK_ERR_NOMEM):
+ * ISIZE is only a hint, so the size query inflates.  Damage: TBK_ERR_FORMAT and the host path's message ("inflate: ...").
+ * _opts: chunk / window = compressed bytes per chunk / per window, 0 = the default (TBK_GZIP_CHUNK / TBK_GZIP_WINDOW). */
+int tbk_gzip_inflate_device(int device, const uint8_t *data, uint64_t size, uint8_t *dst, uint64_t cap, uint64_t *text_len);
+int tbk_gzip_inflate_device_opts(int device, const uint8_t *data, uint64_t size, uint8_t *dst, uint64_t cap, uint64_t *text_len, uint64_t chunk,
+                                 uint64_t window);
+/* The same plan, chain check and loop with the host's own decoder (TbkInflate::run16) in the device's place: no GPU needed. */
+int tbk_gzip_inflate_host(const uint8_t *data, uint64_t size, uint8_t *dst, uint64_t cap, uint64_t *text_len, uint64_t chunk, uint64_t window);
+/* Of the calling thread's last tbk_gzip_inflate_device / _host: out[0] windows, [1] chunks guessed, [2] chunks accepted, [3] chunks
+ * decoded again (cut off behind a wrong guess, a member's end or a full buffer), [4] bytes handed back to the host path, [5] the most
+ * chunks accepted in one window. */
+void tbk_gzip_inflate_stats(uint64_t out[6]);
+/* The inflater timed by itself on a whole file, `reps` times: *kernels_s the kernels' own time per pass over the file (pass_s[0] the
+ * marker inflate, pass_s[1] propagate + resolve + CRC-32; HIP events), *ring_s the wall time per pass (pass_s[2] of it: the host's
+ * block-start guesses), *text_bytes the file's text.  pass_s may be NULL. */
+int tbk_gzip_inflate_bench_device(int device, const uint8_t *data, uint64_t size, int reps, double *ring_s, double *kernels_s, uint64_t *text_bytes,
+                                  double pass_s[3]);
+/* (tests) The first member of `data` decoded up to the first block header at or past stop_bit by one decoder and from that bit -
+ * *boundary_bit - on by a second one that is told nothing but the bit: the text of both, in dst. */
+int tbk_inflate_resume_at_bit(const uint8_t *data, uint64_t size, uint64_t stop_bit, uint8_t *dst, uint64_t cap, uint64_t *text_len,
+                              uint64_t *boundary_bit);
 int tbk_bin_writer_encoder(const tbk_bin_writer *w);
 int tbk_bin_writer_write(tbk_bin_writer *w, const tbk_fastx_batch *b, const char *bins);
 int tbk_bin_writer_close(tbk_bin_writer *w);

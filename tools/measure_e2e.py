@@ -280,7 +280,8 @@ if a.gz_trace and "bgzf" in gz_inputs:
     res["gz_trace"] = {"rc": p.returncode, "stderr_tail": p.stderr.decode()[-600:]}
     shutil.rmtree(out, ignore_errors=True)
 gz_inputs = {label: path for label, path in gz_inputs.items() if label in a.gz_kinds.split(",")}
-gz_runs = [(label, path, "", False) for label, path in gz_inputs.items()]
+# (an ordinary member runs twice: inflated by the host's threads - the yardstick - and on the GPU, csrc/tbk_gzplan.cpp)
+gz_runs = [(label, path, e, False) for label, path in gz_inputs.items() for e in (("TBK_GZIP_INFLATE=cpu", "TBK_GZIP_INFLATE=gpu") if label == "one_gzip_member" else ("",))]
 gz_runs += [(label, path, e, False) for e in a.gz_env.split(";") if e for label, path in gz_inputs.items()]
 if a.gz_both:
     gz_runs += [(label, path, "", True) for label, path in gz_inputs.items()]

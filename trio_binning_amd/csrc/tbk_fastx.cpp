@@ -46,6 +46,7 @@
 #include "tbk_inflate.h"
 #include "tbk_pack.h"
 #include "tbk_gdeflate.h"
+#include "tbk_gzplan.h"
 
 uint32_t tbk_crc32(uint32_t crc, const uint8_t *p, size_t n);  // tbk_crc.cpp: zlib's crc32() by carry-less multiplication
 
@@ -161,6 +162,8 @@ struct LineSource {
     // BGZF blocks inflated on the GPU (tbk_fastx_set_device; csrc/tbk_gdeflate.hip, second half): one wave per block, windows of
     // 96 MB of the file four deep.  -1: on the host's threads.
     int gpu_device = -1;
+    bool gzip_gpu = false;   // an ordinary gzip file inflated there too (gzip_loop_gpu)
+    TbkGzStats gz_stats = {0, 0, 0, 0, 0, 0.0, 0};
     uint64_t gpu_windows = 0, gpu_blocks = 0;
     double gpu_stage_s = 0, gpu_wait_s = 0, gpu_slot_wait_s = 0;
     double chunk_wait_s = 0, left_copy_s = 0; uint64_t left_bytes = 0;   // the parser's side: waiting for a window, copying what it had left in front of it
@@ -708,9 +711,49 @@ struct LineSource {
             tail.swap(next_tail);
         }
     }
+    // ---- an ordinary gzip stream on the GPU --------------------------------------------------------
+    // The same scheme with a wave of the device per chunk (tbk_gzplan.cpp: the plan, the chain check and the loop; tbk_gdeflate.hip,
+    // last part: the passes): this thread guesses block starts with the reader's threads, the device decodes, resolves and sums, and
+    // every window's text is handed to the parser as a chunk.  tbk_fastx_set_device on a mapped gzip file of TBK_PINFLATE_MIN bytes
+    // or more that is not bgzf, with TBK_GZIP_INFLATE=gpu.  No inflater (no device, no memory for it) before the first text: the host
+    // path reads the file.  Anything later - a stream that does not decode, a CRC, a HIP error - ends the run with its message.
+    bool gzip_for_device() const {
+        const char *how = getenv("TBK_GZIP_INFLATE");
+        return !bgzf && fast && map && how && strcmp(how, "gpu") == 0 && map_size >= env_size("TBK_PINFLATE_MIN", (size_t)16 << 20);
+    }
+    void gzip_loop_gpu() {
+        TbkGzBackend *g = nullptr;
+        bool delivered = false;
+        int rc = tbk_gzinflate_create(gpu_device, &g);
+        std::string msg;
+        if (rc == TBK_OK) {
+            const TbkGzOptions opt = tbk_gz_options_from_env(threads);
+            rc = tbk_gz_run(*g, map, map_size, opt, [&](const uint8_t *p, size_t len, bool last) {
+                { std::lock_guard<std::mutex> lk(mu); if (stop) return false; }
+                Chunk c;
+                if (len) { c.data = take_buffer(len); memcpy(c.data.data(), p, len); }
+                c.off = 0; c.len = len; c.last = last;
+                delivered = true;
+                push(std::move(c));
+                return true;
+            }, &gz_stats, &msg);
+            tbk_gzinflate_destroy(g);
+        }
+        if (rc == TBK_OK || rc == TBK_ERR_STATE) return;
+        if (!delivered && (rc == TBK_ERR_NO_DEVICE || rc == TBK_ERR_HIP || rc == TBK_ERR_NOMEM)) {
+            // the host's threads inflate, from the file's first byte (`inf` has not moved)
+            gzip_gpu = false;
+            gz_stats.handed_back = map_size;
+            if (guessing()) pinflate_loop(); else inflate_loop();
+            return;
+        }
+        Chunk c;
+        c.err = msg.empty() ? std::string("inflate: ") + tbk_last_error() : msg; c.last = true;
+        push(std::move(c));
+    }
     // own decoder: returns like refill()
     bool refill_fast() {
-        if (!started) { started = true; worker = std::thread([this] { if (bgzf && gpu_device >= 0 && map) bgzf_loop_gpu(); else if (bgzf) bgzf_loop(); else if (guessing()) pinflate_loop(); else inflate_loop(); }); }
+        if (!started) { started = true; worker = std::thread([this] { if (bgzf && gpu_device >= 0 && map) bgzf_loop_gpu(); else if (bgzf) bgzf_loop(); else if (gzip_gpu) gzip_loop_gpu(); else if (guessing()) pinflate_loop(); else inflate_loop(); }); }
         Chunk c;
         {
             const auto t0 = std::chrono::steady_clock::now();
@@ -1626,14 +1669,21 @@ extern "C" int tbk_fastx_set_device(tbk_fastx_reader *r, int device) {
     if (how && strcmp(how, "cpu") == 0) return TBK_OK;
     if (r->src.started) return ffail(TBK_ERR_STATE, "tbk_fastx_set_device after the first read");
     r->src.gpu_device = device;
+    r->src.gzip_gpu = r->src.gzip_for_device();   // (TBK_GZIP_INFLATE=gpu: an ordinary gzip file goes there as well)
     // the host's threads do not inflate now: the chunk-parallel scan has them (TBK_INFLATED_SCAN=0 keeps the sequential machine), and
     // the windows it scans can keep a batch's records (tbk_fastx_set_borrowing)
     const char *scan_env = getenv("TBK_FASTQ_SCAN"), *inflated_env = getenv("TBK_INFLATED_SCAN");
-    if (r->src.bgzf && r->src.map && !(scan_env && *scan_env == '0') && !(inflated_env && *inflated_env == '0')) r->scan.inflated = true;
+    if ((r->src.bgzf || r->src.gzip_gpu) && r->src.map && !(scan_env && *scan_env == '0') && !(inflated_env && *inflated_env == '0')) r->scan.inflated = true;
     return TBK_OK;
 }
 // 1 when the reader's BGZF blocks are (being) inflated on a device
-extern "C" int tbk_fastx_inflates_on_device(const tbk_fastx_reader *r) { return r && r->src.bgzf && r->src.gpu_device >= 0 && r->src.map ? 1 : 0; }
+extern "C" int tbk_fastx_inflates_on_device(const tbk_fastx_reader *r) { return r && (r->src.bgzf || r->src.gzip_gpu) && r->src.gpu_device >= 0 && r->src.map ? 1 : 0; }
+// the gzip inflater's counts so far (tbk_gzip_inflate_stats's six), for a reader whose ordinary gzip input is inflated on a device
+extern "C" void tbk_fastx_gzip_stats(const tbk_fastx_reader *r, uint64_t out[6]) {
+    const TbkGzStats z = {0, 0, 0, 0, 0, 0.0, 0};
+    const TbkGzStats &s = r ? r->src.gz_stats : z;
+    out[0] = s.windows; out[1] = s.guessed; out[2] = s.accepted; out[3] = s.redecoded; out[4] = s.handed_back; out[5] = s.most_accepted;
+}
 
 extern "C" int tbk_fastx_set_borrowing(tbk_fastx_reader *r, int on) {
     if (!r) return ffail(TBK_ERR_INVALID, "NULL argument");

@@ -37,6 +37,7 @@
 
 #include "../../include/tbk.h"
 #include "tbk_gdeflate.h"
+#include "tbk_gzplan.h"
 
 extern "C" void tbk_set_error_(int, const char *msg);
 
@@ -1727,5 +1728,459 @@ extern "C" int tbk_bgzf_bench_device(int device, const uint8_t *data, uint64_t s
         *ring_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / reps;
     }
     tbk_ginflate_destroy(g);
+    return rc;
+}
+
+
+// =====================================================================================================================================
+// Ordinary gzip input - one member, or several of any size - inflated on the GPU in two passes (the plan, the chain check and the loop
+// around these kernels: tbk_gzplan.cpp, host only; the scheme: LineSource::pinflate_loop, tbk_fastx.cpp).
+// =====================================================================================================================================
+// A DEFLATE stream that is not bgzf has no independent pieces: the host guesses block starts (TbkInflate::open_dynamic_block_at), and
+// pass a decodes a chunk from each guess into 16-BIT symbols - a byte value, or 0x8000 + i for "byte i of the 32 KiB window in front of
+// me, which I do not have".  The host keeps the chunks whose predecessor ended exactly on their start (so every one kept starts on a
+// block boundary of the real chain); pass b fills in the kept chunks' windows front to back, pass c turns symbols into bytes, pass d
+// (gd_crc_kernel, a chunk as its "member") sums each chunk's CRC-32, which the host folds into the member's.
+//
+// The window in front of a chunk is MATERIALISED: TBK_GZ_HIST elements in front of the chunk's symbols, written by the wave first (markers)
+// or put there by the host (chunk 0 of a window: the real one; TBK_GZ_NOTHING where the member had not begun).  64 KiB per chunk - 3 % of
+// what a chunk of 128 KiB of FASTQ.gz writes - buys a match copy with no case to tell apart: DEFLATE's distances end at 32768, so
+// dst + pos - dist lies in the chunk's own stretch whatever the stream says, pass b can resolve a chunk's window where it lies, and
+// pass c reads window and symbols through one pointer.  A reference before the member's first byte is no decoding error here, as it is
+// none in the host's run16: it copies TBK_GZ_NOTHING, which pass c reports (a resolved value above 0xFF).
+//
+// gz_inflate_kernel is gi_inflate_kernel's decoder (GiBits, gi_build, gi_lookup, GiTables: shared) in a kernel of its own, so that the
+// bgzf kernel stays the code it was.  The safety rules are that kernel's: fuel on every loop, the input-overrun checks, and a wave
+// whose chunk does not decode ENDS.  A chunk that fails is an ordinary event here (a wrong guess decodes garbage): the lowest such
+// index is kept in ctl[1], and a wave that draws a chunk above it ends too - the chain is broken below, nobody will look at that chunk.
+__global__ void __launch_bounds__(64 * GI_WAVES)
+gz_inflate_kernel(const uint8_t *__restrict__ in, uint64_t in_bytes, const TbkGzChunk *__restrict__ chunks, uint32_t n_chunks, uint16_t *__restrict__ sym,
+                  TbkGzResult *__restrict__ res, uint32_t *__restrict__ ctl) {
+    __shared__ GiTables tabs[GI_WAVES];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    GiTables &T = tabs[wave];
+    const uint64_t in_bits = in_bytes * 8;
+  for (;;) {
+    uint32_t next = 0, low = 0;
+    if (lane == 0) { next = atomicAdd(ctl, 1u); low = __atomic_load_n(ctl + 1, __ATOMIC_RELAXED); }
+    const uint32_t ci = (uint32_t)__builtin_amdgcn_readfirstlane((int)next);
+    if (ci >= n_chunks || ci > (uint32_t)__builtin_amdgcn_readfirstlane((int)low)) break;
+    const TbkGzChunk ck = chunks[ci];
+    uint16_t *win = sym + ck.sym_off, *dst = win + TBK_GZ_HIST;
+    if (!ck.window_known) {   // the markers: 8 to a lane and store
+        for (uint32_t i = (uint32_t)lane * 8; i < TBK_GZ_HIST; i += 512) {
+            const uint32_t m = 0x8000u + i;
+            *reinterpret_cast<uint4 *>(win + i) = make_uint4(m | ((m + 1) << 16), (m + 2) | ((m + 3) << 16), (m + 4) | ((m + 5) << 16), (m + 6) | ((m + 7) << 16));
+        }
+    }
+    uint32_t pos = 0, status = 0;
+    uint64_t end_bit = 0;
+    const uint64_t start_byte = ck.start_bit >> 3;
+    GiBits b;
+    b.init(in, in + in_bytes);
+    if (start_byte >= in_bytes) status = TBK_GZ_NO_INPUT;
+    else {
+        b.init(in + start_byte, in + in_bytes);
+        b.refill();
+        b.drop((int)(ck.start_bit & 7));
+    }
+    const uint64_t fuel64 = (uint64_t)ck.out_cap + 8u * (in_bytes - (start_byte < in_bytes ? start_byte : in_bytes)) + 1024u;
+    uint32_t fuel = fuel64 > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)fuel64;
+    const uint32_t cap = ck.out_cap;
+    while (status == 0) {
+        const uint64_t at = (uint64_t)(b.p - in) * 8 - (uint64_t)b.cnt;
+        if (at > in_bits) { status = TBK_GZ_NO_INPUT; break; }
+        if (at >= ck.stop_bit) { status = TBK_GZ_BOUNDARY; end_bit = at; break; }
+        if (fuel < 8u) { status = TBK_GZ_FAILED; break; }
+        fuel -= 8u;
+        if (b.p > b.end + 8) { status = TBK_GZ_NO_INPUT; break; }
+        b.refill();
+        const bool last = b.take(1) != 0;
+        const uint32_t type = b.take(2);
+        if (type == 0) {  // stored
+            b.drop(b.cnt & 7);
+            b.p -= b.cnt >> 3; b.buf = 0; b.cnt = 0;
+            if (b.p + 4 > b.end) { status = TBK_GZ_NO_INPUT; break; }
+            const uint32_t n = b.p[0] | ((uint32_t)b.p[1] << 8);
+            if ((n ^ (b.p[2] | ((uint32_t)b.p[3] << 8))) != 0xFFFFu) { status = TBK_GZ_FAILED; break; }
+            b.p += 4;
+            if (b.p + n > b.end) { status = TBK_GZ_NO_INPUT; break; }
+            if (pos + n > cap) { status = TBK_GZ_NO_ROOM; break; }
+            for (uint32_t i = lane; i < n; i += 64) dst[pos + i] = (uint16_t)b.p[i];
+            pos += n; b.p += n;
+        } else if (type == 3) { status = TBK_GZ_FAILED; break; }
+        else {
+            int nlit = 288, ndist = 30;
+            bool fail = false;
+            if (type == 1) {
+                for (int i = lane; i < 288; i += 64) T.len[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8;
+                if (lane < 30) T.len[288 + lane] = 5;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            } else {
+                nlit = (int)b.take(5) + 257; ndist = (int)b.take(5) + 1;
+                const int ncl = (int)b.take(4) + 4;
+                if (nlit > 286 || ndist > 30) { status = TBK_GZ_FAILED; break; }
+                if (lane < 19) T.len[lane] = 0;
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                for (int i = 0; i < ncl; i++) { if (b.cnt < 3) b.refill(); const uint32_t v = b.take(3); if (lane == 0) T.len[GI_CLORD[i]] = (uint8_t)v; }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                if (!gi_build(T.len, 19, T.dcount, T.dsym, T.dfast, 7, 2, lane)) { status = TBK_GZ_FAILED; break; }
+                uint8_t prev = 0;
+                int i = 0;
+                const int want = nlit + ndist;
+                while (i < want && !fail) {
+                    if (b.p > b.end + 8) { fail = true; break; }
+                    b.refill();
+                    const uint32_t e = gi_lookup(b, T.dfast, 7, T.dcount, T.dsym, 2);
+                    const int s = (int)(e >> 16);
+                    if (s > 18) { fail = true; break; }
+                    if (s < 16) { if (lane == 0) T.len[i] = (uint8_t)s; prev = (uint8_t)s; i++; continue; }
+                    int rep; uint8_t val = 0;
+                    if (s == 16) { if (i == 0) { fail = true; break; } val = prev; rep = 3 + (int)b.take(2); }
+                    else if (s == 17) rep = 3 + (int)b.take(3);
+                    else rep = 11 + (int)b.take(7);
+                    if (i + rep > want) { fail = true; break; }
+                    for (int r = lane; r < rep; r += 64) T.len[i + r] = val;
+                    i += rep; prev = val;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                if (fail) { status = TBK_GZ_FAILED; break; }
+                if (__builtin_amdgcn_readfirstlane((int)T.len[256]) == 0) { status = TBK_GZ_FAILED; break; }
+            }
+            const bool lit_ok = gi_build(T.len, nlit, T.lcount, T.lsym, T.fast, GI_FAST_BITS, 0, lane);
+            const bool dist_ok = gi_build(T.len + nlit, ndist, T.dcount, T.dsym, T.dfast, GI_DFAST_BITS, 1, lane);
+            if (type == 2 && !(lit_ok && dist_ok)) { status = TBK_GZ_FAILED; break; }
+            // ---- the symbols ----
+            for (;;) {
+                if (b.cnt < 32) { if (b.p > b.end + 8) { status = TBK_GZ_NO_INPUT; break; } b.refill(); }
+                if (fuel-- == 0u) { status = TBK_GZ_FAILED; break; }
+                uint32_t e = gi_lookup(b, T.fast, GI_FAST_BITS, T.lcount, T.lsym, 0);
+                if (e & 0x100u) {
+                    if (pos >= cap) { status = TBK_GZ_NO_ROOM; break; }
+                    dst[pos++] = (uint16_t)(e >> 16);
+                    continue;
+                }
+                if (e & 0x200u) break;   // end of block
+                if ((e >> 16) == 0xFFFFu) { status = TBK_GZ_FAILED; break; }
+                if (b.cnt < 32) b.refill();
+                const uint32_t len = (e >> 16) + b.take((int)((e >> 4) & 15u));
+                const uint32_t d = gi_lookup(b, T.dfast, GI_DFAST_BITS, T.dcount, T.dsym, 1);
+                if ((d >> 16) == 0xFFFFu) { status = TBK_GZ_FAILED; break; }
+                if (b.cnt < 16) b.refill();
+                const uint32_t dist = (d >> 16) + b.take((int)((d >> 4) & 15u));
+                if (dist > TBK_GZ_HIST) { status = TBK_GZ_FAILED; break; }   // (no code says so; the window's 32 Ki elements are what is there)
+                if (pos + len > cap) { status = TBK_GZ_NO_ROOM; break; }
+                // elements, whatever they are: symbols of this chunk or of the window in front of it
+                const uint16_t *src = dst + pos - dist;
+                if (dist >= len) { for (uint32_t i = lane; i < len; i += 64) dst[pos + i] = src[i]; }
+                else { for (uint32_t i = lane; i < len; i += 64) dst[pos + i] = src[i % dist]; }
+                pos += len;
+            }
+            if (status) break;
+        }
+        if (last) {
+            end_bit = (uint64_t)(b.p - in) * 8 - (uint64_t)b.cnt;
+            status = end_bit > in_bits ? TBK_GZ_NO_INPUT : TBK_GZ_MEMBER_DONE;
+        }
+    }
+    // a stream that broke on the zeros behind the input did not break: it needs more input
+    if (status == TBK_GZ_FAILED && (uint64_t)(b.p - in) * 8 - (uint64_t)b.cnt + 48 > in_bits) status = TBK_GZ_NO_INPUT;
+    if (lane == 0) {
+        res[ci] = TbkGzResult{status, pos, end_bit};
+        if (status != TBK_GZ_BOUNDARY) atomicMin(ctl + 1, ci);   // (a member's end cuts the window as a failure does)
+    }
+    if (status != TBK_GZ_BOUNDARY) break;   // this wave is done
+  }
+}
+
+// pass b: the windows of the kept chunks, front to back, each written where pass a left its markers.  One workgroup: a step is 32 Ki
+// independent look-ups in the chunk before, and the steps are a chain.
+constexpr int GZ_PROP_T = 1024;
+__global__ void __launch_bounds__(GZ_PROP_T)
+gz_propagate_kernel(uint16_t *sym, const TbkGzChunk *__restrict__ chunks, const TbkGzResult *__restrict__ res, uint32_t n_acc) {
+    for (uint32_t i = 1; i < n_acc; i++) {
+        const uint16_t *before = sym + chunks[i - 1].sym_off, *src = before + TBK_GZ_HIST;
+        uint16_t *w = sym + chunks[i].sym_off;
+        const uint32_t n = res[i - 1].n_sym, take = n < TBK_GZ_HIST ? n : TBK_GZ_HIST, keep = TBK_GZ_HIST - take;
+        for (uint32_t k = threadIdx.x; k < TBK_GZ_HIST; k += GZ_PROP_T) {
+            uint16_t v;
+            if (k < keep) v = before[take + k];
+            else { v = src[n - take + (k - keep)]; if (v >= 0x8000u) v = before[v - 0x8000u]; }
+            w[k] = v;
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+
+// pass c: symbols -> bytes, chunk after chunk back to back in the text; eight symbols (one 16-byte load, one 8-byte store) to a lane
+struct __attribute__((packed)) GzBytes8 { uint64_t v; };
+__global__ void __launch_bounds__(GD_T)
+gz_resolve_kernel(const uint16_t *__restrict__ sym, const TbkGzChunk *__restrict__ chunks, const TbkGzResult *__restrict__ res, const uint64_t *__restrict__ text_off,
+                  uint32_t first, uint8_t *__restrict__ text, uint8_t *__restrict__ bad) {
+    const uint32_t ci = first + blockIdx.y;
+    const uint32_t n = res[ci].n_sym;
+    const uint64_t k = ((uint64_t)blockIdx.x * GD_T + threadIdx.x) * 8;
+    if (k >= n) return;
+    const uint16_t *w = sym + chunks[ci].sym_off, *s = w + TBK_GZ_HIST + k;
+    uint8_t *o = text + text_off[ci] + k;
+    uint32_t seen = 0;
+    if (k + 8 <= n) {
+        const uint4 q = *reinterpret_cast<const uint4 *>(s);
+        const uint32_t h[4] = {q.x, q.y, q.z, q.w};
+        uint64_t bytes = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            uint32_t v = (h[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
+            if (v >= 0x8000u) v = w[v - 0x8000u];
+            seen |= v;
+            bytes |= (uint64_t)(v & 0xFFu) << (8 * j);
+        }
+        reinterpret_cast<GzBytes8 *>(o)->v = bytes;
+    } else {
+        for (uint32_t j = 0; k + j < n; j++) {
+            uint32_t v = s[j];
+            if (v >= 0x8000u) v = w[v - 0x8000u];
+            seen |= v;
+            o[j] = (uint8_t)v;
+        }
+    }
+    if (seen > 0xFFu) bad[ci] = 1;   // a reference before the member's first byte ("distance too far back" on the host)
+}
+
+namespace {
+struct GzDevice : TbkGzBackend {
+    int device = 0;
+    hipStream_t stream = nullptr, stream_in = nullptr, stream_out = nullptr;
+    hipEvent_t in_done = nullptr, done = nullptr, t0 = nullptr, t1 = nullptr;
+    GdX2n x2n = gd_x2n_table();
+    GdCrcTabs *d_crc_tabs = nullptr;
+    PinBuf h_in, h_out, h_chunks, h_res, h_win, h_members, h_offs, h_crc, h_bad, h_ctl;
+    DevBuf d_in, d_out, d_chunks, d_res, d_sym, d_members, d_offs, d_crc, d_bad, d_ctl;
+    int cus = 256, resident_wgs = 5;
+    size_t n_last = 0;
+    double pass_a_s = 0, pass_bcd_s = 0;   // the kernels' own time (HIP events), summed over the windows
+
+    int fail(int code, const char *what, hipError_t e) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "GPU gzip inflater: %s: %s", what, hipGetErrorString(e));
+        tbk_set_error_(code, buf);
+        (void)hipGetLastError();
+        return code;
+    }
+    int open(int dev) {
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess || dev < 0 || dev >= n) { (void)hipGetLastError(); tbk_set_error_(TBK_ERR_NO_DEVICE, "GPU gzip inflater: no such device"); return TBK_ERR_NO_DEVICE; }
+        device = dev;
+        hipError_t e = hipSetDevice(dev);
+        if (e != hipSuccess) return fail(TBK_ERR_HIP, "hipSetDevice", e);
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+        e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&stream_in, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&stream_out, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&in_done, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreate(&t0);
+        if (e == hipSuccess) e = hipEventCreate(&t1);
+        if (e == hipSuccess) {
+            GdCrcTabs tabs;
+            for (uint32_t j = 0; j < 128; j++) { tabs.lo[j] = gd_x2nmodp(x2n, j, 3 + 6); tabs.hi[j] = gd_x2nmodp(x2n, j, 3 + 6 + 7); }
+            e = hipMalloc((void **)&d_crc_tabs, sizeof tabs);
+            if (e == hipSuccess) e = hipMemcpy(d_crc_tabs, &tabs, sizeof tabs, hipMemcpyHostToDevice);
+        }
+        if (e != hipSuccess) return fail(TBK_ERR_HIP, "setup", e);
+        return TBK_OK;
+    }
+    ~GzDevice() override {
+        if (hipSetDevice(device) == hipSuccess) {
+            for (hipStream_t s : {stream, stream_in, stream_out}) if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+            for (PinBuf *p : {&h_in, &h_out, &h_chunks, &h_res, &h_win, &h_members, &h_offs, &h_crc, &h_bad, &h_ctl}) p->drop();
+            for (DevBuf *p : {&d_in, &d_out, &d_chunks, &d_res, &d_sym, &d_members, &d_offs, &d_crc, &d_bad, &d_ctl}) p->drop();
+            for (hipEvent_t ev : {in_done, done, t0, t1}) if (ev) (void)hipEventDestroy(ev);
+            if (d_crc_tabs) (void)hipFree(d_crc_tabs);
+        }
+    }
+    // a window's buffers ahead of its first use (what a window of in_bytes, n chunks, `symbols` elements and text_bytes of text needs)
+    int reserve(size_t in_bytes, size_t n, size_t symbols, size_t text_bytes) {
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = h_in.need(in_bytes + 64, true);
+        if (e == hipSuccess) e = d_in.need(in_bytes + 64, true);
+        if (e == hipSuccess) e = h_chunks.need(n * sizeof(TbkGzChunk));
+        if (e == hipSuccess) e = d_chunks.need(n * sizeof(TbkGzChunk));
+        if (e == hipSuccess) e = h_res.need(n * sizeof(TbkGzResult));
+        if (e == hipSuccess) e = d_res.need(n * sizeof(TbkGzResult));
+        if (e == hipSuccess) e = h_win.need(TBK_GZ_HIST * 2);
+        if (e == hipSuccess) e = h_ctl.need(64);
+        if (e == hipSuccess) e = d_ctl.need(64);
+        if (e == hipSuccess) e = d_sym.need(symbols * 2 + 64, true);
+        if (e == hipSuccess) e = h_members.need((n + 1) * sizeof(GdMember));
+        if (e == hipSuccess) e = d_members.need((n + 1) * sizeof(GdMember));
+        if (e == hipSuccess) e = h_offs.need((n + 1) * 8);
+        if (e == hipSuccess) e = d_offs.need((n + 1) * 8);
+        if (e == hipSuccess) e = h_crc.need((n + 1) * 4);
+        if (e == hipSuccess) e = d_crc.need((n + 1) * 4);
+        if (e == hipSuccess) e = h_bad.need(n + 64);
+        if (e == hipSuccess) e = d_bad.need(n + 64);
+        if (e == hipSuccess && text_bytes) e = h_out.need(text_bytes + 64, true);
+        if (e == hipSuccess && text_bytes) e = d_out.need(text_bytes + 64, true);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "buffers", e);
+        return TBK_OK;
+    }
+    int decode(const uint8_t *in, size_t in_bytes, const TbkGzChunk *chunks, size_t n, const uint16_t *window0, TbkGzResult *res) override {
+        if (!n || n > 0x7FFFFFF0ull) { tbk_set_error_(TBK_ERR_INVALID, "GPU gzip inflater: bad argument"); return TBK_ERR_INVALID; }
+        size_t symbols = 0;
+        for (size_t i = 0; i < n; i++) {
+            if ((chunks[i].sym_off & 7) || chunks[i].start_bit >= chunks[i].stop_bit) { tbk_set_error_(TBK_ERR_INVALID, "GPU gzip inflater: a malformed chunk"); return TBK_ERR_INVALID; }
+            if (chunks[i].sym_off < symbols) { tbk_set_error_(TBK_ERR_INVALID, "GPU gzip inflater: chunks overlap"); return TBK_ERR_INVALID; }
+            symbols = (size_t)chunks[i].sym_off + TBK_GZ_HIST + chunks[i].out_cap + 8;
+        }
+        int rc = reserve(in_bytes, n, symbols, 0);
+        if (rc) return rc;
+        if (in_bytes) memcpy(h_in.p, in, in_bytes);
+        memcpy(h_chunks.p, chunks, n * sizeof(TbkGzChunk));
+        memcpy(h_win.p, window0, TBK_GZ_HIST * 2);
+        uint32_t *ctl = (uint32_t *)h_ctl.p;
+        ctl[0] = 0; ctl[1] = 0xFFFFFFFFu;
+        uint16_t *d_s = (uint16_t *)d_sym.p;
+        hipError_t e = hipSuccess;
+        if (in_bytes) e = hipMemcpyAsync(d_in.p, h_in.p, in_bytes, hipMemcpyHostToDevice, stream_in);
+        if (e == hipSuccess) e = hipMemsetAsync((uint8_t *)d_in.p + in_bytes, 0, 64, stream_in);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_chunks.p, h_chunks.p, n * sizeof(TbkGzChunk), hipMemcpyHostToDevice, stream_in);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_ctl.p, h_ctl.p, 8, hipMemcpyHostToDevice, stream_in);
+        if (e == hipSuccess && chunks[0].window_known) e = hipMemcpyAsync(d_s + chunks[0].sym_off, h_win.p, TBK_GZ_HIST * 2, hipMemcpyHostToDevice, stream_in);
+        if (e == hipSuccess) e = hipMemsetAsync(d_res.p, 0, n * sizeof(TbkGzResult), stream_in);
+        if (e == hipSuccess) e = hipEventRecord(in_done, stream_in);
+        if (e == hipSuccess) e = hipStreamWaitEvent(stream, in_done, 0);
+        if (e == hipSuccess) e = hipEventRecord(t0, stream);
+        if (e == hipSuccess) {
+            const size_t wgs = std::min<size_t>((n + GI_WAVES - 1) / GI_WAVES, (size_t)cus * (size_t)resident_wgs);
+            hipLaunchKernelGGL(gz_inflate_kernel, dim3((unsigned)wgs), dim3(64 * GI_WAVES), 0, stream, (const uint8_t *)d_in.p, (uint64_t)in_bytes, (const TbkGzChunk *)d_chunks.p,
+                               (uint32_t)n, d_s, (TbkGzResult *)d_res.p, (uint32_t *)d_ctl.p);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(t1, stream);
+        if (e == hipSuccess) e = hipEventRecord(done, stream);
+        // (the statuses' copy home is queued when the kernel is done, as tbk_ginflate_wait queues its text's)
+        if (e == hipSuccess) e = hipEventSynchronize(done);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_res.p, d_res.p, n * sizeof(TbkGzResult), hipMemcpyDeviceToHost, stream_out);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_out);
+        float ms = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, t0, t1);
+        if (e != hipSuccess) return fail(TBK_ERR_HIP, "pass a", e);
+        pass_a_s += ms * 1e-3;
+        memcpy(res, h_res.p, n * sizeof(TbkGzResult));
+        n_last = n;
+        return TBK_OK;
+    }
+    int resolve(size_t n_acc, const TbkGzResult *res, const uint64_t *text_off, uint64_t text_total, uint8_t **text, uint32_t *crc, uint8_t *bad) override {
+        if (!n_acc || n_acc > n_last) { tbk_set_error_(TBK_ERR_STATE, "GPU gzip inflater: nothing decoded to resolve"); return TBK_ERR_STATE; }
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = h_out.need((size_t)text_total + 64);
+        if (e == hipSuccess) e = d_out.need((size_t)text_total + 64);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "buffers", e);
+        GdMember *hm = (GdMember *)h_members.p;
+        uint32_t longest = 0;
+        for (size_t i = 0; i < n_acc; i++) { hm[i] = GdMember{text_off[i], 0, res[i].n_sym, 0}; longest = std::max(longest, res[i].n_sym); }
+        memcpy(h_offs.p, text_off, n_acc * 8);
+        e = hipMemcpyAsync(d_members.p, h_members.p, n_acc * sizeof(GdMember), hipMemcpyHostToDevice, stream_in);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_offs.p, h_offs.p, n_acc * 8, hipMemcpyHostToDevice, stream_in);
+        if (e == hipSuccess) e = hipMemsetAsync(d_crc.p, 0, (n_acc + 1) * 4, stream_in);
+        if (e == hipSuccess) e = hipMemsetAsync(d_bad.p, 0, n_acc + 64, stream_in);
+        if (e == hipSuccess) e = hipEventRecord(in_done, stream_in);
+        if (e == hipSuccess) e = hipStreamWaitEvent(stream, in_done, 0);
+        if (e == hipSuccess) e = hipEventRecord(t0, stream);
+        if (e == hipSuccess) {
+            uint16_t *d_s = (uint16_t *)d_sym.p;
+            if (n_acc > 1) hipLaunchKernelGGL(gz_propagate_kernel, dim3(1), dim3(GZ_PROP_T), 0, stream, d_s, (const TbkGzChunk *)d_chunks.p, (const TbkGzResult *)d_res.p, (uint32_t)n_acc);
+            if (longest) {
+                for (size_t first = 0; first < n_acc; first += 65535) {
+                    const size_t part = std::min<size_t>(65535, n_acc - first);
+                    hipLaunchKernelGGL(gz_resolve_kernel, dim3((unsigned)(((uint64_t)longest + 8 * GD_T - 1) / (8 * GD_T)), (unsigned)part), dim3(GD_T), 0, stream, (const uint16_t *)d_s,
+                                       (const TbkGzChunk *)d_chunks.p, (const TbkGzResult *)d_res.p, (const uint64_t *)d_offs.p, (uint32_t)first, (uint8_t *)d_out.p, (uint8_t *)d_bad.p);
+                    hipLaunchKernelGGL(gd_crc_kernel, dim3((unsigned)std::max<uint64_t>(1, (((uint64_t)longest + 63) / 64 + GD_T - 1) / GD_T), (unsigned)part), dim3(GD_T), 0, stream,
+                                       (const uint8_t *)d_out.p, (const GdMember *)d_members.p + first, (const GdCrcTabs *)d_crc_tabs, x2n, (uint32_t *)d_crc.p + first);
+                }
+            }
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(t1, stream);
+        if (e == hipSuccess) e = hipEventRecord(done, stream);
+        if (e == hipSuccess) e = hipEventSynchronize(done);
+        if (e == hipSuccess && text_total) e = hipMemcpyAsync(h_out.p, d_out.p, (size_t)text_total, hipMemcpyDeviceToHost, stream_out);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_crc.p, d_crc.p, n_acc * 4, hipMemcpyDeviceToHost, stream_out);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_bad.p, d_bad.p, n_acc, hipMemcpyDeviceToHost, stream_out);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream_out);
+        float ms = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, t0, t1);
+        if (e != hipSuccess) return fail(TBK_ERR_HIP, "passes b-d", e);
+        pass_bcd_s += ms * 1e-3;
+        memcpy(crc, h_crc.p, n_acc * 4);
+        memcpy(bad, h_bad.p, n_acc);
+        *text = (uint8_t *)h_out.p;
+        return TBK_OK;
+    }
+};
+}  // namespace
+
+int tbk_gzinflate_create(int device, TbkGzBackend **out) {
+    *out = nullptr;
+    GzDevice *g = new GzDevice();
+    const int rc = g->open(device);
+    if (rc) { delete g; return rc; }
+    if (const char *v = getenv("TBK_BGZF_GPU_WGS")) g->resident_wgs = std::max(1, std::min(8, atoi(v)));
+    *out = g;
+    return TBK_OK;
+}
+void tbk_gzinflate_destroy(TbkGzBackend *g) { delete g; }
+int tbk_gzinflate_reserve(TbkGzBackend *g, size_t in_bytes, size_t n_chunks, size_t symbols, size_t text_bytes) { return static_cast<GzDevice *>(g)->reserve(in_bytes, n_chunks, symbols, text_bytes); }
+
+int tbk_gz_run_to_buffer(TbkGzBackend &be, const uint8_t *data, uint64_t size, uint8_t *dst, uint64_t cap, uint64_t *text_len, const TbkGzOptions &opt);  // tbk_gzplan.cpp
+
+// C-ABI (include/tbk.h)
+extern "C" int tbk_gzip_inflate_device_opts(int device, const uint8_t *data, uint64_t size, uint8_t *dst, uint64_t cap, uint64_t *text_len, uint64_t chunk, uint64_t window) {
+    if ((!data && size) || !text_len) { tbk_set_error_(TBK_ERR_INVALID, "tbk_gzip_inflate_device: NULL argument"); return TBK_ERR_INVALID; }
+    *text_len = 0;
+    TbkGzBackend *g = nullptr;
+    int rc = tbk_gzinflate_create(device, &g);
+    if (rc) return rc;
+    TbkGzOptions opt = tbk_gz_options_from_env(16);
+    if (chunk) opt.chunk = std::max<size_t>((size_t)chunk, 1024);
+    if (window) opt.window = (size_t)window;
+    opt.window = std::max(opt.window, opt.chunk);
+    rc = tbk_gz_run_to_buffer(*g, data, size, dst, cap, text_len, opt);
+    tbk_gzinflate_destroy(g);
+    return rc;
+}
+extern "C" int tbk_gzip_inflate_device(int device, const uint8_t *data, uint64_t size, uint8_t *dst, uint64_t cap, uint64_t *text_len) {
+    return tbk_gzip_inflate_device_opts(device, data, size, dst, cap, text_len, 0, 0);
+}
+
+// C-ABI (include/tbk.h): the inflater by itself, the whole file `reps` times.  *kernels_s: the kernels' own time per pass over the file
+// (HIP events around pass a and around passes b-d of every window: out[0] + out[1] of pass_s); *ring_s: wall time per pass over the file
+// as tbk_gzip_inflate_device drives it - guesses, staging copy, copies in and home included; pass_s[2]: the host's seconds of guessing.
+extern "C" int tbk_gzip_inflate_bench_device(int device, const uint8_t *data, uint64_t size, int reps, double *ring_s, double *kernels_s, uint64_t *text_bytes, double pass_s[3]) {
+    if (!data || !size || reps < 1 || !ring_s || !kernels_s || !text_bytes) { tbk_set_error_(TBK_ERR_INVALID, "tbk_gzip_inflate_bench_device: bad argument"); return TBK_ERR_INVALID; }
+    TbkGzBackend *be = nullptr;
+    int rc = tbk_gzinflate_create(device, &be);
+    if (rc) return rc;
+    GzDevice *g = static_cast<GzDevice *>(be);
+    const TbkGzOptions opt = tbk_gz_options_from_env(16);
+    uint64_t n = 0;
+    auto pass = [&](TbkGzStats *st) { n = 0; return tbk_gz_run(*g, data, (size_t)size, opt, [&](const uint8_t *, size_t len, bool) { n += len; return true; }, st, nullptr); };
+    TbkGzStats st;
+    rc = pass(&st);   // every buffer exists
+    g->pass_a_s = g->pass_bcd_s = 0;
+    double guess = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int i = 0; i < reps && !rc; i++) { rc = pass(&st); guess += st.guess_s; }
+    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (!rc) {
+        *ring_s = wall / reps;
+        *kernels_s = (g->pass_a_s + g->pass_bcd_s) / reps;
+        *text_bytes = n;
+        if (pass_s) { pass_s[0] = g->pass_a_s / reps; pass_s[1] = g->pass_bcd_s / reps; pass_s[2] = guess / reps; }
+    }
+    tbk_gzinflate_destroy(be);
     return rc;
 }

@@ -36,6 +36,24 @@ public:
     uint64_t bit_position() const { return (uint64_t)(ip_ - in_) * 8 - (uint64_t)bitcnt_; }
     // Start decoding at bit `bitpos` if a non-final dynamic-Huffman block can begin there.
     bool open_dynamic_block_at(const uint8_t *data, size_t size, uint64_t bitpos);
+    // Stand in front of the block header at bit `bitpos`, a block boundary of the real chain that the caller knows (where a chunk of
+    // the GPU's gzip inflater ended, tbk_gzplan.cpp): run() / run16() go on from there as if they had decoded up to it themselves.
+    void position_at_bit(const uint8_t *data, size_t size, uint64_t bitpos) {
+        reset(data, size);
+        ip_ = in_ + (size_t)(bitpos >> 3);
+        refill();
+        take((int)(bitpos & 7));
+        state_ = BLOCK_HEAD;
+    }
+    // The header of the gzip member at byte `off` (zero padding in front of it is skipped): true when bit_position() stands on
+    // its first block header, or - *at_end - when nothing but padding was left; false: error().
+    bool open_member_at(const uint8_t *data, size_t size, size_t off, bool *at_end) {
+        reset(data, size);
+        ip_ = in_ + (off < size ? off : size);
+        if (!parse_header()) return false;
+        *at_end = state_ == HEADER;
+        return true;
+    }
     const char *error() const { return err_ ? err_ : ""; }
     // CRC-32 and ISIZE from the trailer of the member that just ended (after MEMBER_DONE)
     uint32_t trailer_crc() const { return t_crc_; }

@@ -269,8 +269,9 @@ class BatchReader:
     ``Batch`` and returns the number of records (0 at end of input)."""
 
     def __init__(self, filename: str, packing: bool = False, borrowing: bool = False, device: Optional[int] = None):
-        """``device``: BGZF input is inflated on that GPU (``tbk_fastx_set_device``: what ``classify-by-kmers`` does by itself);
-        None: on the host's threads.  ``inflates_on_device`` says which it is."""
+        """``device``: BGZF input is inflated on that GPU (``tbk_fastx_set_device``: what ``classify-by-kmers`` does by itself),
+        and with ``TBK_GZIP_INFLATE=gpu`` an ordinary gzip file as well (``gzip_stats``); None: on the host's threads.
+        ``inflates_on_device`` says which it is."""
         import ctypes as C
         import os
 
@@ -310,6 +311,17 @@ class BatchReader:
             self.close()
         except Exception:
             pass
+
+    def gzip_stats(self) -> dict:
+        """The GPU gzip inflater's counts for this reader so far (``gzip_inflate_stats``'s keys); zeros when it is not in use."""
+        import ctypes as C
+
+        from ._lib import lib
+
+        out = (C.c_uint64 * 6)()
+        if self._h:
+            lib.tbk_fastx_gzip_stats(self._h, out)
+        return dict(zip(("windows", "guessed", "accepted", "redecoded", "handed_back", "most_accepted"), (int(v) for v in out)))
 
     def __enter__(self):
         return self
@@ -407,3 +419,49 @@ def bgzf_inflate_device(data: bytes, device: int = 0) -> bytes:
     buf = C.create_string_buffer(n.value)
     check(lib.tbk_bgzf_inflate_device(device, data, len(data), buf, n.value, C.byref(n)))
     return C.string_at(C.addressof(buf), n.value)
+
+
+def _gzip_inflate(call, data: bytes) -> bytes:
+    import ctypes as C
+
+    from ._lib import TBK_ERR_NOMEM, check
+
+    # ISIZE (the last four bytes) is the size modulo 2^32 of the LAST member only: a first guess; the call says what it takes
+    hint = int.from_bytes(data[-4:], "little") if len(data) >= 18 else 0
+    n = C.c_uint64()
+    cap = max(hint, 1 << 16)
+    buf = C.create_string_buffer(cap)
+    status = call(buf, cap, C.byref(n))
+    if status == TBK_ERR_NOMEM and n.value > cap:
+        cap = n.value
+        buf = C.create_string_buffer(cap)
+        status = call(buf, cap, C.byref(n))
+    check(status)
+    return C.string_at(C.addressof(buf), n.value)
+
+
+def gzip_inflate_stats() -> dict:
+    """Of this thread's last ``gzip_inflate_device`` / ``gzip_inflate_host``: windows, chunks guessed / accepted / decoded again,
+    bytes handed back to the host path, the most chunks accepted in one window."""
+    import ctypes as C
+
+    from ._lib import lib
+
+    out = (C.c_uint64 * 6)()
+    lib.tbk_gzip_inflate_stats(out)
+    return dict(zip(("windows", "guessed", "accepted", "redecoded", "handed_back", "most_accepted"), (int(v) for v in out)))
+
+
+def gzip_inflate_device(data: bytes, device: int = 0, chunk: Optional[int] = None, window: Optional[int] = None) -> bytes:
+    """The text of an ordinary gzip file (bytes; one member or several), inflated on the GPU (``tbk_gzip_inflate_device``): what
+    ``gzip.decompress`` returns.  ``chunk`` / ``window``: compressed bytes per chunk / per window (None: the defaults)."""
+    from ._lib import lib
+
+    return _gzip_inflate(lambda buf, cap, n: lib.tbk_gzip_inflate_device_opts(device, data, len(data), buf, cap, n, chunk or 0, window or 0), data)
+
+
+def gzip_inflate_host(data: bytes, chunk: Optional[int] = None, window: Optional[int] = None) -> bytes:
+    """``gzip_inflate_device``'s plan, chain check and loop with the host's decoder in the device's place (no GPU)."""
+    from ._lib import lib
+
+    return _gzip_inflate(lambda buf, cap, n: lib.tbk_gzip_inflate_host(data, len(data), buf, cap, n, chunk or 0, window or 0), data)
