@@ -1,7 +1,8 @@
 """Host code of the library (list parser, FASTX reader, bin writer, TSV formatter, error paths)
 under AddressSanitizer + UndefinedBehaviorSanitizer.  CPU only: the sanitized build is loaded
 through TBK_LIBRARY in a child interpreter with the ASan runtime preloaded, and the native-I/O,
-packer, multi-device dealer and CLI host tests are re-run against it."""
+packer, multi-device dealer and CLI host tests and the gzip inflater's host side on the files of
+tests/gzip_shapes.py are re-run against it."""
 import glob
 import os
 import subprocess
@@ -31,7 +32,8 @@ def test_host_code_under_asan_ubsan(built):
                         os.path.join(ROOT, "tests", "test_host_native_io.py"),
                         os.path.join(ROOT, "tests", "test_host_pack.py"),
                         os.path.join(ROOT, "tests", "test_multi_cpu.py"),
-                        os.path.join(ROOT, "tests", "test_host_cli.py")],
+                        os.path.join(ROOT, "tests", "test_host_cli.py"),
+                        os.path.join(ROOT, "tests", "test_host_gzip_shapes.py")],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     out = p.stdout + p.stderr
     assert "AddressSanitizer" not in out and "runtime error:" not in out, out[-4000:]

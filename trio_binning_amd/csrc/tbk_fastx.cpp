@@ -154,6 +154,8 @@ struct LineSource {
     }
     bool skip_lf = false;      // previous line ended in '\r' at the window edge: swallow a leading '\n'
     std::string err;
+    std::string worker_err;    // the error the inflating thread ended with: every later refill gives it again.  (Every worker loop
+                               // ENDS behind the chunk that carries its error - c.err, c.last - so nothing follows that chunk.)
     // BGZF (bgzip) files are gzip files whose members are independent blocks of <= 64 KiB that
     // carry their own compressed size in a "BC" extra subfield: such members can be inflated side
     // by side.  Same bytes as the sequential path; taken while every member at hand is such a block.
@@ -330,6 +332,7 @@ struct LineSource {
         // worth, at most 64 MiB and a record, is at hand): the window is then parsed where it lies.  0 = every window is copied.
         const size_t head_room = env_size("TBK_BGZF_GPU_ROOM", (size_t)72 << 20);
         auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+        // (whoever pushes a chunk with an error ends its loop: refill_fast keeps the error and never waits behind that chunk)
         auto fail_with = [&](const std::string &msg) { Chunk c; c.err = msg; c.last = true; push(std::move(c)); };
         // The windows on the device, oldest first, and the thread that takes them home: it waits for a window's kernels, copies its text
         // into the slot's pinned output and hands it to the parser, while this thread stages the next window.
@@ -753,6 +756,7 @@ struct LineSource {
     }
     // own decoder: returns like refill()
     bool refill_fast() {
+        if (!worker_err.empty()) { err = worker_err; return false; }   // (the worker ended with it: said again, not waited for)
         if (!started) { started = true; worker = std::thread([this] { if (bgzf && gpu_device >= 0 && map) bgzf_loop_gpu(); else if (bgzf) bgzf_loop(); else if (gzip_gpu) gzip_loop_gpu(); else if (guessing()) pinflate_loop(); else inflate_loop(); }); }
         Chunk c;
         {
@@ -764,7 +768,7 @@ struct LineSource {
             ready.pop_front();
             cv.notify_all();
         }
-        if (!c.err.empty()) { err = c.err; return false; }
+        if (!c.err.empty()) { worker_err = err = c.err; return false; }
         if (c.ext && c.hold && end - pos <= c.room) {
             // a window of the GPU inflater, and room in front of it for what is left of the text at hand: parsed where it lies
             const size_t left = end - pos;

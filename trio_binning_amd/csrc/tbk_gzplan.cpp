@@ -39,8 +39,10 @@ TbkGzOptions tbk_gz_options_from_env(int threads) {
     o.threads = std::max(1, std::min(threads, 64));
     if (const char *e = getenv("TBK_GZIP_CHUNK")) if (*e) o.chunk = (size_t)strtoull(e, nullptr, 10);
     if (const char *e = getenv("TBK_GZIP_WINDOW")) if (*e) o.window = (size_t)strtoull(e, nullptr, 10);
+    if (const char *e = getenv("TBK_GZIP_RATIO")) if (*e) o.ratio = (size_t)strtoull(e, nullptr, 10);
     o.chunk = std::max<size_t>(o.chunk, 1024);
     o.window = std::max<size_t>(o.window, o.chunk);
+    o.ratio = std::min(std::max<size_t>(o.ratio, 1), GZ_MAX_RATIO);
     return o;
 }
 
@@ -124,7 +126,7 @@ int tbk_gz_run(TbkGzBackend &be, const uint8_t *data, size_t size, const TbkGzOp
     std::vector<uint32_t> crcs;
     std::vector<uint8_t> bad;
     std::vector<uint16_t> tail(TBK_GZ_HIST);
-    size_t ratio = 6, off = 0;
+    size_t ratio = opt.ratio, off = 0;   // (1 .. GZ_MAX_RATIO: tbk_gz_options_from_env)
     for (;;) {   // members
         bool at_end = false;
         if (!hdr->open_member_at(data, size, off, &at_end)) return done(TBK_ERR_FORMAT, std::string("inflate: ") + hdr->error());
@@ -227,6 +229,7 @@ struct HostBackend : TbkGzBackend {
             TbkGzResult r = {TBK_GZ_FAILED, (uint32_t)(pos - TBK_GZ_HIST), d->bit_position()};
             if (st == TbkInflate::BOUNDARY) r.status = TBK_GZ_BOUNDARY;
             else if (st == TbkInflate::MEMBER_DONE) { r.status = TBK_GZ_MEMBER_DONE; r.end_bit -= 64; }   // (run16 has read the trailer)
+            else if (st == TbkInflate::ERROR && d->cut_in_trailer()) r.status = TBK_GZ_MEMBER_DONE;   // (as the device, which never reads a trailer: the loop finds it cut)
             else if (st == TbkInflate::NEED_OUTPUT) r.status = TBK_GZ_NO_ROOM;
             else if (st == TbkInflate::ERROR && strcmp(d->error(), "truncated gzip file") == 0) r.status = TBK_GZ_NO_INPUT;
             res[i] = r;

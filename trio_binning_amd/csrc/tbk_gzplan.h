@@ -42,8 +42,9 @@ struct TbkGzOptions {
     size_t window = (size_t)256 << 20;   // compressed bytes per window
     int threads = 16;                    // for the block-start guesses
     size_t max_symbols = (size_t)3 << 29;   // elements of one window's symbol buffer at the most
+    size_t ratio = 6;                    // symbols of room per compressed byte to begin with (a chunk without room doubles it)
 };
-// TBK_GZIP_CHUNK / TBK_GZIP_WINDOW (tests) over the defaults
+// TBK_GZIP_CHUNK / TBK_GZIP_WINDOW / TBK_GZIP_RATIO (tests) over the defaults
 TbkGzOptions tbk_gz_options_from_env(int threads);
 
 // The next window's chunks: chunk 0 at `start_bit` (exact), the others at the first bit of their span of opt.chunk bytes where a

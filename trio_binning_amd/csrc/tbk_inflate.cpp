@@ -356,7 +356,7 @@ TbkInflate::Status TbkInflate::run_impl(T *out, size_t *pos, size_t cap, size_t 
         }
         case TRAILER: {
             byte_align_and_unread();
-            if (in_end_ - ip_ < 8) return fail("truncated gzip file");
+            if (in_end_ - ip_ < 8) { *pos = (size_t)(op - out); return fail("truncated gzip file"); }
             t_crc_ = ip_[0] | ((uint32_t)ip_[1] << 8) | ((uint32_t)ip_[2] << 16) | ((uint32_t)ip_[3] << 24);
             t_isize_ = ip_[4] | ((uint32_t)ip_[5] << 8) | ((uint32_t)ip_[6] << 16) | ((uint32_t)ip_[7] << 24);
             ip_ += 8;

@@ -58,6 +58,8 @@ public:
     // CRC-32 and ISIZE from the trailer of the member that just ended (after MEMBER_DONE)
     uint32_t trailer_crc() const { return t_crc_; }
     uint32_t trailer_isize() const { return t_isize_; }
+    // after ERROR: the final block was decoded whole and the input ends inside the eight bytes behind it (*pos holds the text's end)
+    bool cut_in_trailer() const { return state_ == TRAILER; }
     bool at_end() const { return state_ == HEADER && bits_consumed_past_end() == 0 && ip_ - (bitcnt_ >> 3) >= in_end_; }
 
 private:

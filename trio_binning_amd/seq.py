@@ -427,7 +427,8 @@ def _gzip_inflate(call, data: bytes) -> bytes:
     from ._lib import TBK_ERR_NOMEM, check
 
     # ISIZE (the last four bytes) is the size modulo 2^32 of the LAST member only: a first guess; the call says what it takes
-    hint = int.from_bytes(data[-4:], "little") if len(data) >= 18 else 0
+    # (and of a file that is damaged or cut, no size at all: DEFLATE makes at most 1032 bytes of one)
+    hint = min(int.from_bytes(data[-4:], "little"), 1032 * len(data)) if len(data) >= 18 else 0
     n = C.c_uint64()
     cap = max(hint, 1 << 16)
     buf = C.create_string_buffer(cap)
