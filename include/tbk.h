@@ -631,6 +631,42 @@ typedef struct tbk_counter tbk_counter;
  * when HBM cannot hold that. */
 int tbk_counter_create(int k, uint64_t capacity_kmers, int device, tbk_counter **out);
 void tbk_counter_destroy(tbk_counter *c);
+/* Counting in passes, for libraries whose distinct k-mers (sequencing errors included) outgrow one table in HBM.
+ * The canonical k-mers fall into `passes` classes by a hash of the k-mer alone.  Every batch added is kept on the
+ * device in packed form - one 64-bit word per 16 bases: 2-bit codes and a not-ACGT bit, 0.5 bytes per base - while
+ * class 0 is counted from it into a table sized for ONE class (it starts at capacity_kmers / passes and grows by
+ * the rule above).  Finishing turns the table into the class's database - the k-mers seen at least twice with
+ * their counter capped at 255, 9 bytes each; the k-mers seen once only enter the histogram - then counts class 1,
+ * 2, ... from the kept reads into the same table, one after the other, and frees store and table.  Histogram,
+ * subtraction and dump then work on the databases and give what one pass gives.  passes = 1 is
+ * tbk_counter_create: nothing is kept, nothing is distilled. */
+#define TBK_COUNTER_MAX_PASSES 1024
+typedef struct tbk_counter_options {
+    uint32_t size;              /* sizeof(tbk_counter_options) of the caller (tbk_counter_options_init sets it) */
+    int32_t passes;             /* >= 1 */
+    uint64_t store_limit_bytes; /* most the kept reads may take; 0: whatever HBM gives.  A batch that would pass
+                                 * it (or that HBM cannot take) is TBK_ERR_NOMEM; nothing spills to the host. */
+} tbk_counter_options;
+void tbk_counter_options_init(tbk_counter_options *o);  /* passes = 1, no limit */
+/* opts may be NULL (= tbk_counter_create). */
+int tbk_counter_create_opts(int k, uint64_t capacity_kmers, const tbk_counter_options *opts, int device, tbk_counter **out);
+/* No more batches: adding to a finished counter is TBK_ERR_INVALID.  With passes > 1 this counts the remaining
+ * classes (see above); tbk_counter_histogram, tbk_counter_distinct and tbk_counter_unique finish such a counter
+ * themselves.  With passes = 1 only this call finishes, and it does nothing else. */
+int tbk_counter_finish(tbk_counter *c);
+typedef struct tbk_counter_info {
+    uint32_t size;              /* in: sizeof(tbk_counter_info) of the caller */
+    int32_t passes;
+    int32_t finished;
+    uint32_t reserved;
+    uint64_t store_bytes;       /* HBM held by the kept reads (0 once finished, and with passes = 1) */
+    uint64_t store_used_bytes;  /* of which filled: 8 bytes per 16 bases of the separated stream, each batch rounded up */
+    uint64_t peak_table_bytes;  /* the largest table held at any time (while it is rebuilt, the old one is held too) */
+    uint64_t database_bytes;    /* 9 bytes per k-mer seen at least twice, over the classes distilled so far */
+    uint64_t distinct;          /* distinct k-mers met: the classes distilled so far plus the class in the table;
+                                 * never finishes the counter (tbk_counter_distinct does) */
+} tbk_counter_info;
+int tbk_counter_stats_ex(const tbk_counter *c, tbk_counter_info *info);
 /* Count the canonical k-mers of a batch of reads (the classifier's batch layout; host memory). */
 int tbk_counter_add_batch(tbk_counter *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads);
 /* Same for a batch already in HBM (d_bases readable up to total_bases). */
@@ -643,7 +679,8 @@ int tbk_counter_adds_issued(tbk_counter *c, uint64_t *adds);
  * kmc_tools writes, except that KMC's -ci2 database has no row-1 k-mers (callers zero hist[1]);
  * hist[0]: all distinct k-mers met. */
 int tbk_counter_histogram(tbk_counter *c, uint64_t hist[256]);
-/* Distinct k-mers met so far (slots taken). */
+/* Distinct k-mers met so far (slots taken).  A counter working in passes is finished first: the number is the sum
+ * over its classes. */
 int tbk_counter_distinct(const tbk_counter *c, uint64_t *distinct);
 int tbk_counter_stats(const tbk_counter *c, uint64_t *n_slots, uint64_t *table_bytes, uint64_t *bases_added, uint64_t *reads_added);
 /* Bucket selection of the table as it stands (it is chosen again whenever the table is rebuilt): w m-mers of m bases
@@ -652,7 +689,8 @@ int tbk_counter_stats(const tbk_counter *c, uint64_t *n_slots, uint64_t *table_b
 int tbk_counter_params(const tbk_counter *c, int *w, int *m, int *o, int *t);
 /* kmers_subtract + kmc_dump: write to out_path, one k-mer per line in lexicographic order, the
  * k-mers of `a` seen at least twice whose counter lies in [min_count, max_count] and that `b` has
- * seen at most once. */
+ * seen at most once.  Both counters must work in the same number of passes (TBK_ERR_INVALID otherwise: their
+ * classes would not match); counters working in passes are finished first, and the file is the same. */
 int tbk_counter_unique(tbk_counter *a, tbk_counter *b, uint32_t min_count, uint32_t max_count, const char *out_path,
                        uint64_t *n_written);
 

@@ -11,6 +11,7 @@ ap.add_argument("--coverage", type=float, default=30.0)
 ap.add_argument("--read-len", type=int, default=150)
 ap.add_argument("--split", type=int, default=1, help="files per parent library")
 ap.add_argument("--gzip", action="store_true", help="gzip the parents' FASTQ files")
+ap.add_argument("--passes", type=int, default=0, help="find-unique-kmers --passes (0: it chooses)")
 a = ap.parse_args()
 k = 21
 rng = np.random.default_rng(5)
@@ -45,7 +46,7 @@ for h, name in zip(haps, ("mother", "father")):
     del reads
 env = dict(os.environ, PYTHONPATH=ROOT)
 t = time.time()
-p = subprocess.run([sys.executable, "-m", "trio_binning_amd.find_unique_kmers", "-k", str(k), "-o", tmp, "-s", tmp, files[0], files[1]], env=env, capture_output=True)
+p = subprocess.run([sys.executable, "-m", "trio_binning_amd.find_unique_kmers", "-k", str(k), "-o", tmp, "-s", tmp, "--passes", str(a.passes), files[0], files[1]], env=env, capture_output=True)
 t_unique = time.time() - t
 assert p.returncode == 0, p.stderr.decode()[-2000:]
 err = p.stderr.decode()
@@ -65,7 +66,7 @@ assert p2.returncode == 0, p2.stderr.decode()[-2000:]
 bins = [l.split("\t")[1] for l in p2.stdout.decode().splitlines()]
 right = sum(1 for i, b in enumerate(bins) if b == "AB"[i % 2])
 print(json.dumps({"genome": a.genome, "parent_reads": n_reads, "parent_gbases_each": round(n_reads * a.read_len / 1e9, 3),
-                  "files_per_parent": a.split, "gzip": a.gzip, "file_GB_each_parent": round(sum(os.path.getsize(f) for f in files[0].split(",")) / 1e9, 2), "find_unique_s": round(t_unique, 2),
+                  "files_per_parent": a.split, "passes": a.passes, "gzip": a.gzip, "file_GB_each_parent": round(sum(os.path.getsize(f) for f in files[0].split(",")) / 1e9, 2), "find_unique_s": round(t_unique, 2),
                   "cutoffs": [l for l in err.splitlines() if "Using counts" in l], "list_sizes": n_list,
                   "classify_s": round(t_classify, 2), "child_reads": n_long, "binned_to_the_right_parent": right}))
 for f in os.listdir(tmp): os.remove(os.path.join(tmp, f))

@@ -172,6 +172,24 @@ if hasattr(lib, "tbk_classifier_sweep_keys"):  # (variant builds of tools/build_
 _sig("tbk_host_threads", C.c_int)
 _sig("tbk_counter_create", C.c_int, C.c_int, _u64, C.c_int, C.POINTER(_vp))
 _sig("tbk_counter_destroy", None, _vp)
+
+
+class CounterOptions(C.Structure):
+    """tbk_counter_options (include/tbk.h)."""
+    _fields_ = [("size", C.c_uint32), ("passes", C.c_int32), ("store_limit_bytes", C.c_uint64)]
+
+
+class CounterInfo(C.Structure):
+    """tbk_counter_info (include/tbk.h)."""
+    _fields_ = [("size", C.c_uint32), ("passes", C.c_int32), ("finished", C.c_int32), ("reserved", C.c_uint32),
+                ("store_bytes", C.c_uint64), ("store_used_bytes", C.c_uint64), ("peak_table_bytes", C.c_uint64),
+                ("database_bytes", C.c_uint64), ("distinct", C.c_uint64)]
+
+
+_sig("tbk_counter_options_init", None, C.POINTER(CounterOptions))
+_sig("tbk_counter_create_opts", C.c_int, C.c_int, _u64, C.POINTER(CounterOptions), C.c_int, C.POINTER(_vp))
+_sig("tbk_counter_finish", C.c_int, _vp)
+_sig("tbk_counter_stats_ex", C.c_int, _vp, C.POINTER(CounterInfo))
 _sig("tbk_counter_add_batch", C.c_int, _vp, _vp, _vp, _u64)
 _sig("tbk_counter_add_device", C.c_int, _vp, _vp, _vp, _u64, _u64)
 _sig("tbk_counter_kernel_timing", C.c_int, _vp, _u64p, _u64p, _dp, C.c_int)

@@ -118,6 +118,21 @@ TBK_HD uint32_t tbk_mix32(uint64_t key) {
     return h;
 }
 
+// Class of a canonical k-mer when the counter works in passes (tbk_count.cpp): a function of the key and the
+// number of classes alone - not of the table's size or its minimizer parameters - so both parents' counters,
+// and a table before and after it is rebuilt, agree on it.  A hash of its own (other multipliers, another
+// finaliser than tbk_mix32): plain mode takes the bucket from the top bits of tbk_mix32(key), and a class cut
+// from those bits would fill only 1 / n_classes of the buckets.
+TBK_HD uint32_t tbk_class_of(uint64_t key, uint32_t n_classes) {
+    uint32_t h = ((uint32_t)key ^ 0x2545F491u) * 0xCC9E2D51u + ((uint32_t)(key >> 32) ^ 0x68E31DA4u) * 0x1B873593u;
+    h ^= h >> 16;
+    h *= 0x7FEB352Du;
+    h ^= h >> 15;
+    h *= 0x846CA68Bu;
+    h ^= h >> 16;
+    return (uint32_t)(((uint64_t)h * (uint64_t)n_classes) >> 32);
+}
+
 // bucket = floor(h * n_buckets / 2^32): uniform over [0, n_buckets) without a division.
 TBK_HD uint32_t tbk_reduce(uint32_t h, uint32_t n_buckets) {
     return (uint32_t)(((uint64_t)h * (uint64_t)n_buckets) >> 32);

@@ -40,6 +40,13 @@ extern "C" hipError_t tbk_launch_count_histogram(uint64_t *, uint32_t, TbkMz, un
 extern "C" hipError_t tbk_launch_count_unique(uint64_t *, uint32_t, TbkMz, uint64_t *, uint32_t, TbkMz, int, uint32_t, uint32_t,
                                               uint64_t *, uint64_t, unsigned long long *, hipStream_t);
 extern "C" hipError_t tbk_launch_sort_u64(const uint64_t *, uint64_t *, uint64_t, int, hipStream_t);
+// pass mode
+extern "C" hipError_t tbk_launch_retain(const uint8_t *, uint64_t, uint64_t *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_count_class(const uint64_t *, uint64_t, uint64_t, uint64_t, int, uint64_t *, uint32_t, TbkMz, int *, unsigned long long *,
+                                             uint32_t, uint32_t, hipStream_t);
+extern "C" hipError_t tbk_launch_count_distil(uint64_t *, uint32_t, TbkMz, uint64_t *, uint8_t *, uint64_t, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_db_unique(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, int, uint32_t, uint32_t, uint64_t *,
+                                           uint64_t, unsigned long long *, hipStream_t);
 
 static int cfail(int code, const char *fmt, ...) {
     char buf[512];
@@ -76,6 +83,27 @@ struct tbk_counter {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     uint64_t timed_launches = 0, timed_windows = 0;
     double timed_ms = 0.0;
+    uint64_t peak_table_bytes = 0;  // the largest table this counter has held
+    bool finished = false;          // no more batches (tbk_counter_finish)
+    bool broken = false;            // finishing failed half way: nothing more can be asked of the counter
+    // ---- pass mode (passes > 1) -----------------------------------------------------------------------
+    // The canonical k-mers fall into `passes` classes (tbk_class_of).  Every batch is retained on the device in
+    // packed form (tbk_retain_kernel) while class 0 is counted from it; finishing distils class 0 into its
+    // database - the keys seen at least twice and their capped counters - counts class 1, 2, ... from the store
+    // into the same table, distilling each, and then frees store and table.  The table only ever holds one class.
+    int passes = 1;
+    uint64_t store_limit = 0;  // bytes the store may take (0: what HBM gives)
+    struct Segment { uint64_t *d = nullptr; uint64_t cap = 0, used = 0; };  // 64-bit words
+    struct Piece { uint32_t segment; uint64_t first, words; };              // one batch: whole words of one segment
+    std::vector<Segment> segments;
+    std::vector<Piece> pieces;
+    uint64_t store_bytes = 0, store_words = 0;  // allocated bytes; words in use
+    struct ClassDb { uint64_t *d_keys = nullptr; uint8_t *d_counts = nullptr; uint64_t n = 0; };
+    std::vector<ClassDb> db;                    // one per finished class
+    uint64_t database_bytes = 0;
+    unsigned long long *d_hist = nullptr;       // running histogram of the classes distilled so far
+    uint64_t hist[256] = {0};                   // its host copy
+    uint64_t distinct_done = 0;                 // distinct k-mers of the classes distilled so far
 };
 
 static int counter_device(const tbk_counter *c) {
@@ -86,7 +114,7 @@ static int counter_device(const tbk_counter *c) {
 }
 
 // lines for `capacity` distinct k-mers at the counter's target load; keys = all ones (free), counters = 0
-static int alloc_lines(int k, uint64_t capacity, double load, uint64_t **d_lines, uint32_t *n_buckets, TbkMz *mz) {
+static int alloc_lines(int k, uint64_t capacity, double load, uint64_t **d_lines, uint32_t *n_buckets, TbkMz *mz, uint64_t *peak) {
     uint64_t nb = (uint64_t)((double)capacity / (TBK_SLOTS_PER_BUCKET * load)) + 16;
     if (nb > 0x7FFFFFF0ull) return cfail(TBK_ERR_NOMEM, "%llu distinct k-mers are more than one table holds", (unsigned long long)capacity);
     const size_t bytes = (size_t)nb * 128;
@@ -101,16 +129,37 @@ static int alloc_lines(int k, uint64_t capacity, double load, uint64_t **d_lines
                      (unsigned long long)capacity, bytes, hipGetErrorString(e));
     }
     *n_buckets = (uint32_t)nb;
+    if (peak && bytes > *peak) *peak = bytes;
     const char *ew = getenv("TBK_COUNT_W"), *em = getenv("TBK_COUNT_M");
     *mz = tbk_mz_params(k, ew ? atoi(ew) : 6, capacity, em ? atoi(em) : 0, 0);
     return TBK_OK;
 }
 
+extern "C" void tbk_counter_options_init(tbk_counter_options *o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->size = (uint32_t)sizeof *o;
+    o->passes = 1;
+}
+
 extern "C" int tbk_counter_create(int k, uint64_t capacity_kmers, int device, tbk_counter **out) {
+    return tbk_counter_create_opts(k, capacity_kmers, nullptr, device, out);
+}
+
+extern "C" int tbk_counter_create_opts(int k, uint64_t capacity_kmers, const tbk_counter_options *opts, int device, tbk_counter **out) {
     if (!out) return cfail(TBK_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (k < 1 || k > 32) return cfail(TBK_ERR_INVALID, "k = %d out of range (1..32)", k);
     if (!capacity_kmers) return cfail(TBK_ERR_INVALID, "capacity is 0");
+    tbk_counter_options o;
+    tbk_counter_options_init(&o);
+    if (opts) {
+        if (opts->size < 8 || opts->size > sizeof o) return cfail(TBK_ERR_INVALID, "tbk_counter_options.size = %u (this library knows %zu bytes)", opts->size, sizeof o);
+        memcpy(&o, opts, opts->size);
+        o.size = (uint32_t)sizeof o;
+    }
+    if (o.passes < 1 || o.passes > TBK_COUNTER_MAX_PASSES)
+        return cfail(TBK_ERR_INVALID, "passes = %d out of range (1..%d)", o.passes, TBK_COUNTER_MAX_PASSES);
     tbk_counter tmp;
     tmp.device = device;
     int rc = counter_device(&tmp);
@@ -120,12 +169,18 @@ extern "C" int tbk_counter_create(int k, uint64_t capacity_kmers, int device, tb
     // twice as large whenever the next batch could fill it.
     tbk_counter *c = new tbk_counter();
     c->device = device; c->k = k;
+    c->passes = o.passes; c->store_limit = o.store_limit_bytes;
+    if (c->passes > 1) capacity_kmers = std::max<uint64_t>(1, capacity_kmers / (uint64_t)c->passes);  // the table holds one class
     const char *ev = getenv("TBK_COUNT_LOAD");
     c->load = ev ? atof(ev) : 0.6;
     if (c->load < 0.05) c->load = 0.05;
     if (c->load > 0.9) c->load = 0.9;
-    rc = alloc_lines(k, capacity_kmers, c->load, &c->d_lines, &c->n_buckets, &c->mz);
+    rc = alloc_lines(k, capacity_kmers, c->load, &c->d_lines, &c->n_buckets, &c->mz, &c->peak_table_bytes);
     hipError_t e = hipSuccess;
+    if (!rc && c->passes > 1) {
+        e = hipMalloc((void **)&c->d_hist, 256 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMemset(c->d_hist, 0, 256 * sizeof(unsigned long long));
+    }
     if (!rc) e = hipMalloc((void **)&c->d_failed, sizeof(int));
     if (!rc && e == hipSuccess) e = hipMalloc((void **)&c->d_used, 1025 * sizeof(unsigned long long));
     if (!rc && e == hipSuccess) e = hipMemset(c->d_failed, 0, sizeof(int));
@@ -141,7 +196,7 @@ static int counter_grow(tbk_counter *c, uint64_t capacity) {
     uint64_t *d_new = nullptr;
     uint32_t nb = 0;
     TbkMz mz{0, 0, 0, 0};
-    int rc = alloc_lines(c->k, capacity, c->load, &d_new, &nb, &mz);
+    int rc = alloc_lines(c->k, capacity, c->load, &d_new, &nb, &mz, &c->peak_table_bytes);
     if (rc) return rc;
     hipError_t e = tbk_launch_count_rehash(c->d_lines, c->n_buckets, c->mz, d_new, nb, mz, c->d_failed, nullptr);
     int failed = 0;
@@ -161,26 +216,26 @@ extern "C" void tbk_counter_destroy(tbk_counter *c) {
         (void)hipDeviceSynchronize();
         if (c->ev0) (void)hipEventDestroy(c->ev0);
         if (c->ev1) (void)hipEventDestroy(c->ev1);
-        for (void *p : {(void *)c->d_lines, (void *)c->d_failed, (void *)c->d_used, (void *)c->d_raw, (void *)c->d_sep, (void *)c->d_off})
+        for (void *p : {(void *)c->d_lines, (void *)c->d_failed, (void *)c->d_used, (void *)c->d_raw, (void *)c->d_sep, (void *)c->d_off, (void *)c->d_hist})
             if (p) (void)hipFree(p);
+        for (const tbk_counter::Segment &s : c->segments)
+            if (s.d) (void)hipFree(s.d);
+        for (const tbk_counter::ClassDb &d : c->db) {
+            if (d.d_keys) (void)hipFree(d.d_keys);
+            if (d.d_counts) (void)hipFree(d.d_counts);
+        }
     }
     delete c;
 }
 
-static int counter_run(tbk_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t total) {
-    const size_t need_sep = (size_t)total + n_reads + 64;
-    if (need_sep > c->cap_sep) {
-        if (c->d_sep) CHIP(hipFree(c->d_sep));
-        c->d_sep = nullptr; c->cap_sep = 0;
-        CHIP(hipMalloc((void **)&c->d_sep, need_sep + need_sep / 8));
-        c->cap_sep = need_sep + need_sep / 8;
-    }
-    CHIP(tbk_launch_separate(d_bases, d_offsets, n_reads, c->d_sep, nullptr));
+// Count a stream of sep_total positions, the separated ASCII stream d_sep (cls < 0) or, in pass mode, the
+// retained words of one batch for class cls.
+static int count_stream(tbk_counter *c, const void *d_stream, uint64_t sep_total, int cls) {
     // The stream is counted in pieces of a quarter of the table's slots (at least 64 M window
     // starts).  Every window of a piece could be a k-mer never seen before, so before a piece that
     // could fill the table the table is rebuilt twice as large - a piece can then never run out of
     // room half way, and the table grows once its load passes 0.6.
-    const uint64_t sep_total = total + n_reads, passes = tbk_probe_passes(sep_total);
+    const uint64_t passes = tbk_probe_passes(sep_total);
     for (uint64_t p0 = 0; p0 < passes;) {
         uint64_t slots = (uint64_t)c->n_buckets * TBK_SLOTS_PER_BUCKET;
         // (at most 2^30 window starts however large the table: a piece on top of counters just set back to 2^31 must stay below 2^32 - see below)
@@ -202,7 +257,11 @@ static int counter_run(tbk_counter *c, const uint8_t *d_bases, const uint64_t *d
         c->since_clamp += windows;
         if (!c->ev0) { CHIP(hipEventCreate(&c->ev0)); CHIP(hipEventCreate(&c->ev1)); }
         CHIP(hipEventRecord(c->ev0, nullptr));
-        CHIP(tbk_launch_count(c->d_sep, sep_total, p0, np, c->k, c->d_lines, c->n_buckets, c->mz, c->d_failed, c->d_used, nullptr));
+        if (cls < 0)
+            CHIP(tbk_launch_count((const uint8_t *)d_stream, sep_total, p0, np, c->k, c->d_lines, c->n_buckets, c->mz, c->d_failed, c->d_used, nullptr));
+        else
+            CHIP(tbk_launch_count_class((const uint64_t *)d_stream, sep_total / 16, p0, np, c->k, c->d_lines, c->n_buckets, c->mz, c->d_failed, c->d_used,
+                                        (uint32_t)c->passes, (uint32_t)cls, nullptr));
         CHIP(hipEventRecord(c->ev1, nullptr));
         int failed = 0;
         unsigned long long used = 0;
@@ -217,6 +276,126 @@ static int counter_run(tbk_counter *c, const uint8_t *d_bases, const uint64_t *d
         if (failed) return cfail(TBK_ERR_NOMEM, "counting table is full (%llu slots, %llu taken)", (unsigned long long)slots, used);
         p0 += np;
     }
+    return TBK_OK;
+}
+
+// Pack the separated stream of a batch (c->d_sep) into the store.  The store is a list of segments, each at least
+// half as large as everything kept before it, so its growth never copies and costs O(log) allocations; a batch
+// lies in one segment, on a word boundary, and is replayed from there.
+static int store_append(tbk_counter *c, uint64_t sep_total, uint64_t **d_words, uint64_t *n_words) {
+    const uint64_t words = (sep_total + 15) / 16;
+    if (c->store_limit && (c->store_words + words) * 8 > c->store_limit)
+        return cfail(TBK_ERR_NOMEM, "the retained store would pass its limit of %llu bytes: %llu bases are retained in %llu bytes, the next batch needs %llu more",
+                     (unsigned long long)c->store_limit, (unsigned long long)c->bases_added, (unsigned long long)(c->store_words * 8),
+                     (unsigned long long)(words * 8));
+    if (c->segments.empty() || c->segments.back().cap - c->segments.back().used < words) {
+        uint64_t cap = std::max<uint64_t>(words, std::max<uint64_t>((uint64_t)1 << 17, c->store_words / 2));
+        if (c->store_limit) cap = std::max<uint64_t>(words, std::min<uint64_t>(cap, c->store_limit / 8 - c->store_words));
+        tbk_counter::Segment seg;
+        const hipError_t e = hipMalloc((void **)&seg.d, cap * 8);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "the retained store cannot grow by %llu bytes (%s): %llu bases are retained in %llu bytes",
+                         (unsigned long long)(cap * 8), hipGetErrorString(e), (unsigned long long)c->bases_added, (unsigned long long)c->store_bytes);
+        }
+        seg.cap = cap;
+        c->segments.push_back(seg);
+        c->store_bytes += cap * 8;
+    }
+    tbk_counter::Segment &seg = c->segments.back();
+    CHIP(tbk_launch_retain(c->d_sep, sep_total, seg.d + seg.used, words, nullptr));
+    c->pieces.push_back({(uint32_t)(c->segments.size() - 1), seg.used, words});
+    *d_words = seg.d + seg.used;
+    *n_words = words;
+    seg.used += words;
+    c->store_words += words;
+    return TBK_OK;
+}
+
+// The class just counted becomes its database; the table is empty afterwards.
+static int distil_class(tbk_counter *c) {
+    CHIP(tbk_launch_count_histogram(c->d_lines, c->n_buckets, c->mz, c->d_hist, nullptr));  // adds this class's rows to the running histogram
+    unsigned long long h[256];
+    CHIP(hipMemcpy(h, c->d_hist, sizeof h, hipMemcpyDeviceToHost));
+    uint64_t keep = 0;
+    for (int i = 2; i < 256; i++) keep += h[i] - c->hist[i];
+    c->distinct_done += h[0] - c->hist[0];
+    for (int i = 0; i < 256; i++) c->hist[i] = h[i];
+    tbk_counter::ClassDb d;
+    c->db.push_back(d);  // (owned by the counter from here on: freed with it whatever happens below)
+    tbk_counter::ClassDb &db = c->db.back();
+    if (keep) {
+        CHIP(hipMalloc((void **)&db.d_keys, keep * sizeof(uint64_t)));
+        CHIP(hipMalloc((void **)&db.d_counts, keep));
+    }
+    unsigned long long got = 0;
+    CHIP(hipMemset(c->d_used, 0, sizeof got));  // [0] doubles as the append cursor: the class's slot count has been read
+    CHIP(tbk_launch_count_distil(c->d_lines, c->n_buckets, c->mz, db.d_keys, db.d_counts, keep, c->d_used, nullptr));
+    CHIP(hipMemcpy(&got, c->d_used, sizeof got, hipMemcpyDeviceToHost));
+    CHIP(hipMemset(c->d_used, 0, sizeof got));
+    if (got != keep) return cfail(TBK_ERR_HIP, "distilling a class: %llu k-mers seen twice in the histogram, %llu in the table", (unsigned long long)keep, got);
+    db.n = keep;
+    c->database_bytes += keep * 9;
+    c->used = 0;
+    c->since_clamp = 0;
+    return TBK_OK;
+}
+
+static int counter_finish(tbk_counter *c) {
+    if (c->finished) return TBK_OK;
+    if (c->broken) return cfail(TBK_ERR_INVALID, "the counter failed while it was being finished");
+    if (c->passes == 1) { c->finished = true; return TBK_OK; }
+    int rc = counter_device(c);
+    if (rc) return rc;
+    c->broken = true;  // until every class is through
+    rc = distil_class(c);
+    for (int cls = 1; !rc && cls < c->passes; cls++) {
+        for (size_t i = 0; !rc && i < c->pieces.size(); i++) {
+            const tbk_counter::Piece &pc = c->pieces[i];
+            rc = count_stream(c, c->segments[pc.segment].d + pc.first, pc.words * 16, cls);
+        }
+        if (!rc) rc = distil_class(c);
+    }
+    if (rc) return rc;
+    // only the databases and the histogram remain
+    for (tbk_counter::Segment &sg : c->segments) (void)hipFree(sg.d);
+    c->segments.clear(); c->pieces.clear();
+    c->store_bytes = 0; c->store_words = 0;
+    for (void **p : {(void **)&c->d_lines, (void **)&c->d_raw, (void **)&c->d_sep, (void **)&c->d_off}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    c->n_buckets = 0; c->cap_raw = 0; c->cap_sep = 0; c->cap_reads = 0;
+    c->broken = false;
+    c->finished = true;
+    return TBK_OK;
+}
+
+extern "C" int tbk_counter_finish(tbk_counter *c) {
+    if (!c) return cfail(TBK_ERR_INVALID, "counter is NULL");
+    return counter_finish(c);
+}
+
+static int counter_run(tbk_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t total) {
+    const size_t need_sep = (size_t)total + n_reads + 64;
+    if (need_sep > c->cap_sep) {
+        if (c->d_sep) CHIP(hipFree(c->d_sep));
+        c->d_sep = nullptr; c->cap_sep = 0;
+        CHIP(hipMalloc((void **)&c->d_sep, need_sep + need_sep / 8));
+        c->cap_sep = need_sep + need_sep / 8;
+    }
+    CHIP(tbk_launch_separate(d_bases, d_offsets, n_reads, c->d_sep, nullptr));
+    const uint64_t sep_total = total + n_reads;
+    int rc;
+    if (c->passes > 1) {
+        // pass mode: keep the batch, and count class 0 from the kept words while they are at hand
+        uint64_t *d_words = nullptr, n_words = 0;
+        rc = store_append(c, sep_total, &d_words, &n_words);
+        if (!rc) rc = count_stream(c, d_words, n_words * 16, 0);
+    } else {
+        rc = count_stream(c, c->d_sep, sep_total, -1);
+    }
+    if (rc) return rc;
     c->bases_added += total;
     c->reads_added += n_reads;
     return TBK_OK;
@@ -226,6 +405,7 @@ extern "C" int tbk_check_offsets_(const uint64_t *offsets, uint64_t n_reads);
 
 extern "C" int tbk_counter_add_batch(tbk_counter *c, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads) {
     if (!c || (n_reads && (!bases || !offsets))) return cfail(TBK_ERR_INVALID, "NULL argument");
+    if (c->finished || c->broken) return cfail(TBK_ERR_INVALID, "the counter is finished: no more reads can be added");
     if (!n_reads) return TBK_OK;
     int rc = tbk_check_offsets_(offsets, n_reads);  // same rule as tbk_stream_submit
     if (rc) return rc;
@@ -251,6 +431,7 @@ extern "C" int tbk_counter_add_batch(tbk_counter *c, const uint8_t *bases, const
 
 extern "C" int tbk_counter_add_device(tbk_counter *c, const void *d_bases, const void *d_offsets, uint64_t n_reads, uint64_t total_bases) {
     if (!c || (n_reads && (!d_bases || !d_offsets))) return cfail(TBK_ERR_INVALID, "NULL argument");
+    if (c->finished || c->broken) return cfail(TBK_ERR_INVALID, "the counter is finished: no more reads can be added");
     if (!n_reads) return TBK_OK;
     int rc = counter_device(c);
     if (rc) return rc;
@@ -282,6 +463,12 @@ extern "C" int tbk_counter_histogram(tbk_counter *c, uint64_t hist[256]) {
     if (!c || !hist) return cfail(TBK_ERR_INVALID, "NULL argument");
     int rc = counter_device(c);
     if (rc) return rc;
+    if (c->passes > 1) {
+        rc = counter_finish(c);
+        if (rc) return rc;
+        for (int i = 0; i < 256; i++) hist[i] = c->hist[i];
+        return TBK_OK;
+    }
     unsigned long long *d_hist = nullptr;
     CHIP(hipMalloc((void **)&d_hist, 256 * sizeof(unsigned long long)));
     hipError_t e = hipMemset(d_hist, 0, 256 * sizeof(unsigned long long));
@@ -296,6 +483,12 @@ extern "C" int tbk_counter_histogram(tbk_counter *c, uint64_t hist[256]) {
 
 extern "C" int tbk_counter_distinct(const tbk_counter *c, uint64_t *distinct) {
     if (!c || !distinct) return cfail(TBK_ERR_INVALID, "NULL argument");
+    if (c->passes > 1) {  // the sum over the classes: known once all have been counted
+        const int rc = counter_finish(const_cast<tbk_counter *>(c));
+        if (rc) return rc;
+        *distinct = c->distinct_done;
+        return TBK_OK;
+    }
     *distinct = c->used;
     return TBK_OK;
 }
@@ -315,6 +508,23 @@ extern "C" int tbk_counter_params(const tbk_counter *c, int *w, int *m, int *o, 
     if (m) *m = c->mz.m;
     if (o) *o = c->mz.o;
     if (t) *t = c->mz.t;
+    return TBK_OK;
+}
+
+extern "C" int tbk_counter_stats_ex(const tbk_counter *c, tbk_counter_info *info) {
+    if (!c || !info) return cfail(TBK_ERR_INVALID, "NULL argument");
+    if (info->size < 8 || info->size > sizeof(tbk_counter_info)) return cfail(TBK_ERR_INVALID, "tbk_counter_info.size = %u (this library knows %zu bytes)", info->size, sizeof(tbk_counter_info));
+    tbk_counter_info v;
+    memset(&v, 0, sizeof v);
+    v.size = info->size;
+    v.passes = c->passes;
+    v.finished = c->finished ? 1 : 0;
+    v.store_bytes = c->store_bytes;
+    v.store_used_bytes = c->store_words * 8;
+    v.peak_table_bytes = c->peak_table_bytes;
+    v.database_bytes = c->database_bytes;
+    v.distinct = c->distinct_done + c->used;  // classes distilled so far + the class in the table
+    memcpy(info, &v, info->size);
     return TBK_OK;
 }
 
@@ -361,9 +571,17 @@ extern "C" int tbk_counter_unique(tbk_counter *a, tbk_counter *b, uint32_t min_c
     if (!a || !b || !out_path || !n_written) return cfail(TBK_ERR_INVALID, "NULL argument");
     if (a->k != b->k) return cfail(TBK_ERR_INVALID, "the counters have different k (%d and %d)", a->k, b->k);
     if (a->device != b->device) return cfail(TBK_ERR_INVALID, "the counters live on different devices");
+    if (a->passes != b->passes)
+        return cfail(TBK_ERR_INVALID, "the counters count in different numbers of passes (%d and %d): their classes do not match", a->passes, b->passes);
     *n_written = 0;
     int rc = counter_device(a);
     if (rc) return rc;
+    const bool by_class = a->passes > 1;
+    if (by_class) {
+        rc = counter_finish(a);
+        if (!rc) rc = counter_finish(b);
+        if (rc) return rc;
+    }
     // upper bound of what can come out: k-mers of A with a counter in range
     uint64_t hist[256];
     rc = tbk_counter_histogram(a, hist);
@@ -379,9 +597,24 @@ extern "C" int tbk_counter_unique(tbk_counter *a, tbk_counter *b, uint32_t min_c
         if (e == hipSuccess) e = hipMalloc((void **)&d_sorted, cap * sizeof(uint64_t));
         if (e == hipSuccess) e = hipMalloc((void **)&d_n, sizeof got);
         if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof got);
-        if (e == hipSuccess)
+        if (e == hipSuccess && !by_class)
             e = tbk_launch_count_unique(a->d_lines, a->n_buckets, a->mz, b->d_lines, b->n_buckets, b->mz, a->k, min_count, max_count,
                                         d_out, cap, d_n, nullptr);
+        if (e == hipSuccess && by_class) {
+            // class by class: B's keys of the class sorted (keys alone), A's looked up among them
+            uint64_t most = 0, *d_bs = nullptr;
+            for (const tbk_counter::ClassDb &d : b->db) most = std::max(most, d.n);
+            if (most) e = hipMalloc((void **)&d_bs, most * sizeof(uint64_t));
+            for (size_t p = 0; e == hipSuccess && p < a->db.size(); p++) {
+                const tbk_counter::ClassDb &da = a->db[p], &db = b->db[p];
+                if (!da.n) continue;
+                if (db.n) e = tbk_launch_sort_u64(db.d_keys, d_bs, db.n, 2 * a->k, nullptr);
+                if (e == hipSuccess)
+                    e = tbk_launch_db_unique(da.d_keys, da.d_counts, da.n, d_bs, db.n, a->k, min_count, max_count, d_out, cap, d_n, nullptr);
+            }
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+            if (d_bs) (void)hipFree(d_bs);
+        }
         if (e == hipSuccess) e = hipMemcpy(&got, d_n, sizeof got, hipMemcpyDeviceToHost);
         n = std::min<uint64_t>(got, cap);
         if (e == hipSuccess && n) e = tbk_launch_sort_u64(d_out, d_sorted, n, 2 * a->k, nullptr);

@@ -35,6 +35,21 @@ tbk_separate_kernel(const uint8_t *__restrict__ bases, const uint64_t *__restric
     }
 }
 
+// Pass mode keeps every batch on the device in the form the counting kernel stages: one 64-bit word per 16
+// bases of the separated stream, 32 bits of 2-bit codes and the 16-bit not-ACGT mask above them (load_chunk's
+// value; 0.5 bytes per base).  A batch takes whole words: the positions of its last word past its end carry the
+// bad bit (load_chunk reads them as 0), so no window spans two batches.
+__global__ void __launch_bounds__(256)
+tbk_retain_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_t *__restrict__ store, uint64_t n_chunks) {
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks; c += (uint64_t)gridDim.x * blockDim.x)
+        store[c] = load_chunk(sep, c * 16, total);
+}
+
+// The class a pass-mode launch counts: windows whose canonical k-mer has tbk_class_of(key, n_classes) == cls.
+struct TbkClassSel {
+    uint32_t n_classes, cls;
+};
+
 // bucket b = one 128-byte line: 8 keys (TBK_EMPTY = free), then their 8 32-bit counters, then 32
 // spare bytes - keys and counters of a bucket arrive with one HBM line and the increments of a run
 // of windows land in a line that already sits in L2
@@ -76,10 +91,16 @@ __device__ __forceinline__ bool count_from(const TbkCountView &t, uint64_t key, 
 // The copy may be stale - other lanes insert meanwhile - but only in one direction: a slot seen
 // occupied never changes, and a slot seen free is claimed with a compare-and-swap that returns what
 // is really there.
-template <int W, bool M64>
+//
+// Pass mode (tbk_count.cpp) instantiates the kernel with a TbkClassSel as one more argument: `bases` is then the
+// retained store of a batch (tbk_retain_kernel; `total` = 16 x its words), staged with plain 8-byte loads, and a
+// clean window counts only if its k-mer belongs to the class.  The plain instantiations have no such argument.
+template <int W, bool M64, typename... Sel>
 __global__ void __launch_bounds__(64)
 tbk_count_kernel(const uint8_t *__restrict__ bases, uint64_t total, uint64_t first_pass, uint64_t n_passes, int k, TbkCountView t,
-                 int *__restrict__ failed, unsigned long long *__restrict__ used) {
+                 int *__restrict__ failed, unsigned long long *__restrict__ used, Sel... sel) {
+    static_assert(sizeof...(Sel) == 0 || (sizeof...(Sel) == 1 && (std::is_same<Sel, TbkClassSel>::value && ...)), "at most one class selector");
+    constexpr bool PACKED = sizeof...(Sel) == 1;
     __shared__ uint64_t stage[TBK_CHUNKS + 2];
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1ull);
@@ -98,9 +119,18 @@ tbk_count_kernel(const uint8_t *__restrict__ bases, uint64_t total, uint64_t fir
     for (uint64_t pass = first_pass + blockIdx.x; pass < first_pass + n_passes; pass += gridDim.x) {
         const uint64_t P0 = pass * TBK_PASS;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        stage[lane] = load_chunk(bases, P0 + (uint64_t)lane * 16, total);
-        stage[64 + lane] = load_chunk(bases, P0 + (uint64_t)(64 + lane) * 16, total);
-        if (lane < 2) stage[128 + lane] = load_chunk(bases, P0 + (uint64_t)(128 + lane) * 16, total);
+        if constexpr (PACKED) {
+            const uint64_t *store = reinterpret_cast<const uint64_t *>(bases);
+            const uint64_t c0 = P0 / 16, n_chunks = total / 16;  // words past the store read as sixteen not-ACGT bases
+            auto word = [&](uint64_t c) -> uint64_t { return c < n_chunks ? store[c] : 0xFFFFull << 32; };
+            stage[lane] = word(c0 + lane);
+            stage[64 + lane] = word(c0 + 64 + lane);
+            if (lane < 2) stage[128 + lane] = word(c0 + 128 + lane);
+        } else {
+            stage[lane] = load_chunk(bases, P0 + (uint64_t)lane * 16, total);
+            stage[64 + lane] = load_chunk(bases, P0 + (uint64_t)(64 + lane) * 16, total);
+            if (lane < 2) stage[128 + lane] = load_chunk(bases, P0 + (uint64_t)(128 + lane) * 16, total);
+        }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         const uint64_t e0 = stage[2 * lane], e1 = stage[2 * lane + 1], e2 = stage[2 * lane + 2], e3 = stage[2 * lane + 3];
         uint32_t s0 = (uint32_t)e0, s1 = (uint32_t)e1, s2 = (uint32_t)e2, s3 = (uint32_t)e3;
@@ -149,7 +179,11 @@ tbk_count_kernel(const uint8_t *__restrict__ bases, uint64_t total, uint64_t fir
             const uint64_t fwd = ((uint64_t)s0 | ((uint64_t)s1 << 32)) & kmask;
             const uint64_t rc = ((uint64_t)t2 | ((uint64_t)t3 << 32)) & kmask;
             const uint64_t key = fwd < rc ? fwd : rc;
-            const bool ok = (bad_lo & badk) == 0 && P0 + (uint64_t)lane * TBK_WPL + (uint64_t)j + (uint64_t)k <= total;
+            bool ok = (bad_lo & badk) == 0 && P0 + (uint64_t)lane * TBK_WPL + (uint64_t)j + (uint64_t)k <= total;
+            if constexpr (PACKED) {
+                const TbkClassSel cs = (sel, ...);
+                ok = ok && tbk_class_of(key, cs.n_classes) == cs.cls;
+            }
             uint32_t hsel;
             if (W > 0) {
 #pragma unroll
@@ -316,6 +350,93 @@ tbk_count_unique_kernel(TbkCountView a, TbkCountView b, int k, uint32_t ci, uint
     }
 }
 
+// ---- pass mode: the database a class leaves behind ---------------------------------------------------
+// After a class has been counted, its table is distilled: every k-mer seen at least twice (kmc's -ci2) is
+// appended to the class's database as (key, counter capped at 255) - 9 bytes - and every slot goes back to
+// free, ready for the next class.  The k-mers seen once are dropped here; the histogram (taken just before,
+// tbk_count_histogram_kernel) has counted them.  Appends are per wave, as in tbk_count_unique_kernel.
+__global__ void __launch_bounds__(256)
+tbk_count_distil_kernel(TbkCountView t, uint64_t *__restrict__ db_keys, uint8_t *__restrict__ db_counts, uint64_t capacity,
+                        unsigned long long *__restrict__ n_out) {
+    const uint64_t n_slots = (uint64_t)t.n_buckets * TBK_SLOTS_PER_BUCKET;
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; i0 < n_slots; i0 += step) {
+        const uint64_t i = i0 + lane;
+        bool emit = false;
+        uint64_t key = 0;
+        uint32_t raw = 0;
+        if (i < n_slots) {
+            unsigned long long *kp = &t.keys((uint32_t)(i >> 3))[i & 7];
+            key = *kp;
+            if (key != TBK_EMPTY) {
+                uint32_t *cp = &t.counts((uint32_t)(i >> 3))[i & 7];
+                raw = *cp;
+                emit = raw >= 2u;
+                *kp = TBK_EMPTY;
+                *cp = 0;
+            }
+        }
+        const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
+        if (mask) {
+            unsigned long long base = 0;
+            const int leader = __builtin_ctzll(mask);
+            if ((int)lane == leader) base = atomicAdd(n_out, (unsigned long long)__popcll(mask));
+            base = __shfl(base, leader);
+            if (emit) {
+                const uint64_t at = base + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+                if (at < capacity) {
+                    db_keys[at] = key;
+                    db_counts[at] = (uint8_t)(raw < 255u ? raw : 255u);
+                }
+            }
+        }
+    }
+}
+
+// kmers_subtract + kmc_dump on the databases of ONE class (a k-mer's class depends on the k-mer alone, so the
+// other parent holds it in the same class or not at all): the keys of A whose counter lies in [ci, cx] and that
+// are not among B's, which arrive sorted; appended as lexicographic ranks like tbk_count_unique_kernel's.
+__global__ void __launch_bounds__(256)
+tbk_db_unique_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restrict__ a_counts, uint64_t n_a,
+                     const uint64_t *__restrict__ b_sorted, uint64_t n_b, int k, uint32_t ci, uint32_t cx,
+                     uint64_t *__restrict__ out, uint64_t capacity, unsigned long long *__restrict__ n_out) {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; i0 < n_a; i0 += step) {
+        const uint64_t i = i0 + lane;
+        bool emit = false;
+        uint64_t key = 0;
+        if (i < n_a) {
+            key = a_keys[i];
+            const uint32_t c = a_counts[i];
+            emit = c >= 2u && c >= ci && c <= cx;
+            if (emit) {
+                uint64_t lo = 0, hi = n_b;  // first element >= key
+                while (lo < hi) {
+                    const uint64_t mid = lo + (hi - lo) / 2;
+                    if (b_sorted[mid] < key) lo = mid + 1; else hi = mid;
+                }
+                emit = !(lo < n_b && b_sorted[lo] == key);
+            }
+        }
+        const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
+        if (mask) {
+            unsigned long long base = 0;
+            const int leader = __builtin_ctzll(mask);
+            if ((int)lane == leader) base = atomicAdd(n_out, (unsigned long long)__popcll(mask));
+            base = __shfl(base, leader);
+            if (emit) {
+                const uint64_t at = base + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+                if (at < capacity) {
+                    const uint64_t lex = ((uint64_t)rev_pairs((uint32_t)key) << 32) | (uint64_t)rev_pairs((uint32_t)(key >> 32));
+                    out[at] = lex >> (64 - 2 * k);
+                }
+            }
+        }
+    }
+}
+
 // =======================================================================================
 // launchers (called from tbk_count.cpp)
 // =======================================================================================
@@ -367,5 +488,54 @@ extern "C" hipError_t tbk_launch_count_unique(uint64_t *a_lines, uint32_t a_buck
                                               unsigned long long *d_n, hipStream_t stream) {
     hipLaunchKernelGGL(tbk_count_unique_kernel, dim3(8192), dim3(256), 0, stream, TbkCountView{a_lines, a_buckets, a_mz},
                        TbkCountView{b_lines, b_buckets, b_mz}, k, ci, cx, d_out, capacity, d_n);
+    return hipGetLastError();
+}
+
+// ---- pass mode ------------------------------------------------------------------------------------------
+extern "C" hipError_t tbk_launch_retain(const uint8_t *d_sep, uint64_t total, uint64_t *d_store, uint64_t n_chunks, hipStream_t stream) {
+    if (!n_chunks) return hipSuccess;
+    const uint64_t blocks = (n_chunks + 255) / 256;
+    hipLaunchKernelGGL(tbk_retain_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, d_sep, total, d_store, n_chunks);
+    return hipGetLastError();
+}
+
+// tbk_launch_count for one class of a retained batch of n_chunks words
+extern "C" hipError_t tbk_launch_count_class(const uint64_t *d_store, uint64_t n_chunks, uint64_t first_pass, uint64_t n_passes, int k,
+                                             uint64_t *d_lines, uint32_t n_buckets, TbkMz mz, int *d_failed, unsigned long long *d_used,
+                                             uint32_t n_classes, uint32_t cls, hipStream_t stream) {
+    const uint64_t total = n_chunks * 16;
+    if (total < (uint64_t)k || !n_passes) return hipSuccess;
+    if (!n_classes || cls >= n_classes) return hipErrorInvalidValue;
+    const uint64_t blocks = n_passes < (1u << 20) ? n_passes : (1u << 20);
+    const TbkCountView view{d_lines, n_buckets, mz};
+    const TbkClassSel sel{n_classes, cls};
+    const uint8_t *d_bases = reinterpret_cast<const uint8_t *>(d_store);
+    const dim3 grid((unsigned)blocks), block(64);
+    const bool m64 = mz.m > 16;
+#define TBK_COUNT_LAUNCH(N) case N: if (m64) hipLaunchKernelGGL((tbk_count_kernel<N, true, TbkClassSel>), grid, block, 0, stream, d_bases, total, first_pass, n_passes, k, view, d_failed, d_used, sel); \
+                                    else hipLaunchKernelGGL((tbk_count_kernel<N, false, TbkClassSel>), grid, block, 0, stream, d_bases, total, first_pass, n_passes, k, view, d_failed, d_used, sel); break;
+    switch (mz.t > 0 ? -1 : mz.w) {
+        case 0: hipLaunchKernelGGL((tbk_count_kernel<0, false, TbkClassSel>), grid, block, 0, stream, d_bases, total, first_pass, n_passes, k, view, d_failed, d_used, sel); break;
+        TBK_COUNT_LAUNCH(1) TBK_COUNT_LAUNCH(2) TBK_COUNT_LAUNCH(3) TBK_COUNT_LAUNCH(4)
+        TBK_COUNT_LAUNCH(5) TBK_COUNT_LAUNCH(6) TBK_COUNT_LAUNCH(7) TBK_COUNT_LAUNCH(8)
+        default: return hipErrorInvalidValue;
+    }
+#undef TBK_COUNT_LAUNCH
+    return hipGetLastError();
+}
+
+extern "C" hipError_t tbk_launch_count_distil(uint64_t *d_lines, uint32_t n_buckets, TbkMz mz, uint64_t *d_keys, uint8_t *d_counts,
+                                              uint64_t capacity, unsigned long long *d_n, hipStream_t stream) {
+    hipLaunchKernelGGL(tbk_count_distil_kernel, dim3(4096), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz}, d_keys, d_counts, capacity, d_n);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t tbk_launch_db_unique(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *b_sorted, uint64_t n_b,
+                                           int k, uint32_t ci, uint32_t cx, uint64_t *d_out, uint64_t capacity, unsigned long long *d_n,
+                                           hipStream_t stream) {
+    if (!n_a) return hipSuccess;
+    const uint64_t blocks = (n_a + 255) / 256;
+    hipLaunchKernelGGL(tbk_db_unique_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, a_keys, a_counts, n_a, b_sorted, n_b,
+                       k, ci, cx, d_out, capacity, d_n);
     return hipGetLastError();
 }

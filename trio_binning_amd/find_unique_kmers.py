@@ -51,6 +51,12 @@ def parse_args(argv=None):
              "from the input sizes, within the free HBM",
     )
     parser.add_argument(
+        "--passes", type=int, default=0,
+        help="count each library in this many passes over its reads, which are kept on the GPU in packed form: a "
+             "table then holds 1/N of the distinct k-mers at a time (for libraries whose k-mers, sequencing errors "
+             "included, outgrow the HBM); 1: one pass, nothing kept; default 0: the fewest passes that fit (choose_passes)",
+    )
+    parser.add_argument(
         "read_files", nargs=2,
         help="one comma-separated list of file paths for both libraries being compared. Files can "
              "be in fasta or fastq format, and uncompressed or gzipped.",
@@ -90,14 +96,14 @@ def analyze_histogram(rows: Sequence[Tuple[int, int]], histogram_path: str = "")
     return min_coverage, max_coverage
 
 
-def count_library(paths: List[str], k: int, capacity: int) -> "kmers.KmerCounter":
+def count_library(paths: List[str], k: int, capacity: int, passes: int = 1) -> "kmers.KmerCounter":
     """Count the canonical k-mers of all files of one library (what `kmc -k<k> @files` does).
     The files are read side by side, one reader thread each (a gzip stream inflates on one core, but
     a library usually comes as many files); this thread feeds their batches to the GPU."""
     import queue
     import threading
 
-    counter = kmers.KmerCounter(k, capacity)
+    counter = kmers.KmerCounter(k, capacity, passes=passes)
     n_readers = max(1, min(len(paths), kmers.host_threads()))
     todo: "queue.Queue" = queue.Queue()
     for p in paths:
@@ -161,14 +167,69 @@ def count_library(paths: List[str], k: int, capacity: int) -> "kmers.KmerCounter
     return counter
 
 
-def estimate_capacity(paths: List[str]) -> int:
-    """Distinct k-mers cannot outnumber the bases: uncompressed FASTQ spends two bytes per base,
-    gzip compresses it about fourfold.  Bounded by what two tables (16 bytes per slot at load 0.6)
-    may take of the free HBM."""
+def estimate_bases(paths: List[str]) -> int:
+    """Bases of a library from its file sizes: uncompressed FASTQ spends two bytes per base, gzip
+    compresses it about fourfold."""
     bases = 0
     for p in paths:
         size = os.path.getsize(p)
         bases += size * 2 if p.endswith(".gz") else size // 2 + 1
+    return bases
+
+
+MAX_PASSES = 1024          # TBK_COUNTER_MAX_PASSES
+PLAN_FRACTION = (4, 5)     # choose_passes plans with 4/5 of the free HBM
+TABLE_BYTES = (80, 3)      # per distinct k-mer of a table: 16 bytes per slot at load 0.6
+STORE_BYTES = (1, 2)       # per base kept: one 64-bit word per 16 bases
+DATABASE_SHARE = 8         # 1 / this of a parent's distinct k-mers is planned to be seen twice or more ...
+DATABASE_BYTES = 9         # ... and costs a key and a one-byte counter
+
+
+def choose_passes(capacity: int, bases_estimate: int, free_bytes: int) -> int:
+    """The fewest passes in which one parent of `capacity` distinct k-mers and `bases_estimate` bases can be
+    counted within `free_bytes` of HBM.  A pure function of its arguments; all arithmetic in integers.
+
+    The budget is 4/5 of the free bytes (the rest is left to the batch staging, the sort of the dump and
+    the allocator).  With table(P) = ceil(capacity / P) * 80 // 3 bytes (16 bytes per slot at load 0.6):
+
+    * P = 1 (one pass, nothing kept: both parents' tables stay resident until the dumps are written, and a
+      table that doubles is held beside its twice as large successor) fits if 4 * table(1) <= budget;
+    * P > 1 fits if  store + 3 * table(P) + databases <= budget, where store = ceil(bases_estimate / 2) (the
+      reads of the parent being counted, 0.5 bytes per base), 3 * table(P) is one class's table beside its
+      doubling twin, and databases = 2 * 9 * (capacity // 8) is what both parents leave behind: a ninth byte on
+      every key seen at least twice, planned as an eighth of the distinct k-mers (the others are the k-mers
+      seen once that -ci2 drops).
+
+    Returns the smallest such P; ValueError when the store and the databases alone pass the budget, or when
+    more than 1024 passes would be needed."""
+    if capacity < 1 or bases_estimate < 0 or free_bytes < 0:
+        raise ValueError("choose_passes: capacity must be positive, bases and free bytes not negative")
+    budget = free_bytes * PLAN_FRACTION[0] // PLAN_FRACTION[1]
+
+    def table(p: int) -> int:
+        return -(-capacity // p) * TABLE_BYTES[0] // TABLE_BYTES[1]
+
+    if 4 * table(1) <= budget:
+        return 1
+    store = -(-bases_estimate * STORE_BYTES[0] // STORE_BYTES[1])
+    fixed = store + 2 * DATABASE_BYTES * (capacity // DATABASE_SHARE)
+    if store > budget:
+        raise ValueError(
+            "the reads alone ({} bases, {} bytes packed) do not fit the {} bytes planned of {} free on the GPU: "
+            "keeping reads on the host is not supported".format(bases_estimate, store, budget, free_bytes))
+    for p in range(2, MAX_PASSES + 1):
+        if fixed + 3 * table(p) <= budget:
+            return p
+    raise ValueError(
+        "{} distinct k-mers of {} bases cannot be counted in up to {} passes within the {} bytes planned of {} free "
+        "on the GPU (packed reads and databases: {} bytes); give --capacity (the distinct k-mers expected) or --passes".format(
+            capacity, bases_estimate, MAX_PASSES, budget, free_bytes, fixed))
+
+
+def estimate_capacity(paths: List[str]) -> int:
+    """Distinct k-mers cannot outnumber the bases (estimate_bases).  Bounded by what two tables
+    (16 bytes per slot at load 0.6) may take of the free HBM."""
+    bases = estimate_bases(paths)
     free, _total = kmers.device_mem_info()
     fit = int(0.35 * free / 16 * 0.6)
     return max(1 << 16, min(bases, fit))
@@ -188,6 +249,16 @@ def main(argv=None):
     args = parse_args(argv)
     k = args.kmer_size
     libraries = []  # (counter, min_count, max_count)
+    if args.passes < 0 or args.passes > MAX_PASSES:
+        raise ValueError("--passes must be between 0 and {}".format(MAX_PASSES))
+    passes = args.passes
+    if not passes:
+        # both parents are counted in the same number of passes (their classes must match): the larger need decides
+        passes, free = 1, kmers.device_mem_info()[0]
+        for files_string in args.read_files:
+            paths = [p for p in files_string.split(",") if os.path.isfile(p)]  # (a missing file is reported below, in its turn)
+            bases = estimate_bases(paths)
+            passes = max(passes, choose_passes(args.capacity or max(1 << 16, bases), bases, free))
     try:
         for hap_id, files_string in zip(["A", "B"], args.read_files):
             print("\033[92mCounting k-mers in haplotype {}...\033[0m".format(hap_id), file=sys.stderr)
@@ -195,7 +266,9 @@ def main(argv=None):
             for p in paths:
                 if not os.path.isfile(p):
                     raise IOError("no such file: {}".format(p))
-            counter = count_library(paths, k, args.capacity or estimate_capacity(paths))
+            # (in passes the table holds one class and is not bound by what two resident tables may take)
+            capacity = args.capacity or (estimate_capacity(paths) if passes == 1 else max(1 << 16, estimate_bases(paths)))
+            counter = count_library(paths, k, capacity, passes)
             libraries.append([counter, None, None])
             print("\033[92mComputing and analyzing histogram...\033[0m", file=sys.stderr)
             histogram_path = os.path.join(args.scratch_dir, "haplotype{}.histogram".format(hap_id))

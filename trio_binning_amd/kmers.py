@@ -806,13 +806,25 @@ def device_mem_info(device: Optional[int] = None) -> Tuple[int, int]:
 class KmerCounter:
     """Counting table of canonical k-mers in HBM: the database `kmc` builds for the reference's
     find-unique-kmers step (find_unique_kmers.py:62-103), with the histogram, subtraction and dump
-    `kmc_tools` / `kmc_dump` provide (find_unique_kmers.py:123-129,186-194,218-225)."""
+    `kmc_tools` / `kmc_dump` provide (find_unique_kmers.py:123-129,186-194,218-225).
 
-    def __init__(self, k: int, capacity: int, device: Optional[int] = None):
+    ``passes`` > 1 counts a library whose distinct k-mers outgrow one table: the k-mers fall into that many
+    classes, the reads are kept on the device in packed form (0.5 bytes per base, at most ``store_limit`` bytes if
+    given), and one class at a time goes through a table sized for a class (``tbk_counter_create_opts`` in
+    include/tbk.h).  Results are those of one pass; ``unique`` needs both counters made with the same ``passes``."""
+
+    def __init__(self, k: int, capacity: int, device: Optional[int] = None, passes: int = 1, store_limit: int = 0):
         self._h = C.c_void_p()
         self.k = k
+        self.passes = passes
         self.device = default_device() if device is None else device
-        check(lib.tbk_counter_create(k, capacity, self.device, C.byref(self._h)))
+        if passes == 1 and not store_limit:
+            check(lib.tbk_counter_create(k, capacity, self.device, C.byref(self._h)))
+        else:
+            opts = _lib.CounterOptions()
+            lib.tbk_counter_options_init(C.byref(opts))
+            opts.passes, opts.store_limit_bytes = passes, store_limit
+            check(lib.tbk_counter_create_opts(k, capacity, C.byref(opts), self.device, C.byref(self._h)))
 
     def add_reads(self, reads: Sequence[str]) -> None:
         bases, offsets = pack_reads(reads)
@@ -837,6 +849,11 @@ class KmerCounter:
         check(lib.tbk_counter_kernel_timing(self._h, C.byref(n), C.byref(w), C.byref(ms), int(reset)))
         return n.value, w.value, ms.value
 
+    def finish(self) -> None:
+        """No more reads.  With ``passes`` > 1 this counts the remaining classes and frees the kept reads and the
+        table (``histogram`` and ``unique`` do it themselves when it has not been done)."""
+        check(lib.tbk_counter_finish(self._h))
+
     def histogram(self) -> np.ndarray:
         """hist[c], c = 1..255: distinct k-mers whose counter (capped at 255) is c; hist[0]: all."""
         hist = np.zeros(256, dtype=np.uint64)
@@ -846,12 +863,15 @@ class KmerCounter:
     def stats(self) -> dict:
         v = [C.c_uint64() for _ in range(4)]
         check(lib.tbk_counter_stats(self._h, *[C.byref(x) for x in v]))
-        d = C.c_uint64()
-        check(lib.tbk_counter_distinct(self._h, C.byref(d)))
+        info = _lib.CounterInfo(size=C.sizeof(_lib.CounterInfo))
+        check(lib.tbk_counter_stats_ex(self._h, C.byref(info)))  # (its `distinct` never finishes a counter working in passes)
         p = [C.c_int() for _ in range(4)]
         check(lib.tbk_counter_params(self._h, *[C.byref(x) for x in p]))
-        return dict(zip(("n_slots", "table_bytes", "bases_added", "reads_added", "distinct", "w", "m", "o", "t"),
-                        [x.value for x in v] + [d.value] + [x.value for x in p]))
+        st = dict(zip(("n_slots", "table_bytes", "bases_added", "reads_added", "distinct", "w", "m", "o", "t"),
+                      [x.value for x in v] + [info.distinct] + [x.value for x in p]))
+        for name in ("passes", "finished", "store_bytes", "store_used_bytes", "peak_table_bytes", "database_bytes"):
+            st[name] = int(getattr(info, name))
+        return st
 
     def unique(self, other: "KmerCounter", min_count: int, max_count: int, out_path: str) -> int:
         """Write the k-mers this library saw at least twice, with a counter in [min_count,
