@@ -694,6 +694,48 @@ int tbk_counter_params(const tbk_counter *c, int *w, int *m, int *o, int *t);
 int tbk_counter_unique(tbk_counter *a, tbk_counter *b, uint32_t min_count, uint32_t max_count, const char *out_path,
                        uint64_t *n_written);
 
+/* ---- count databases: what a counter leaves behind, kept -----------------------------------
+ * The reference's `kmc` leaves haplotypeA.* / haplotypeB.* under --outpath (find_unique_kmers.py:247) and its
+ * HistogramError tells the user to choose cut-offs by hand and dump again.  A tbk_kmerdb is that database: on
+ * one device, k, n keys - lexicographic ranks (base 0 in the top bits of the 2k, A < C < G < T), strictly
+ * ascending - n one-byte counters in 2..255, the whole 256-row histogram of the counter it came from (row 1 the
+ * k-mers seen once, row 0 all distinct k-mers, as tbk_counter_histogram defines them) and the reads and bases
+ * that were counted.  9 bytes of HBM per k-mer; twice that while tbk_counter_export orders one.  It outlives
+ * its counter.  Uniting two databases is not offered: a k-mer seen once in each half is in neither, so a union
+ * would not equal one count of both halves. */
+typedef struct tbk_kmerdb tbk_kmerdb;
+/* Finishes the counter (no more batches: tbk_counter_add_batch is TBK_ERR_INVALID afterwards; a counter in passes
+ * counts its remaining classes first) and makes its database.  A one-pass counter's table is only read:
+ * tbk_counter_histogram and tbk_counter_unique answer afterwards as before.  The database is the same whatever
+ * `passes` was.  TBK_ERR_NOMEM leaves the counter as it was (a one-pass counter not even finished). */
+int tbk_counter_export(tbk_counter *c, tbk_kmerdb **out);
+void tbk_kmerdb_destroy(tbk_kmerdb *db);
+/* The file (*.tbkdb, little-endian; INTEGRATION.md has the table): a 2096-byte header - magic "TBKKMDB1", header
+ * size, k, n, reads, bases, the histogram, CRC-32 of all that, a zero word - then n keys, then n counters: exactly
+ * 2096 + 9n bytes.  Written to path + ".tmp" in pieces and renamed, so an interrupted save leaves no file of the
+ * right name; no time stamp, no host name: equal databases give equal bytes. */
+int tbk_kmerdb_save(const tbk_kmerdb *db, const char *path);
+/* A file is checked before it is used.  On the host: magic, header size, k in 1..32, CRC, zero pad, file size
+ * against n, sum(hist[2..255]) == n, hist[0] >= hist[1] + n.  On the device, in one pass before anything
+ * searches the keys: strictly ascending keys, no key bit above 2k, no counter below 2, and the counters' tally
+ * equal to the header's rows 2..255.  A missing or unreadable file is TBK_ERR_IO, everything else TBK_ERR_FORMAT
+ * with the reason in tbk_last_error(); *out stays NULL and the device stays usable. */
+int tbk_kmerdb_load(const char *path, int device, tbk_kmerdb **out);
+/* The header alone, with the host-side checks above; needs no device.  Any out pointer may be NULL. */
+int tbk_kmerdb_file_info(const char *path, int *k, uint64_t *n, uint64_t hist[256], uint64_t *reads, uint64_t *bases);
+/* bytes: HBM the database holds (9n).  Any out pointer may be NULL. */
+int tbk_kmerdb_info(const tbk_kmerdb *db, int *k, uint64_t *n, int *device, uint64_t *bytes);
+int tbk_kmerdb_stats(const tbk_kmerdb *db, uint64_t *reads_added, uint64_t *bases_added);
+int tbk_kmerdb_histogram(const tbk_kmerdb *db, uint64_t hist[256]);
+/* Entries first .. first + count - 1 to host memory (either pointer may be NULL); a range outside the database
+ * is TBK_ERR_INVALID. */
+int tbk_kmerdb_read(const tbk_kmerdb *db, uint64_t first, uint64_t count, uint64_t *keys, uint8_t *counts);
+/* tbk_counter_unique between two databases: the k-mers of `a` whose counter lies in [max(2, min_count),
+ * min(255, max_count)] and that `b` does not hold, one per line in lexicographic order - the same file.  An
+ * empty range or an empty `a` gives an empty file and TBK_OK; a different k or device is TBK_ERR_INVALID. */
+int tbk_kmerdb_unique(const tbk_kmerdb *a, const tbk_kmerdb *b, uint32_t min_count, uint32_t max_count, const char *out_path,
+                      uint64_t *n_written);
+
 /* Host threads the library starts for its own host-side work (list parsing, gzip members,
  * scoring): hardware threads limited by the CPU affinity mask and the cgroup CPU quota, divided by the
  * number of ranks the launcher started on this node (LOCAL_WORLD_SIZE, or TBK_LOCAL_RANKS): one process per GPU

@@ -12,6 +12,11 @@ ap.add_argument("--read-len", type=int, default=150)
 ap.add_argument("--split", type=int, default=1, help="files per parent library")
 ap.add_argument("--gzip", action="store_true", help="gzip the parents' FASTQ files")
 ap.add_argument("--passes", type=int, default=0, help="find-unique-kmers --passes (0: it chooses)")
+ap.add_argument("--from-databases", action="store_true",
+                help="also: a --keep-databases run, a re-dump from the two *.tbkdb files at the first run's cut-offs, and the seconds "
+                     "of export, save, load and unique on their own; the legs alternate --repeat times")
+ap.add_argument("--tree", default="", help="with --from-databases: a checkout of the parent commit (built) whose full counting run is timed beside the re-dump")
+ap.add_argument("--repeat", type=int, default=3)
 a = ap.parse_args()
 k = 21
 rng = np.random.default_rng(5)
@@ -69,5 +74,54 @@ print(json.dumps({"genome": a.genome, "parent_reads": n_reads, "parent_gbases_ea
                   "files_per_parent": a.split, "passes": a.passes, "gzip": a.gzip, "file_GB_each_parent": round(sum(os.path.getsize(f) for f in files[0].split(",")) / 1e9, 2), "find_unique_s": round(t_unique, 2),
                   "cutoffs": [l for l in err.splitlines() if "Using counts" in l], "list_sizes": n_list,
                   "classify_s": round(t_classify, 2), "child_reads": n_long, "binned_to_the_right_parent": right}))
+if a.from_databases:
+    import re, shutil
+    cut = [int(x) for l in err.splitlines() if "Using counts" in l for x in re.findall(r"\d+", l.split("range")[1])]
+    assert len(cut) == 4, err
+    want = [open(f, "rb").read() for f in lists]
+    def cli(tree, out, extra, parents):
+        os.makedirs(out, exist_ok=True)
+        t = time.time()
+        q = subprocess.run([sys.executable, "-m", "trio_binning_amd.find_unique_kmers", "-k", str(k), "-o", out, "-s", out] + extra + parents,
+                           env=dict(os.environ, PYTHONPATH=tree), capture_output=True)
+        dt = time.time() - t
+        assert q.returncode == 0, q.stderr.decode()[-2000:]
+        got = [open(os.path.join(out, n), "rb").read() for n in ("hapA_only_kmers.txt", "hapB_only_kmers.txt")]
+        assert got == want, "the lists differ from the first run's"
+        return round(dt, 2)
+    keep = os.path.join(tmp, "keep")
+    dbs = [os.path.join(keep, "haplotypeA.tbkdb"), os.path.join(keep, "haplotypeB.tbkdb")]
+    cuts = ["--min-count-a", str(cut[0]), "--max-count-a", str(cut[1]), "--min-count-b", str(cut[2]), "--max-count-b", str(cut[3])]
+    legs = {"plain_s": [], "keep_databases_s": [], "redump_from_files_s": [], "parent_commit_plain_s": []}
+    for _ in range(a.repeat):  # the legs alternate
+        if a.tree:
+            legs["parent_commit_plain_s"].append(cli(a.tree, os.path.join(tmp, "parent"), ["--passes", str(a.passes)], files))
+        legs["plain_s"].append(cli(ROOT, os.path.join(tmp, "plain"), ["--passes", str(a.passes)], files))
+        legs["keep_databases_s"].append(cli(ROOT, keep, ["--passes", str(a.passes), "--keep-databases"], files))
+        legs["redump_from_files_s"].append(cli(ROOT, os.path.join(tmp, "redump"), cuts, dbs))
+    # the four steps on their own, in this process
+    sys.path.insert(0, ROOT)
+    from trio_binning_amd import find_unique_kmers as fu, kmers
+    steps = {"export_s": [], "save_s": [], "load_s": [], "unique_s": []}
+    n_kept = []
+    for files_string, hap in zip(files, "AB"):
+        paths = files_string.split(",")
+        counter = fu.count_library(paths, k, fu.estimate_capacity(paths), 1)
+        t = time.time(); db = counter.database(); steps["export_s"].append(round(time.time() - t, 3))
+        counter.close()
+        path = os.path.join(tmp, "step%s.tbkdb" % hap)
+        t = time.time(); db.save(path); steps["save_s"].append(round(time.time() - t, 3))
+        n_kept.append(len(db)); db.close()
+    loaded = []
+    for hap in "AB":
+        t = time.time(); loaded.append(kmers.KmerDatabase.load(os.path.join(tmp, "step%s.tbkdb" % hap))); steps["load_s"].append(round(time.time() - t, 3))
+    for x, y, lo, hi in ((0, 1, cut[0], cut[1]), (1, 0, cut[2], cut[3])):
+        t = time.time(); loaded[x].unique(loaded[y], lo, hi, os.path.join(tmp, "step.txt")); steps["unique_s"].append(round(time.time() - t, 3))
+    for d in loaded: d.close()
+    sizes = [os.path.getsize(os.path.join(tmp, "step%s.tbkdb" % hap)) for hap in "AB"]
+    print(json.dumps({"from_databases": True, "legs": legs, "steps_per_parent": steps, "kept_kmers": n_kept, "file_bytes": sizes,
+                      "file_bytes_per_kept_kmer": [round(sz / max(1, n), 4) for sz, n in zip(sizes, n_kept)]}))
+    for d in ("keep", "plain", "redump", "parent"):
+        shutil.rmtree(os.path.join(tmp, d), ignore_errors=True)
 for f in os.listdir(tmp): os.remove(os.path.join(tmp, f))
 os.rmdir(tmp)

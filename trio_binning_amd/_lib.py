@@ -198,6 +198,19 @@ _sig("tbk_counter_distinct", C.c_int, _vp, _u64p)
 _sig("tbk_counter_stats", C.c_int, _vp, _u64p, _u64p, _u64p, _u64p)
 _sig("tbk_counter_params", C.c_int, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
 _sig("tbk_counter_unique", C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, C.c_char_p, _u64p)
+HAS_KMERDB = hasattr(lib, "tbk_kmerdb_load")  # (variant builds of tools/build_variant.sh may predate the count databases)
+if HAS_KMERDB:
+    _u8p = C.POINTER(C.c_uint8)
+    _sig("tbk_counter_export", C.c_int, _vp, C.POINTER(_vp))
+    _sig("tbk_kmerdb_destroy", None, _vp)
+    _sig("tbk_kmerdb_save", C.c_int, _vp, C.c_char_p)
+    _sig("tbk_kmerdb_load", C.c_int, C.c_char_p, C.c_int, C.POINTER(_vp))
+    _sig("tbk_kmerdb_file_info", C.c_int, C.c_char_p, C.POINTER(C.c_int), _u64p, _u64p, _u64p, _u64p)
+    _sig("tbk_kmerdb_info", C.c_int, _vp, C.POINTER(C.c_int), _u64p, C.POINTER(C.c_int), _u64p)
+    _sig("tbk_kmerdb_stats", C.c_int, _vp, _u64p, _u64p)
+    _sig("tbk_kmerdb_histogram", C.c_int, _vp, _u64p)
+    _sig("tbk_kmerdb_read", C.c_int, _vp, _u64, _u64, _vp, _vp)
+    _sig("tbk_kmerdb_unique", C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, C.c_char_p, _u64p)
 _sig("tbk_calib_gather", C.c_int, C.c_int, _u64, C.c_int, C.c_int, C.c_int, _u64, C.c_int, _dp, _dp)
 _sig("tbk_calib_atomics", C.c_int, C.c_int, _u64, C.c_int, C.c_int, _dp)
 if hasattr(lib, "tbk_calib_atomics64"):

@@ -632,3 +632,365 @@ extern "C" int tbk_counter_unique(tbk_counter *a, tbk_counter *b, uint32_t min_c
     *n_written = n;
     return TBK_OK;
 }
+
+// =====================================================================================================================
+// Count databases (tbk_kmerdb): what `kmc` leaves under --outpath in the reference (find_unique_kmers.py:247) - the
+// k-mers seen at least twice with their capped counters - as an object that outlives its counter, goes to a file
+// and comes back, and is subtracted from another at cut-offs the caller names.  Keys are lexicographic ranks in
+// ascending order, so subtraction is a bisection and a dump needs no conversion.
+// =====================================================================================================================
+extern "C" hipError_t tbk_launch_count_export(uint64_t *, uint32_t, TbkMz, int, uint64_t *, uint8_t *, uint64_t, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_db_rank(const uint64_t *, const uint8_t *, uint64_t, int, uint64_t *, uint8_t *, hipStream_t);
+extern "C" hipError_t tbk_launch_kmerdb_check(const uint64_t *, const uint8_t *, uint64_t, int, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_kmerdb_unique(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, uint32_t, uint32_t, uint64_t *,
+                                               uint64_t, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_sort_u64_u8(const uint64_t *, uint64_t *, const uint8_t *, uint8_t *, uint64_t, int, hipStream_t);
+
+struct tbk_kmerdb {
+    int device = 0, k = 0;
+    uint64_t n = 0;
+    uint64_t *d_keys = nullptr;   // n ranks, strictly ascending
+    uint8_t *d_counts = nullptr;  // their counters, 2..255
+    uint64_t hist[256] = {0};     // the counter's whole histogram (tbk_counter_histogram)
+    uint64_t reads_added = 0, bases_added = 0;
+};
+
+static int kmerdb_device(int device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return cfail(TBK_ERR_NO_DEVICE, "no HIP device visible; libtbk_hip has no CPU fallback");
+    CHIP(hipSetDevice(device));
+    return TBK_OK;
+}
+
+extern "C" void tbk_kmerdb_destroy(tbk_kmerdb *db) {
+    if (!db) return;
+    if ((db->d_keys || db->d_counts) && hipSetDevice(db->device) == hipSuccess) {
+        if (db->d_keys) (void)hipFree(db->d_keys);
+        if (db->d_counts) (void)hipFree(db->d_counts);
+    }
+    delete db;
+}
+
+extern "C" int tbk_counter_export(tbk_counter *c, tbk_kmerdb **out) {
+    if (!c || !out) return cfail(TBK_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (c->broken) return cfail(TBK_ERR_INVALID, "the counter failed while it was being finished");
+    int rc = counter_device(c);
+    if (rc) return rc;
+    if (c->passes > 1) {
+        rc = counter_finish(c);
+        if (rc) return rc;
+    }
+    uint64_t hist[256];
+    rc = tbk_counter_histogram(c, hist);
+    if (rc) return rc;
+    uint64_t n = 0;
+    for (int i = 2; i < 256; i++) n += hist[i];
+    tbk_kmerdb *db = new tbk_kmerdb();
+    db->device = c->device; db->k = c->k; db->n = n;
+    db->reads_added = c->reads_added; db->bases_added = c->bases_added;
+    memcpy(db->hist, hist, sizeof hist);
+    if (n) {
+        // the pairs as they come out of the table or the classes, then ordered by rank into the database's own arrays
+        uint64_t *d_rk = nullptr;
+        uint8_t *d_rc = nullptr;
+        unsigned long long *d_n = nullptr, got = 0;
+        hipError_t e = hipMalloc((void **)&db->d_keys, n * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&db->d_counts, n);
+        if (e == hipSuccess) e = hipMalloc((void **)&d_rk, n * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&d_rc, n);
+        if (e == hipSuccess && c->passes == 1) {
+            e = hipMalloc((void **)&d_n, sizeof got);  // (a cursor of its own: the counter's d_used stays as it is)
+            if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof got);
+            if (e == hipSuccess) e = tbk_launch_count_export(c->d_lines, c->n_buckets, c->mz, c->k, d_rk, d_rc, n, d_n, nullptr);
+            if (e == hipSuccess) e = hipMemcpy(&got, d_n, sizeof got, hipMemcpyDeviceToHost);
+        } else if (e == hipSuccess) {
+            for (const tbk_counter::ClassDb &d : c->db) {
+                if (got + d.n > n) { got += d.n; continue; }  // (reported below; nothing is written past the arrays)
+                if (e == hipSuccess) e = tbk_launch_db_rank(d.d_keys, d.d_counts, d.n, c->k, d_rk + got, d_rc + got, nullptr);
+                got += d.n;
+            }
+        }
+        const bool complete = got == n;
+        if (e == hipSuccess && complete) e = tbk_launch_sort_u64_u8(d_rk, db->d_keys, d_rc, db->d_counts, n, 2 * c->k, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        for (void *p : {(void *)d_rk, (void *)d_rc, (void *)d_n})
+            if (p) (void)hipFree(p);
+        if (e != hipSuccess || !complete) {
+            tbk_kmerdb_destroy(db);
+            (void)hipGetLastError();
+            if (e != hipSuccess) return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "tbk_counter_export (%llu k-mers): %s", (unsigned long long)n, hipGetErrorString(e));
+            return cfail(TBK_ERR_HIP, "tbk_counter_export: %llu k-mers seen twice in the histogram, %llu in the counter", (unsigned long long)n, got);
+        }
+    }
+    c->finished = true;  // (a counter in passes is already)
+    *out = db;
+    return TBK_OK;
+}
+
+// ---- the file (*.tbkdb; INTEGRATION.md has the table) ---------------------------------------------------------------------
+static const char TBK_KMERDB_MAGIC[8] = {'T', 'B', 'K', 'K', 'M', 'D', 'B', '1'};
+constexpr size_t TBK_KMERDB_HEADER = 2096;
+
+struct KmerdbHeader {
+    int k = 0;
+    uint64_t n = 0, reads = 0, bases = 0, hist[256] = {0};
+};
+
+// little-endian hosts only (as the rest of the library: x86-64 beside the MI355X)
+template <typename T> static void put_le(uint8_t *p, T v) { memcpy(p, &v, sizeof v); }
+template <typename T> static T get_le(const uint8_t *p) { T v; memcpy(&v, p, sizeof v); return v; }
+
+static bool write_all(int fd, const void *p, size_t n) {
+    const uint8_t *b = (const uint8_t *)p;
+    while (n) {
+        const ssize_t r = ::write(fd, b, n);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) return false;
+        b += r; n -= (size_t)r;
+    }
+    return true;
+}
+
+static bool read_all(int fd, void *p, size_t n) {
+    uint8_t *b = (uint8_t *)p;
+    while (n) {
+        const ssize_t r = ::read(fd, b, n);
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) return false;
+        b += r; n -= (size_t)r;
+    }
+    return true;
+}
+
+// Header of an open file, checked against itself and the file's size: nothing of the content is trusted before this passes.
+static int kmerdb_read_header(int fd, const char *path, KmerdbHeader *h) {
+    const off_t end = ::lseek(fd, 0, SEEK_END);
+    if (end < 0 || ::lseek(fd, 0, SEEK_SET) != 0) return cfail(TBK_ERR_IO, "%s: %s", path, strerror(errno));
+    const uint64_t size = (uint64_t)end;
+    if (size < TBK_KMERDB_HEADER) return cfail(TBK_ERR_FORMAT, "%s: %llu bytes are less than the header of a k-mer database (%zu)", path, (unsigned long long)size, TBK_KMERDB_HEADER);
+    uint8_t b[TBK_KMERDB_HEADER];
+    if (!read_all(fd, b, sizeof b)) return cfail(TBK_ERR_IO, "%s: cannot read the header: %s", path, strerror(errno));
+    if (memcmp(b, TBK_KMERDB_MAGIC, 8) != 0) return cfail(TBK_ERR_FORMAT, "%s: not a k-mer database (magic)", path);
+    if (get_le<uint32_t>(b + 8) != TBK_KMERDB_HEADER) return cfail(TBK_ERR_FORMAT, "%s: header size %u, expected %zu", path, get_le<uint32_t>(b + 8), TBK_KMERDB_HEADER);
+    const uint32_t k = get_le<uint32_t>(b + 12);
+    if (k < 1 || k > 32) return cfail(TBK_ERR_FORMAT, "%s: k = %u out of range (1..32)", path, k);
+    const uint32_t crc = tbk_crc32_c(0, b, TBK_KMERDB_HEADER - 8);
+    if (crc != get_le<uint32_t>(b + TBK_KMERDB_HEADER - 8)) return cfail(TBK_ERR_FORMAT, "%s: header checksum mismatch (damaged file)", path);
+    if (get_le<uint32_t>(b + TBK_KMERDB_HEADER - 4) != 0) return cfail(TBK_ERR_FORMAT, "%s: header padding is not zero", path);
+    h->k = (int)k;
+    h->n = get_le<uint64_t>(b + 16);
+    h->reads = get_le<uint64_t>(b + 24);
+    h->bases = get_le<uint64_t>(b + 32);
+    for (int i = 0; i < 256; i++) h->hist[i] = get_le<uint64_t>(b + 40 + 8 * i);
+    const uint64_t body = size - TBK_KMERDB_HEADER;
+    if (body % 9 != 0 || body / 9 != h->n)  // (compared by division: 9 * n is never formed from an unchecked n)
+        return cfail(TBK_ERR_FORMAT, "%s: %llu bytes after the header do not hold the %llu k-mers it states (9 bytes each)", path, (unsigned long long)body, (unsigned long long)h->n);
+    uint64_t kept = 0;
+    for (int i = 2; i < 256; i++) {
+        if (h->hist[i] > h->n) return cfail(TBK_ERR_FORMAT, "%s: histogram row %d exceeds the number of k-mers", path, i);
+        kept += h->hist[i];  // (256 terms of at most n < 2^61: no overflow)
+    }
+    if (kept != h->n) return cfail(TBK_ERR_FORMAT, "%s: histogram rows 2..255 sum to %llu, the file states %llu k-mers", path, (unsigned long long)kept, (unsigned long long)h->n);
+    if (h->hist[0] < h->n || h->hist[0] - h->n < h->hist[1])
+        return cfail(TBK_ERR_FORMAT, "%s: histogram row 0 (all distinct k-mers) is below rows 1..255 together", path);
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_file_info(const char *path, int *k, uint64_t *n, uint64_t hist[256], uint64_t *reads, uint64_t *bases) {
+    if (!path) return cfail(TBK_ERR_INVALID, "path is NULL");
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return cfail(TBK_ERR_IO, "cannot open %s: %s", path, strerror(errno));
+    KmerdbHeader h;
+    const int rc = kmerdb_read_header(fd, path, &h);
+    ::close(fd);
+    if (rc) return rc;
+    if (k) *k = h.k;
+    if (n) *n = h.n;
+    if (hist) memcpy(hist, h.hist, sizeof h.hist);
+    if (reads) *reads = h.reads;
+    if (bases) *bases = h.bases;
+    return TBK_OK;
+}
+
+constexpr uint64_t TBK_KMERDB_PIECE = (uint64_t)1 << 22;  // k-mers per piece of a save or a load
+
+extern "C" int tbk_kmerdb_save(const tbk_kmerdb *db, const char *path) {
+    if (!db || !path) return cfail(TBK_ERR_INVALID, "NULL argument");
+    if (db->n) {
+        const int rc = kmerdb_device(db->device);
+        if (rc) return rc;
+    }
+    uint8_t b[TBK_KMERDB_HEADER];
+    memset(b, 0, sizeof b);
+    memcpy(b, TBK_KMERDB_MAGIC, 8);
+    put_le<uint32_t>(b + 8, (uint32_t)TBK_KMERDB_HEADER);
+    put_le<uint32_t>(b + 12, (uint32_t)db->k);
+    put_le<uint64_t>(b + 16, db->n);
+    put_le<uint64_t>(b + 24, db->reads_added);
+    put_le<uint64_t>(b + 32, db->bases_added);
+    for (int i = 0; i < 256; i++) put_le<uint64_t>(b + 40 + 8 * i, db->hist[i]);
+    put_le<uint32_t>(b + TBK_KMERDB_HEADER - 8, tbk_crc32_c(0, b, TBK_KMERDB_HEADER - 8));
+    const std::string tmp = std::string(path) + ".tmp";
+    const int fd = ::open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) return cfail(TBK_ERR_IO, "cannot create %s: %s", tmp.c_str(), strerror(errno));
+    bool ok = write_all(fd, b, sizeof b);
+    hipError_t e = hipSuccess;
+    std::vector<uint64_t> buf((size_t)std::min(db->n, TBK_KMERDB_PIECE));
+    for (uint64_t at = 0; ok && e == hipSuccess && at < db->n; at += TBK_KMERDB_PIECE) {
+        const uint64_t m = std::min(TBK_KMERDB_PIECE, db->n - at);
+        e = hipMemcpy(buf.data(), db->d_keys + at, m * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) ok = write_all(fd, buf.data(), m * sizeof(uint64_t));
+    }
+    for (uint64_t at = 0; ok && e == hipSuccess && at < db->n; at += TBK_KMERDB_PIECE) {
+        const uint64_t m = std::min(TBK_KMERDB_PIECE, db->n - at);
+        e = hipMemcpy(buf.data(), db->d_counts + at, m, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) ok = write_all(fd, buf.data(), m);
+    }
+    const int werr = errno;
+    const bool closed = ::close(fd) == 0;
+    if (e != hipSuccess || !ok || !closed || ::rename(tmp.c_str(), path) != 0) {
+        const int rerr = errno;
+        (void)::unlink(tmp.c_str());
+        if (e != hipSuccess) return cfail(TBK_ERR_HIP, "tbk_kmerdb_save: %s", hipGetErrorString(e));
+        return cfail(TBK_ERR_IO, "cannot write %s: %s", path, strerror(!ok ? werr : rerr));
+    }
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_load(const char *path, int device, tbk_kmerdb **out) {
+    if (!path || !out) return cfail(TBK_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return cfail(TBK_ERR_IO, "cannot open %s: %s", path, strerror(errno));
+    KmerdbHeader h;
+    int rc = kmerdb_read_header(fd, path, &h);
+    if (!rc) rc = kmerdb_device(device);
+    if (rc) { ::close(fd); return rc; }
+    tbk_kmerdb *db = new tbk_kmerdb();
+    db->device = device; db->k = h.k; db->n = h.n;
+    db->reads_added = h.reads; db->bases_added = h.bases;
+    memcpy(db->hist, h.hist, sizeof h.hist);
+    if (h.n) {
+        unsigned long long *d_tally = nullptr, tally[3 + 256];
+        bool ok = true;
+        hipError_t e = hipMalloc((void **)&db->d_keys, h.n * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&db->d_counts, h.n);
+        if (e == hipSuccess) e = hipMalloc((void **)&d_tally, sizeof tally);
+        if (e == hipSuccess) e = hipMemset(d_tally, 0, sizeof tally);
+        std::vector<uint64_t> buf((size_t)std::min(h.n, TBK_KMERDB_PIECE));
+        for (uint64_t at = 0; ok && e == hipSuccess && at < h.n; at += TBK_KMERDB_PIECE) {
+            const uint64_t m = std::min(TBK_KMERDB_PIECE, h.n - at);
+            ok = read_all(fd, buf.data(), m * sizeof(uint64_t));
+            if (ok) e = hipMemcpy(db->d_keys + at, buf.data(), m * sizeof(uint64_t), hipMemcpyHostToDevice);
+        }
+        for (uint64_t at = 0; ok && e == hipSuccess && at < h.n; at += TBK_KMERDB_PIECE) {
+            const uint64_t m = std::min(TBK_KMERDB_PIECE, h.n - at);
+            ok = read_all(fd, buf.data(), m);
+            if (ok) e = hipMemcpy(db->d_counts + at, buf.data(), m, hipMemcpyHostToDevice);
+        }
+        // the content is only data so far: one pass tells whether it may be searched and tallied by
+        if (ok && e == hipSuccess) e = tbk_launch_kmerdb_check(db->d_keys, db->d_counts, h.n, h.k, d_tally, nullptr);
+        if (ok && e == hipSuccess) e = hipMemcpy(tally, d_tally, sizeof tally, hipMemcpyDeviceToHost);
+        if (d_tally) (void)hipFree(d_tally);
+        ::close(fd);
+        if (!ok || e != hipSuccess) {
+            tbk_kmerdb_destroy(db);
+            (void)hipGetLastError();
+            if (!ok) return cfail(TBK_ERR_IO, "%s: cannot read the k-mers: %s", path, strerror(errno));
+            return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "tbk_kmerdb_load (%llu k-mers): %s", (unsigned long long)h.n, hipGetErrorString(e));
+        }
+        int row = 0;
+        for (int i = 2; i < 256 && !row; i++)
+            if (tally[3 + i] != h.hist[i]) row = i;
+        if (tally[0] || tally[1] || tally[2] || row) {
+            tbk_kmerdb_destroy(db);
+            if (tally[0]) return cfail(TBK_ERR_FORMAT, "%s: the k-mers are not in strictly ascending order (%llu places)", path, tally[0]);
+            if (tally[1]) return cfail(TBK_ERR_FORMAT, "%s: %llu k-mers have bits above 2k = %d", path, tally[1], 2 * h.k);
+            if (tally[2]) return cfail(TBK_ERR_FORMAT, "%s: %llu counters are below 2", path, tally[2]);
+            return cfail(TBK_ERR_FORMAT, "%s: %llu counters are %d, the header's histogram states %llu", path, tally[3 + row], row, (unsigned long long)h.hist[row]);
+        }
+    } else {
+        ::close(fd);
+    }
+    *out = db;
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_info(const tbk_kmerdb *db, int *k, uint64_t *n, int *device, uint64_t *bytes) {
+    if (!db) return cfail(TBK_ERR_INVALID, "database is NULL");
+    if (k) *k = db->k;
+    if (n) *n = db->n;
+    if (device) *device = db->device;
+    if (bytes) *bytes = db->n * 9;
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_stats(const tbk_kmerdb *db, uint64_t *reads_added, uint64_t *bases_added) {
+    if (!db) return cfail(TBK_ERR_INVALID, "database is NULL");
+    if (reads_added) *reads_added = db->reads_added;
+    if (bases_added) *bases_added = db->bases_added;
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_histogram(const tbk_kmerdb *db, uint64_t hist[256]) {
+    if (!db || !hist) return cfail(TBK_ERR_INVALID, "NULL argument");
+    memcpy(hist, db->hist, sizeof db->hist);
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_read(const tbk_kmerdb *db, uint64_t first, uint64_t count, uint64_t *keys, uint8_t *counts) {
+    if (!db) return cfail(TBK_ERR_INVALID, "database is NULL");
+    if (first > db->n || count > db->n - first)
+        return cfail(TBK_ERR_INVALID, "entries %llu + %llu lie outside a database of %llu", (unsigned long long)first, (unsigned long long)count, (unsigned long long)db->n);
+    if (!count) return TBK_OK;
+    const int rc = kmerdb_device(db->device);
+    if (rc) return rc;
+    if (keys) CHIP(hipMemcpy(keys, db->d_keys + first, count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (counts) CHIP(hipMemcpy(counts, db->d_counts + first, count, hipMemcpyDeviceToHost));
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_unique(const tbk_kmerdb *a, const tbk_kmerdb *b, uint32_t min_count, uint32_t max_count, const char *out_path,
+                                 uint64_t *n_written) {
+    if (!a || !b || !out_path || !n_written) return cfail(TBK_ERR_INVALID, "NULL argument");
+    if (a->k != b->k) return cfail(TBK_ERR_INVALID, "the databases have different k (%d and %d)", a->k, b->k);
+    if (a->device != b->device) return cfail(TBK_ERR_INVALID, "the databases live on different devices");
+    *n_written = 0;
+    // upper bound of what can come out: k-mers of A with a counter in range
+    uint64_t cap = 0;
+    for (uint32_t cnt = std::max<uint32_t>(2, min_count); cnt <= std::min<uint32_t>(255, max_count); cnt++) cap += a->hist[cnt];
+    cap = std::min(cap, a->n);
+    uint64_t n = 0;
+    std::vector<uint64_t> h_keys;
+    if (cap) {
+        const int rc = kmerdb_device(a->device);
+        if (rc) return rc;
+        uint64_t *d_out = nullptr, *d_sorted = nullptr;
+        unsigned long long *d_n = nullptr, got = 0;
+        hipError_t e = hipMalloc((void **)&d_out, cap * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&d_sorted, cap * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&d_n, sizeof got);
+        if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof got);
+        if (e == hipSuccess) e = tbk_launch_kmerdb_unique(a->d_keys, a->d_counts, a->n, b->d_keys, b->n, min_count, max_count, d_out, cap, d_n, nullptr);
+        if (e == hipSuccess) e = hipMemcpy(&got, d_n, sizeof got, hipMemcpyDeviceToHost);
+        n = std::min<uint64_t>(got, cap);
+        // (waves append in the order they get there: the dump is ordered as tbk_counter_unique orders its own)
+        if (e == hipSuccess && n) e = tbk_launch_sort_u64(d_out, d_sorted, n, 2 * a->k, nullptr);
+        if (e == hipSuccess && n) {
+            h_keys.resize(n);
+            e = hipMemcpy(h_keys.data(), d_sorted, n * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        }
+        if (d_out) (void)hipFree(d_out);
+        if (d_sorted) (void)hipFree(d_sorted);
+        if (d_n) (void)hipFree(d_n);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "tbk_kmerdb_unique: %s", hipGetErrorString(e));
+        }
+    }
+    std::string err;
+    if (!write_list(out_path, h_keys.data(), n, a->k, err)) return cfail(TBK_ERR_IO, "%s", err.c_str());
+    *n_written = n;
+    return TBK_OK;
+}

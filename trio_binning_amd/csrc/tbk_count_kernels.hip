@@ -437,6 +437,132 @@ tbk_db_unique_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restr
     }
 }
 
+// ---- count databases (tbk_kmerdb): what a counter leaves behind, as an object of its own ---------------
+// A database is n (lexicographic rank, counter 2..255) pairs in ascending order of the rank - the form kmc_dump
+// prints and write_list takes.  The kernels below make one from a counter, check one that came from a file
+// and subtract two.
+
+// the lexicographic rank (base 0 in the top bits of the 2k) of a key in the table's form
+__device__ __forceinline__ uint64_t lex_rank(uint64_t key, int k) {
+    const uint64_t lex = ((uint64_t)rev_pairs((uint32_t)key) << 32) | (uint64_t)rev_pairs((uint32_t)(key >> 32));
+    return lex >> (64 - 2 * k);
+}
+
+// A live one-pass table to (rank, capped counter) pairs: tbk_count_distil_kernel without its stores to the
+// table, which is only read.  Appends are per wave; the order is the sort's business.
+__global__ void __launch_bounds__(256)
+tbk_count_export_kernel(TbkCountView t, int k, uint64_t *__restrict__ out_keys, uint8_t *__restrict__ out_counts, uint64_t capacity,
+                        unsigned long long *__restrict__ n_out) {
+    const uint64_t n_slots = (uint64_t)t.n_buckets * TBK_SLOTS_PER_BUCKET;
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; i0 < n_slots; i0 += step) {
+        const uint64_t i = i0 + lane;
+        bool emit = false;
+        uint64_t key = 0;
+        uint32_t raw = 0;
+        if (i < n_slots) {
+            key = t.keys((uint32_t)(i >> 3))[i & 7];
+            if (key != TBK_EMPTY) {
+                raw = t.counts((uint32_t)(i >> 3))[i & 7];
+                emit = raw >= 2u;
+            }
+        }
+        const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
+        if (mask) {
+            unsigned long long base = 0;
+            const int leader = __builtin_ctzll(mask);
+            if ((int)lane == leader) base = atomicAdd(n_out, (unsigned long long)__popcll(mask));
+            base = __shfl(base, leader);
+            if (emit) {
+                const uint64_t at = base + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+                if (at < capacity) {
+                    out_keys[at] = lex_rank(key, k);
+                    out_counts[at] = (uint8_t)(raw < 255u ? raw : 255u);
+                }
+            }
+        }
+    }
+}
+
+// The database of one class (keys in the table's form) to ranks, copied to its place among the other classes'.
+__global__ void __launch_bounds__(256)
+tbk_db_rank_kernel(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ counts, uint64_t n, int k,
+                   uint64_t *__restrict__ out_keys, uint8_t *__restrict__ out_counts) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        out_keys[i] = lex_rank(keys[i], k);
+        out_counts[i] = counts[i];
+    }
+}
+
+// One pass over a database that came from a file, before anything indexes by its content.  tally[0]: places where
+// key[i] >= key[i + 1] (every element reads its right neighbour from memory, so the pairs that straddle a wave, a
+// block or a grid stride are compared like any other); tally[1]: keys with a bit of high_mask (the bits above
+// 2k; 0 for k = 32); tally[2]: counters below 2; tally[3 + c]: counters equal to c.
+__global__ void __launch_bounds__(256)
+tbk_kmerdb_check_kernel(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ counts, uint64_t n, uint64_t high_mask,
+                        unsigned long long *__restrict__ tally) {
+    __shared__ unsigned int h[256];
+    __shared__ unsigned int bad[3];
+    h[threadIdx.x] = 0;
+    if (threadIdx.x < 3) bad[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t disorder = 0, high = 0, low = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t key = keys[i];
+        const uint32_t c = counts[i];
+        if (i + 1 < n && key >= keys[i + 1]) disorder++;
+        if (key & high_mask) high++;
+        if (c < 2u) low++;
+        atomicAdd(&h[c], 1u);
+    }
+    if (disorder) atomicAdd(&bad[0], disorder);
+    if (high) atomicAdd(&bad[1], high);
+    if (low) atomicAdd(&bad[2], low);
+    __syncthreads();
+    if (threadIdx.x < 3 && bad[threadIdx.x]) atomicAdd(&tally[threadIdx.x], (unsigned long long)bad[threadIdx.x]);
+    if (h[threadIdx.x]) atomicAdd(&tally[3 + threadIdx.x], (unsigned long long)h[threadIdx.x]);
+}
+
+// kmers_subtract + kmc_dump between two databases: the ranks of A whose counter lies in [ci, cx] and that are not
+// among B's ascending ranks (bisection, as in tbk_db_unique_kernel); appended per wave, sorted by the host after.
+__global__ void __launch_bounds__(256)
+tbk_kmerdb_unique_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restrict__ a_counts, uint64_t n_a,
+                         const uint64_t *__restrict__ b_keys, uint64_t n_b, uint32_t ci, uint32_t cx,
+                         uint64_t *__restrict__ out, uint64_t capacity, unsigned long long *__restrict__ n_out) {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; i0 < n_a; i0 += step) {
+        const uint64_t i = i0 + lane;
+        bool emit = false;
+        uint64_t key = 0;
+        if (i < n_a) {
+            key = a_keys[i];
+            const uint32_t c = a_counts[i];
+            emit = c >= 2u && c >= ci && c <= cx;
+            if (emit) {
+                uint64_t lo = 0, hi = n_b;  // first element >= key
+                while (lo < hi) {
+                    const uint64_t mid = lo + (hi - lo) / 2;
+                    if (b_keys[mid] < key) lo = mid + 1; else hi = mid;
+                }
+                emit = !(lo < n_b && b_keys[lo] == key);
+            }
+        }
+        const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
+        if (mask) {
+            unsigned long long base = 0;
+            const int leader = __builtin_ctzll(mask);
+            if ((int)lane == leader) base = atomicAdd(n_out, (unsigned long long)__popcll(mask));
+            base = __shfl(base, leader);
+            if (emit) {
+                const uint64_t at = base + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+                if (at < capacity) out[at] = key;
+            }
+        }
+    }
+}
+
 // =======================================================================================
 // launchers (called from tbk_count.cpp)
 // =======================================================================================
@@ -537,5 +663,40 @@ extern "C" hipError_t tbk_launch_db_unique(const uint64_t *a_keys, const uint8_t
     const uint64_t blocks = (n_a + 255) / 256;
     hipLaunchKernelGGL(tbk_db_unique_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, a_keys, a_counts, n_a, b_sorted, n_b,
                        k, ci, cx, d_out, capacity, d_n);
+    return hipGetLastError();
+}
+
+// ---- count databases ------------------------------------------------------------------------------------
+extern "C" hipError_t tbk_launch_count_export(uint64_t *d_lines, uint32_t n_buckets, TbkMz mz, int k, uint64_t *d_keys, uint8_t *d_counts,
+                                              uint64_t capacity, unsigned long long *d_n, hipStream_t stream) {
+    hipLaunchKernelGGL(tbk_count_export_kernel, dim3(4096), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz}, k, d_keys, d_counts, capacity, d_n);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t tbk_launch_db_rank(const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, int k, uint64_t *d_out_keys,
+                                         uint8_t *d_out_counts, hipStream_t stream) {
+    if (!n) return hipSuccess;
+    const uint64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(tbk_db_rank_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, d_keys, d_counts, n, k, d_out_keys, d_out_counts);
+    return hipGetLastError();
+}
+
+// d_tally: 3 + 256 words, zeroed by the caller
+extern "C" hipError_t tbk_launch_kmerdb_check(const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, int k, unsigned long long *d_tally,
+                                              hipStream_t stream) {
+    if (!n) return hipSuccess;
+    const uint64_t high_mask = k >= 32 ? 0ull : ~0ull << (2 * k);
+    const uint64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(tbk_kmerdb_check_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, d_keys, d_counts, n, high_mask, d_tally);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t tbk_launch_kmerdb_unique(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *b_keys, uint64_t n_b,
+                                               uint32_t ci, uint32_t cx, uint64_t *d_out, uint64_t capacity, unsigned long long *d_n,
+                                               hipStream_t stream) {
+    if (!n_a) return hipSuccess;
+    const uint64_t blocks = (n_a + 255) / 256;
+    hipLaunchKernelGGL(tbk_kmerdb_unique_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, a_keys, a_counts, n_a, b_keys, n_b,
+                       ci, cx, d_out, capacity, d_n);
     return hipGetLastError();
 }

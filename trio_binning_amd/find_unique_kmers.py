@@ -57,11 +57,37 @@ def parse_args(argv=None):
              "included, outgrow the HBM); 1: one pass, nothing kept; default 0: the fewest passes that fit (choose_passes)",
     )
     parser.add_argument(
+        "--keep-databases", action="store_true",
+        help="leave each parent's count database as <outpath>/haplotypeA.tbkdb and haplotypeB.tbkdb (where kmc leaves "
+             "haplotypeA.* in the reference) and go on from them: a later run takes such a file in place of a parent's "
+             "reads and dumps again, at other cut-offs, without counting",
+    )
+    for hap in "ab":
+        for bound in ("min", "max"):
+            parser.add_argument(
+                "--{}-count-{}".format(bound, hap), type=int, default=None, metavar="N",
+                help="count cut-offs of haplotype {} chosen by hand (give both): its histogram is written but not "
+                     "analyzed".format(hap.upper()),
+            )
+    parser.add_argument(
         "read_files", nargs=2,
         help="one comma-separated list of file paths for both libraries being compared. Files can "
-             "be in fasta or fastq format, and uncompressed or gzipped.",
+             "be in fasta or fastq format, and uncompressed or gzipped. A single path ending in .tbkdb is a count "
+             "database kept by --keep-databases: it is loaded instead of counted.",
     )
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    for hap in "ab":
+        lo, hi = getattr(args, "min_count_" + hap), getattr(args, "max_count_" + hap)
+        if (lo is None) != (hi is None):
+            parser.error("--min-count-{0} and --max-count-{0} go together".format(hap))
+        if lo is not None and not 1 <= lo <= hi:
+            parser.error("--min-count-{0} {1} --max-count-{0} {2}: need 1 <= min <= max".format(hap, lo, hi))
+    return args
+
+
+def is_database_path(files_string: str) -> bool:
+    """A parent argument that names one count database (*.tbkdb) and no read files."""
+    return "," not in files_string and files_string.endswith(DATABASE_SUFFIX)
 
 
 def analyze_histogram(rows: Sequence[Tuple[int, int]], histogram_path: str = "") -> Tuple[int, int]:
@@ -177,6 +203,7 @@ def estimate_bases(paths: List[str]) -> int:
     return bases
 
 
+DATABASE_SUFFIX = ".tbkdb"
 MAX_PASSES = 1024          # TBK_COUNTER_MAX_PASSES
 PLAN_FRACTION = (4, 5)     # choose_passes plans with 4/5 of the free HBM
 TABLE_BYTES = (80, 3)      # per distinct k-mer of a table: 16 bytes per slot at load 0.6
@@ -248,34 +275,75 @@ def write_histogram(path: str, hist: Sequence[int]) -> List[Tuple[int, int]]:
 def main(argv=None):
     args = parse_args(argv)
     k = args.kmer_size
-    libraries = []  # (counter, min_count, max_count)
+    libraries = []  # (counter or database, min_count, max_count)
     if args.passes < 0 or args.passes > MAX_PASSES:
         raise ValueError("--passes must be between 0 and {}".format(MAX_PASSES))
+    hap_ids = ["A", "B"]
+    from_file = [is_database_path(s) for s in args.read_files]
+    # with none of the database options both counters stay live until the dumps are written, as ever
+    by_database = args.keep_databases or any(from_file)
+    given = {"A": (args.min_count_a, args.max_count_a), "B": (args.min_count_b, args.max_count_b)}
+    for hap_id, path, is_db in zip(hap_ids, args.read_files, from_file):
+        if is_db:  # its header says what it holds: checked before anything is counted
+            info = kmers.database_file_info(path)
+            if info["k"] != k:
+                sys.exit("find-unique-kmers: {} holds {}-mers, but -k {} was given".format(path, info["k"], k))
     passes = args.passes
     if not passes:
         # both parents are counted in the same number of passes (their classes must match): the larger need decides
-        passes, free = 1, kmers.device_mem_info()[0]
-        for files_string in args.read_files:
+        passes, free = 1, kmers.device_mem_info()[0] if not all(from_file) else 0
+        for files_string, is_db in zip(args.read_files, from_file):
+            if is_db:
+                continue
             paths = [p for p in files_string.split(",") if os.path.isfile(p)]  # (a missing file is reported below, in its turn)
             bases = estimate_bases(paths)
             passes = max(passes, choose_passes(args.capacity or max(1 << 16, bases), bases, free))
+    kept = {}      # haplotype -> the database file it can be dumped from again
+    held = None    # the first HistogramError of a --keep-databases run: raised once both databases are on disk
     try:
-        for hap_id, files_string in zip(["A", "B"], args.read_files):
-            print("\033[92mCounting k-mers in haplotype {}...\033[0m".format(hap_id), file=sys.stderr)
-            paths = files_string.split(",")
-            for p in paths:
-                if not os.path.isfile(p):
-                    raise IOError("no such file: {}".format(p))
-            # (in passes the table holds one class and is not bound by what two resident tables may take)
-            capacity = args.capacity or (estimate_capacity(paths) if passes == 1 else max(1 << 16, estimate_bases(paths)))
-            counter = count_library(paths, k, capacity, passes)
-            libraries.append([counter, None, None])
+        for hap_id, files_string, is_db in zip(hap_ids, args.read_files, from_file):
+            if is_db:
+                print("\033[92mLoading the k-mer database of haplotype {}...\033[0m".format(hap_id), file=sys.stderr)
+                libraries.append([kmers.KmerDatabase.load(files_string), None, None])
+                kept[hap_id] = files_string
+            else:
+                print("\033[92mCounting k-mers in haplotype {}...\033[0m".format(hap_id), file=sys.stderr)
+                paths = files_string.split(",")
+                for p in paths:
+                    if not os.path.isfile(p):
+                        raise IOError("no such file: {}".format(p))
+                # (in passes the table holds one class and is not bound by what two resident tables may take)
+                capacity = args.capacity or (estimate_capacity(paths) if passes == 1 else max(1 << 16, estimate_bases(paths)))
+                counter = count_library(paths, k, capacity, passes)
+                if by_database:
+                    # the database takes the counter's place: its table leaves the HBM before the other parent is counted
+                    try:
+                        libraries.append([counter.database(), None, None])
+                    finally:
+                        counter.close()
+                    if args.keep_databases:
+                        kept[hap_id] = os.path.join(args.outpath, "haplotype{}{}".format(hap_id, DATABASE_SUFFIX))
+                        libraries[-1][0].save(kept[hap_id])
+                else:
+                    libraries.append([counter, None, None])
             print("\033[92mComputing and analyzing histogram...\033[0m", file=sys.stderr)
             histogram_path = os.path.join(args.scratch_dir, "haplotype{}.histogram".format(hap_id))
-            rows = write_histogram(histogram_path, counter.histogram())
-            min_count, max_count = analyze_histogram(rows, histogram_path)
+            rows = write_histogram(histogram_path, libraries[-1][0].histogram())
+            if given[hap_id][0] is not None:
+                min_count, max_count = given[hap_id]
+            else:
+                try:
+                    min_count, max_count = analyze_histogram(rows, histogram_path)
+                except HistogramError as exc:
+                    if not args.keep_databases:
+                        raise
+                    held = held or exc
+                    continue
             print("\033[92mUsing counts in range [{},{}].\033[0m".format(min_count, max_count), file=sys.stderr)
             libraries[-1][1:] = [min_count, max_count]
+        if held is not None:
+            print(redump_advice(args, kept, libraries), file=sys.stderr)
+            raise held
         (counter_a, min_a, max_a), (counter_b, min_b, max_b) = libraries
         print("\033[92mFinding and dumping k-mers unique to haplotype A...\033[0m", file=sys.stderr)
         n_a = counter_a.unique(counter_b, min_a, max_a, os.path.join(args.outpath, "hapA_only_kmers.txt"))
@@ -286,6 +354,16 @@ def main(argv=None):
             lib[0].close()
     print("\n\n\033[94m# of unique k-mers in haplotype A: {}\033[0m".format(n_a), file=sys.stderr)
     print("\033[94m# of unique k-mers in haplotype B: {}\033[0m".format(n_b), file=sys.stderr)
+
+
+def redump_advice(args, kept, libraries) -> str:
+    """What to run once cut-offs have been chosen by hand: the databases are on disk, nothing is counted again."""
+    words = ["find-unique-kmers", "-k", str(args.kmer_size), "-o", args.outpath, "-s", args.scratch_dir]
+    for hap_id, (_, lo, hi) in zip("AB", libraries):
+        words += ["--min-count-" + hap_id.lower(), str(lo) if lo else "MIN", "--max-count-" + hap_id.lower(), str(hi) if hi else "MAX"]
+    words += [kept["A"], kept["B"]]
+    return ("The k-mer databases are kept in {} and {}. Choose the cut-offs marked MIN and MAX from the histograms and dump "
+            "again, without counting:\n  {}".format(kept["A"], kept["B"], " ".join(words)))
 
 
 if __name__ == "__main__":

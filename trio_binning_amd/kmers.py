@@ -880,10 +880,95 @@ class KmerCounter:
         check(lib.tbk_counter_unique(self._h, other._h, min_count, max_count, os.fsencode(out_path), C.byref(n)))
         return n.value
 
+    def database(self) -> "KmerDatabase":
+        """The counter's database as an object of its own (``tbk_counter_export``): it outlives the counter, which
+        takes no more reads afterwards.  A one-pass counter still answers ``histogram`` and ``unique`` as before."""
+        h = C.c_void_p()
+        check(lib.tbk_counter_export(self._h, C.byref(h)))
+        return KmerDatabase(h)
+
     def close(self) -> None:
         if self._h is not None and self._h.value:
             h, self._h = self._h, None
             lib.tbk_counter_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def database_file_info(path: str) -> dict:
+    """Header of a ``*.tbkdb`` file, checked (``tbk_kmerdb_file_info``); touches no device.  ``IOError`` for a file
+    that cannot be read, ``ValueError`` for one that is not a sound database."""
+    k, n, reads, bases = C.c_int(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    hist = np.zeros(256, dtype=np.uint64)
+    check(lib.tbk_kmerdb_file_info(os.fsencode(path), C.byref(k), C.byref(n), hist.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                   C.byref(reads), C.byref(bases)))
+    return {"k": k.value, "n": n.value, "histogram": hist, "reads_added": reads.value, "bases_added": bases.value}
+
+
+class KmerDatabase:
+    """What a ``KmerCounter`` leaves behind, kept: the k-mers seen at least twice as ascending lexicographic ranks
+    with their counters (2..255) in HBM, and the counter's whole histogram - the ``haplotypeA.*`` database `kmc`
+    leaves under --outpath in the reference (find_unique_kmers.py:247).  It goes to a ``*.tbkdb`` file and comes
+    back checked (include/tbk.h), and ``unique`` re-dumps from it at any cut-offs without counting again."""
+
+    def __init__(self, handle):
+        self._h = handle
+        k, n, device = C.c_int(), C.c_uint64(), C.c_int()
+        check(lib.tbk_kmerdb_info(self._h, C.byref(k), C.byref(n), C.byref(device), None))
+        self.k, self._n, self.device = k.value, n.value, device.value
+
+    @classmethod
+    def load(cls, path: str, device: Optional[int] = None) -> "KmerDatabase":
+        h = C.c_void_p()
+        check(lib.tbk_kmerdb_load(os.fsencode(path), default_device() if device is None else device, C.byref(h)))
+        return cls(h)
+
+    def __len__(self) -> int:
+        return self._n
+
+    def save(self, path: str) -> None:
+        check(lib.tbk_kmerdb_save(self._h, os.fsencode(path)))
+
+    def histogram(self) -> np.ndarray:
+        """The histogram of the counter the database came from (``KmerCounter.histogram``), all 256 rows."""
+        hist = np.zeros(256, dtype=np.uint64)
+        check(lib.tbk_kmerdb_histogram(self._h, hist.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return hist
+
+    def stats(self) -> dict:
+        reads, bases, nbytes = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib.tbk_kmerdb_stats(self._h, C.byref(reads), C.byref(bases)))
+        check(lib.tbk_kmerdb_info(self._h, None, None, None, C.byref(nbytes)))
+        return {"reads_added": reads.value, "bases_added": bases.value, "bytes": nbytes.value}
+
+    def entries(self, first: int = 0, count: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(keys uint64, counts uint8) of ``count`` entries from ``first`` on (default: all that follow)."""
+        if count is None:
+            count = max(0, self._n - first)
+        keys, counts = np.zeros(count, dtype=np.uint64), np.zeros(count, dtype=np.uint8)
+        check(lib.tbk_kmerdb_read(self._h, first, count, keys.ctypes.data, counts.ctypes.data))
+        return keys, counts
+
+    def unique(self, other: "KmerDatabase", min_count: int, max_count: int, out_path: str) -> int:
+        """``KmerCounter.unique`` between two databases: the same file."""
+        n = C.c_uint64()
+        check(lib.tbk_kmerdb_unique(self._h, other._h, min_count, max_count, os.fsencode(out_path), C.byref(n)))
+        return n.value
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            h, self._h = self._h, None
+            lib.tbk_kmerdb_destroy(h)
 
     def __enter__(self):
         return self
