@@ -12,6 +12,7 @@ compare counts, histograms and A-minus-B lists with oracle/unique_oracle.py's nu
   test_saturation_and_cutoffs            counters of exactly 1, 2, 3, 254, 255, 256, 300 against B counters of 0, 1, 2
   test_load_and_growth                   TBK_COUNT_LOAD at and beyond its clamps, tables that start at 16 buckets
   test_multi_piece_add                   one add of four pieces (> 3 x 64 M window starts), the table growing between them
+  test_multi_piece_add_in_passes         the same add with passes = 3: the rebuild between the pieces falls into class 0
   test_clamp_keeps_a_counter_below_the_carry   one counter past 2^32 window starts with seven witnesses in its bucket
 
 The matrix runs W = 0 at k = 15, 21, 32, every W from 1 to 8 with m <= 16 (45 triples, m = 4 .. 16, and W = 9, which is clamped
@@ -53,15 +54,17 @@ def _rand(rng, n):
 
 class _Pinned:
     """A KmerCounter with the TBK_COUNT_* knobs pinned: they are put back before every call that may allocate a table (creation
-    and every add - a table that grows asks again), and after each the table must run the bucket selection the case names."""
+    and every add - a table that grows asks again), and after each the table must run the bucket selection the case names.
+    With passes > 1 a table is also rebuilt while the later classes are replayed - inside finish(), histogram(), unique() and
+    database() - so those go through the helper too: pinned before, (w, m, o) checked after."""
 
-    def __init__(self, mp, k, capacity, w=None, m=None, load=None, expect=None):
+    def __init__(self, mp, k, capacity, w=None, m=None, load=None, expect=None, passes=1, store_limit=0):
         from trio_binning_amd import kmers
 
-        self.mp, self.k, self.expect = mp, k, tuple(expect)
+        self.mp, self.k, self.expect, self.passes = mp, k, tuple(expect), passes
         self.env = dict(zip(_KNOBS, (w, m, load)))
         self._pin()
-        self.c = kmers.KmerCounter(k, capacity)
+        self.c = kmers.KmerCounter(k, capacity, passes=passes, store_limit=store_limit)
         self.stats()
 
     def _pin(self):
@@ -84,6 +87,34 @@ class _Pinned:
         self.c.add(bases, offsets)
         self.stats()
 
+    def finish(self):
+        self._pin()
+        self.c.finish()
+        return self.stats()
+
+    def histogram(self):
+        self._pin()
+        hist = self.c.histogram()
+        self.stats()
+        return hist
+
+    def unique(self, other, lo, hi, out):
+        """unique() of two counters in passes finishes both: `other` is finished under its own pins first, so that no table of
+        its is rebuilt under this counter's."""
+        if self.passes > 1:
+            other.finish()
+        self._pin()
+        n = self.c.unique(other.c, lo, hi, out)
+        self.stats()
+        other.stats()
+        return n
+
+    def database(self):
+        self._pin()
+        db = self.c.database()
+        self.stats()
+        return db
+
     def __enter__(self):
         return self
 
@@ -102,13 +133,13 @@ def _expect(k, w, m):
 
 def _compare(ca, cb, oa, ob, k, tmp_path, windows):
     """Distinct count, whole histogram and the A-minus-B lists of two counters against the oracle's counts (keys, counts)."""
-    hist = ca.c.histogram()
+    hist = ca.histogram()
     want = uo.histogram_np(oa[1])
     assert ca.stats()["distinct"] == oa[0].size
     assert [int(x) for x in hist] == [int(x) for x in want]
     for lo, hi in windows:
         out = str(tmp_path / f"u_{lo}_{hi}.txt")
-        n = ca.c.unique(cb.c, lo, hi, out)
+        n = ca.unique(cb, lo, hi, out)
         got = uo.read_list_np(out, k)
         expected = uo.unique_np(oa, ob, lo, hi)
         assert n == got.size == expected.size and np.array_equal(got, expected), (k, lo, hi, n, expected.size)
@@ -360,6 +391,34 @@ def test_multi_piece_add(gpu, deep, tmp_path, monkeypatch, w, m, expect, grown):
         launches, windows, _ = ca.c.kernel_timing()
         assert launches == 4 and windows == int(a[1][-1]) + a[1].size - 1
         assert [int(x) for x in ca.c.histogram()] == [int(x) for x in c_hist]
+        _compare(ca, cb, oa, ob, k, tmp_path, ((2, 255), (20, 60), (1, 4)))
+
+
+@pytest.mark.parametrize("w,m,expect,grown", [(None, None, (6, 15, 6), (6, 17, 5)), (4, 17, (4, 17, 6), (4, 17, 6))], ids=["default", "W4-m17"])
+def test_multi_piece_add_in_passes(gpu, deep, tmp_path, monkeypatch, w, m, expect, grown):
+    """The same add with passes = 3: the 202 M positions are retained and counted in several pieces for class 0, then replayed in
+    the same pieces for classes 1 and 2.  Three times the capacity of test_multi_piece_add gives a class the same first table of
+    2440 slots, so class 0 meets the same rebuild between the first piece and the second (the third of the genome's k-mers that
+    is in by then is still more than the 0.85 M slots the first rebuild leaves over a piece); the table after it is larger than
+    the first one that holds a piece, which is asserted.  Left to itself the table changes from the 32-bit selection to the
+    64-bit one there, in the middle of class 0; the pinned case keeps one 64-bit selection throughout.  Histogram against the C
+    oracle, lists against the numpy counter; three passes over the store cost the device well under a second."""
+    k, a, b, oa, ob, c_hist = deep
+    with _Pinned(monkeypatch, k, 3 * 1390, w, m, None, expect, passes=3) as ca, _Pinned(monkeypatch, k, 90_000_000, w, m, None, expect, passes=3) as cb:
+        assert ca.stats()["n_slots"] == 2440
+        ca.expect = grown
+        ca.add_packed(*a)
+        cb.add_packed(*b)
+        st = ca.stats()
+        positions = int(a[1][-1]) + a[1].size - 1
+        first = (int(2928 * 2 ** 14 / 4.8) + 16) * 8  # the first table of the doubling rule whose 0.85 holds a piece (test_multi_piece_add)
+        assert int(0.85 * first) > _PIECE and st["n_slots"] > first and positions > 3 * _PIECE
+        assert st["store_used_bytes"] == 8 * ((positions + 15) // 16) and st["passes"] == 3 and not st["finished"]
+        launches, windows, _ = ca.c.kernel_timing()
+        assert launches > 1 and windows == 16 * ((positions + 15) // 16)
+        assert [int(x) for x in ca.histogram()] == [int(x) for x in c_hist]
+        launches, windows, _ = ca.c.kernel_timing()
+        assert launches > 2 and windows == 2 * 16 * ((positions + 15) // 16)  # classes 1 and 2, from the store
         _compare(ca, cb, oa, ob, k, tmp_path, ((2, 255), (20, 60), (1, 4)))
 
 
