@@ -98,7 +98,8 @@ void tbk_reverse_complement(const char *kmer_in, char *kmer_out, unsigned char k
  * every tool writes them - each line k bytes and a newline - whose text is staged through pinned memory and
  * packed one line per thread (TBK_LIST_GPU_PARSE=0: off); (3) the general host parser (the reference's getline
  * rules line by line) for anything else.  All three give the same keys.  tbk_table_origin says which it was
- * (0 keys from the caller / the host parser, 1 the GPU parser, 2 the cache); tbk_table_keys copies the keys out. */
+ * (0 keys from the caller / the host parser, 1 the GPU parser, 2 the cache, 3 no file at all: two count databases,
+ * tbk_kmerdb_unique_table); tbk_table_keys copies the keys out. */
 int tbk_table_create_from_file(const char *path, int device, tbk_table **out);
 int tbk_table_origin(const tbk_table *t);
 /* The list's packed keys where they lie in HBM on the list's device (num_kmers of them; read-only, valid until the list is
@@ -735,6 +736,18 @@ int tbk_kmerdb_read(const tbk_kmerdb *db, uint64_t first, uint64_t count, uint64
  * empty range or an empty `a` gives an empty file and TBK_OK; a different k or device is TBK_ERR_INVALID. */
 int tbk_kmerdb_unique(const tbk_kmerdb *a, const tbk_kmerdb *b, uint32_t min_count, uint32_t max_count, const char *out_path,
                       uint64_t *n_written);
+/* The same selection as a k-mer list in HBM on the databases' device, without the text: for every consumer
+ * (tbk_table_num_kmers, tbk_table_k, tbk_table_keys, tbk_classifier_create*, tbk_pipeline_create*, the other
+ * devices of a multi-device classifier) *out is what tbk_table_create_from_file gives on the file
+ * tbk_kmerdb_unique would have written - the same keys (tbk_kmer_to_int's packing) in the same, lexicographic,
+ * order, the same number of lines; tbk_table_origin says 3.  A's ranks ascend, so the selected ones are
+ * compacted in place order and nothing is sorted: three launches (one bit per entry of A and a count per tile of
+ * 1024 entries; a scan of the tile counts; the scatter, which turns each rank into its key), no block waiting
+ * for another.  The keys are allocated at their exact number once it is known; beside them the call takes
+ * n/8 + n/64 bytes for A's n entries, freed before it returns.  A different k or device is TBK_ERR_INVALID, as
+ * above.  An empty selection is TBK_ERR_FORMAT, "empty k-mer list", as an empty list file is.  TBK_ERR_NOMEM
+ * leaves both databases as they were and the device usable.  *out is NULL after every error. */
+int tbk_kmerdb_unique_table(const tbk_kmerdb *a, const tbk_kmerdb *b, uint32_t min_count, uint32_t max_count, tbk_table **out);
 
 /* Host threads the library starts for its own host-side work (list parsing, gzip members,
  * scoring): hardware threads limited by the CPU affinity mask and the cgroup CPU quota, divided by the

@@ -211,6 +211,8 @@ if HAS_KMERDB:
     _sig("tbk_kmerdb_histogram", C.c_int, _vp, _u64p)
     _sig("tbk_kmerdb_read", C.c_int, _vp, _u64, _u64, _vp, _vp)
     _sig("tbk_kmerdb_unique", C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, C.c_char_p, _u64p)
+    if hasattr(lib, "tbk_kmerdb_unique_table"):
+        _sig("tbk_kmerdb_unique_table", C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, C.POINTER(_vp))
 _sig("tbk_calib_gather", C.c_int, C.c_int, _u64, C.c_int, C.c_int, C.c_int, _u64, C.c_int, _dp, _dp)
 _sig("tbk_calib_atomics", C.c_int, C.c_int, _u64, C.c_int, C.c_int, _dp)
 if hasattr(lib, "tbk_calib_atomics64"):
@@ -307,13 +309,21 @@ def device_count() -> int:
     return n.value
 
 
+_warmed_up = False
+
+
 def warm_up() -> None:
     """Start the HIP runtime on the devices this process will use, on a thread of its own: the
     command-line drivers call this before they import numpy and parse their arguments, so that
     the runtime's start-up (device discovery, the primary context) runs beside those instead of
     after them.  Purely a head start - every entry point initialises what it needs anyway; without a
-    device it returns at once."""
+    device it returns at once.  Only the first call of a process does anything (the drivers import one another)."""
     import threading
+
+    global _warmed_up
+    if _warmed_up:
+        return
+    _warmed_up = True
 
     def start():
         n = C.c_int(0)

@@ -24,16 +24,52 @@ from . import _lib
 
 _lib.warm_up()  # the HIP runtime starts beside the imports and the argument parsing below
 
-from . import kmers, seq  # noqa: E402
+from . import find_unique_kmers as fu, kmers, seq  # noqa: E402
 
 # bases per batch handed to the GPU; 3 batches may be in flight
 _BATCH_BASES = int(os.environ.get("TBK_BATCH_BASES", str(64 << 20)))  # small enough that pinning the batch buffers is not what a short run waits for
 _BATCH_READS = int(os.environ.get("TBK_BATCH_READS", str(1 << 20)))
 
 
-def parse_args():
-    """Parse arguments (same positionals, options, defaults and help as the reference,
-    classify_by_kmers.py:14-54; the k-mer tables are built by the ``type=`` callbacks)."""
+class DatabasePair:
+    """Both parents given as count databases (``find-unique-kmers --keep-databases``): the paths and each parent's
+    cut-offs, settled from the files' headers alone.  ``load`` makes the two lists where the databases lie."""
+
+    def __init__(self, path_a: str, path_b: str, range_a: Tuple[int, int], range_b: Tuple[int, int]):
+        self.paths = {"A": path_a, "B": path_b}
+        self.ranges = {"A": range_a, "B": range_b}
+
+    def load(self) -> Tuple[kmers.HashSet, kmers.HashSet]:
+        """Each parent's k-mers with a counter in its range that the other parent does not hold, as the lists
+        find-unique-kmers would dump and ``create_kmer_hash_set`` read back - without the text.  Both databases are
+        closed before this returns: 9 bytes per kept k-mer must not stand beside the paired table."""
+        dbs, sets = {}, {}
+        try:
+            for hap in "AB":
+                print(f"Loading the k-mer database of haplotype {hap} from {self.paths[hap]}...", file=sys.stderr)
+                dbs[hap] = kmers.KmerDatabase.load(self.paths[hap])
+            for hap, other in ("AB", "BA"):
+                lo, hi = self.ranges[hap]
+                try:
+                    sets[hap] = dbs[hap].unique_set(dbs[other], lo, hi)
+                except ValueError as exc:
+                    if "empty k-mer list" not in str(exc):
+                        raise
+                    sys.exit(f"classify-by-kmers: haplotype {hap} has no k-mer with a count in [{lo},{hi}] that haplotype {other} lacks "
+                             f"({self.paths[hap]} minus {self.paths[other]}): nothing to classify by. Choose other cut-offs with "
+                             f"--min-count-{hap.lower()} and --max-count-{hap.lower()}.")
+                print(f"Found {sets[hap].num_kmers} {sets[hap].k}-mers unique to haplotype {hap} (in HBM on device {sets[hap].device}).", file=sys.stderr)
+        except BaseException:
+            for hs in sets.values():
+                hs.close()
+            raise
+        finally:
+            for db in dbs.values():
+                db.close()
+        return sets["A"], sets["B"]
+
+
+def _parser(kmer_list_type) -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         description=__doc__, formatter_class=argparse.ArgumentDefaultsHelpFormatter
     )
@@ -43,19 +79,80 @@ def parse_args():
     )
     parser.add_argument(
         "haplotype_a_kmers",
-        type=kmers.create_kmer_hash_set,
-        help="a list of k-mers unique to haplotype A, one per line",
+        type=kmer_list_type,
+        help="a list of k-mers unique to haplotype A, one per line; or the count database of that parent kept by "
+             "find-unique-kmers --keep-databases (*.tbkdb; then both parents must be databases)",
     )
     parser.add_argument(
         "haplotype_b_kmers",
-        type=kmers.create_kmer_hash_set,
-        help="a list of k-mers unique to haplotype B, one per line",
+        type=kmer_list_type,
+        help="a list of k-mers unique to haplotype B, one per line; or that parent's count database (*.tbkdb)",
     )
     parser.add_argument("--haplotype-a-out-prefix", default="hapA", help="prefix for haplotype A output file")
     parser.add_argument("--haplotype-b-out-prefix", default="hapB", help="prefix for haplotype B output file")
     parser.add_argument("--unclassified-out-prefix", default="unclassified", help="prefix for unclassified output file")
     parser.add_argument("--no-gzip-output", action="store_true", default=False, help="don't gzip the output")
-    return parser.parse_args()
+    for hap in "ab":
+        for bound in ("min", "max"):
+            parser.add_argument(
+                "--{}-count-{}".format(bound, hap), type=int, default=None, metavar="N",
+                help="count databases only: count cut-offs of haplotype {} chosen by hand (give both) instead of the ones "
+                     "find-unique-kmers would choose from its histogram".format(hap.upper()),
+            )
+    return parser
+
+
+def _settle_databases(args) -> DatabasePair:
+    """Everything about a pair of databases that their headers decide - the same k, each parent's cut-offs - before any
+    device is touched; every refusal is a message."""
+    paths = {"A": args.haplotype_a_kmers, "B": args.haplotype_b_kmers}
+    infos = {hap: kmers.database_file_info(paths[hap]) for hap in "AB"}
+    if infos["A"]["k"] != infos["B"]["k"]:
+        sys.exit("classify-by-kmers: {} holds {}-mers, but {} holds {}-mers".format(paths["A"], infos["A"]["k"], paths["B"], infos["B"]["k"]))
+    ranges = {}
+    for hap in "AB":
+        given = getattr(args, "min_count_" + hap.lower()), getattr(args, "max_count_" + hap.lower())
+        if given[0] is None:
+            # the rows find_unique_kmers.write_histogram would write of this database's histogram; no file is written
+            rows = [(c, 0 if c == 1 else int(infos[hap]["histogram"][c])) for c in range(1, 256)]
+            try:
+                given = fu.analyze_histogram(rows, paths[hap])
+            except fu.HistogramError:
+                sys.exit("classify-by-kmers: could not find min and max counts in the histogram of {} (haplotype {}). Choose cut-offs by "
+                         "hand and give them with --min-count-a, --max-count-a, --min-count-b and --max-count-b.".format(paths[hap], hap))
+        print("\033[92mUsing counts in range [{},{}].\033[0m".format(*given), file=sys.stderr)
+        ranges[hap] = (int(given[0]), int(given[1]))
+    return DatabasePair(paths["A"], paths["B"], ranges["A"], ranges["B"])
+
+
+def parse_args():
+    """Parse arguments (same positionals, options, defaults and help as the reference,
+    classify_by_kmers.py:14-54; the k-mer tables of text lists are built by the ``type=`` callbacks).
+
+    The command line is read twice.  The first reading takes the two k-mer arguments as the strings they are and decides
+    what they name: two text lists - then the second reading is the reference's, whose ``type=`` callbacks build the
+    tables - or two count databases, which are settled from their headers (``args.databases``) and loaded by ``main``."""
+    parser = _parser(str)
+    args = parser.parse_args()
+    is_db = [fu.is_database_path(args.haplotype_a_kmers), fu.is_database_path(args.haplotype_b_kmers)]
+    if is_db[0] != is_db[1]:
+        sys.exit("classify-by-kmers: {} is a {} and {} is a {}: give two k-mer lists or two count databases (*{})".format(
+            args.haplotype_a_kmers, "count database" if is_db[0] else "k-mer list", args.haplotype_b_kmers,
+            "count database" if is_db[1] else "k-mer list", fu.DATABASE_SUFFIX))
+    for hap in "ab":
+        lo, hi = getattr(args, "min_count_" + hap), getattr(args, "max_count_" + hap)
+        if (lo is None) != (hi is None):
+            parser.error("--min-count-{0} and --max-count-{0} go together".format(hap))
+        if lo is not None and not 1 <= lo <= hi:
+            parser.error("--min-count-{0} {1} --max-count-{0} {2}: need 1 <= min <= max".format(hap, lo, hi))
+        if lo is not None and not is_db[0]:
+            parser.error("--min-count-{0} and --max-count-{0} choose from a count database (*{1}); a k-mer list was given".format(hap, fu.DATABASE_SUFFIX))
+    if is_db[0]:
+        args.databases = _settle_databases(args)
+        return args
+    args = _parser(kmers.create_kmer_hash_set).parse_args()
+    args.databases = None
+    return args
 
 
 def calculate_scaling_factors(haplotype_a_kmers: kmers.HashSet, haplotype_b_kmers: kmers.HashSet) -> Tuple[float, float]:
@@ -93,6 +190,8 @@ def make_classifier(haplotype_a_kmers, haplotype_b_kmers):
 def main():
     """Main method of program"""
     args = parse_args()
+    if args.databases is not None:
+        args.haplotype_a_kmers, args.haplotype_b_kmers = args.databases.load()
 
     num_a = kmers.get_number_kmers_in_set(args.haplotype_a_kmers)
     num_b = kmers.get_number_kmers_in_set(args.haplotype_b_kmers)

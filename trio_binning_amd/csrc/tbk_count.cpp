@@ -994,3 +994,59 @@ extern "C" int tbk_kmerdb_unique(const tbk_kmerdb *a, const tbk_kmerdb *b, uint3
     *n_written = n;
     return TBK_OK;
 }
+
+// ---- the same subtraction as a k-mer list in HBM -------------------------------------------------------------------------
+extern "C" uint64_t tbk_kmerdb_table_tiles(uint64_t);
+extern "C" uint64_t tbk_kmerdb_table_flag_words(uint64_t);
+extern "C" hipError_t tbk_launch_kmerdb_flag(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, uint32_t, uint32_t, uint64_t *,
+                                             unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_kmerdb_scan(const unsigned long long *, unsigned long long *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_kmerdb_scatter(const uint64_t *, uint64_t, const uint64_t *, const unsigned long long *, int, uint64_t *, uint64_t,
+                                                hipStream_t);
+extern "C" int tbk_table_adopt_device_keys_(uint64_t *, uint64_t, int, int, int, tbk_table **);
+
+// What tbk_kmerdb_unique would write and tbk_table_create_from_file would read back, without the text in between: the
+// selection is flagged (one bit per entry of A, one count per tile), the tile counts are scanned, the list's keys are
+// allocated at their exact number and the flagged ranks go to their places as packed keys.  Beside the list this takes
+// a bit per entry of A and 16 bytes per tile of 1024 entries, freed before it returns.
+extern "C" int tbk_kmerdb_unique_table(const tbk_kmerdb *a, const tbk_kmerdb *b, uint32_t min_count, uint32_t max_count, tbk_table **out) {
+    if (!a || !b || !out) return cfail(TBK_ERR_INVALID, "NULL argument");
+    *out = nullptr;
+    if (a->k != b->k) return cfail(TBK_ERR_INVALID, "the databases have different k (%d and %d)", a->k, b->k);
+    if (a->device != b->device) return cfail(TBK_ERR_INVALID, "the databases live on different devices");
+    // upper bound of what can come out, as in tbk_kmerdb_unique: none in range means nothing to launch
+    uint64_t cap = 0;
+    for (uint32_t cnt = std::max<uint32_t>(2, min_count); cnt <= std::min<uint32_t>(255, max_count); cnt++) cap += a->hist[cnt];
+    cap = std::min(cap, a->n);
+    if (!cap) return cfail(TBK_ERR_FORMAT, "empty k-mer list");
+    const int rc = kmerdb_device(a->device);
+    if (rc) return rc;
+    const uint64_t tiles = tbk_kmerdb_table_tiles(a->n), words = tbk_kmerdb_table_flag_words(a->n);
+    uint64_t *d_flags = nullptr, *d_keys = nullptr;
+    unsigned long long *d_tiles = nullptr, total = 0;  // tiles + 1 counts (the last one 0), then their tiles + 1 offsets (the last one the total)
+    hipError_t e = hipMalloc((void **)&d_flags, words * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_tiles, 2 * (tiles + 1) * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(d_tiles + tiles, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = tbk_launch_kmerdb_flag(a->d_keys, a->d_counts, a->n, b->d_keys, b->n, min_count, max_count, d_flags, d_tiles, nullptr);
+    if (e == hipSuccess) e = tbk_launch_kmerdb_scan(d_tiles, d_tiles + tiles + 1, tiles + 1, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(&total, d_tiles + 2 * tiles + 1, sizeof total, hipMemcpyDeviceToHost);
+    const uint64_t n = std::min<uint64_t>(total, cap);  // (never more than the histogram allows: a list is not written past)
+    if (e == hipSuccess && n) e = hipMalloc((void **)&d_keys, n * sizeof(uint64_t));
+    if (e == hipSuccess && n) e = tbk_launch_kmerdb_scatter(a->d_keys, a->n, d_flags, d_tiles + tiles + 1, a->k, d_keys, n, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (d_flags) (void)hipFree(d_flags);
+    if (d_tiles) (void)hipFree(d_tiles);
+    if (e != hipSuccess) {
+        if (d_keys) (void)hipFree(d_keys);
+        (void)hipGetLastError();
+        return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "tbk_kmerdb_unique_table (%llu k-mers): %s", (unsigned long long)a->n, hipGetErrorString(e));
+    }
+    if (total > cap) {
+        if (d_keys) (void)hipFree(d_keys);
+        return cfail(TBK_ERR_HIP, "tbk_kmerdb_unique_table: %llu k-mers selected, the histogram allows %llu", total, (unsigned long long)cap);
+    }
+    if (!n) return cfail(TBK_ERR_FORMAT, "empty k-mer list");
+    const int made = tbk_table_adopt_device_keys_(d_keys, n, a->k, a->device, 3, out);
+    if (made) (void)hipFree(d_keys);
+    return made;
+}

@@ -1,6 +1,7 @@
 // tbk_count_kernels.hip — the MI355X kernels of the find-unique-kmers step: k-mer counting
 // into a table in HBM, its histogram, the A-minus-B selection.  Host side: tbk_count.cpp.
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_scan.hpp>
 #include <stdint.h>
 
 #include <type_traits>
@@ -563,6 +564,90 @@ tbk_kmerdb_unique_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__r
     }
 }
 
+// ---- the same subtraction, left in HBM as a k-mer list (tbk_kmerdb_unique_table) -------------------------------
+// A's ranks ascend, so the selected ones in their places ARE the dump's order: a stable compaction, no sort and no
+// buffer the size of the upper bound.  Three launches, no block ever waits for another: flag (one bit per entry,
+// one count per tile), an exclusive scan of the tile counts (rocPRIM), scatter.  A tile is TBK_DBT_TILE entries of
+// one block: round r of the block's wave w covers the 64 entries from tile * TILE + (r * 4 + w) * 64 on, and their
+// ballot is flag word tile * 16 + r * 4 + w - so bit j of flag word i belongs to entry 64 i + j.
+constexpr uint32_t TBK_DBT_TILE = 1024;                       // entries per tile: 4 rounds of a 256-thread block
+constexpr uint32_t TBK_DBT_WORDS = TBK_DBT_TILE / 64;         // flag words per tile
+
+// Selection of tbk_kmerdb_unique_kernel, kept as bits.  flags holds n_tiles * 16 words, tile_counts n_tiles.
+__global__ void __launch_bounds__(256)
+tbk_kmerdb_flag_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restrict__ a_counts, uint64_t n_a,
+                       const uint64_t *__restrict__ b_keys, uint64_t n_b, uint32_t ci, uint32_t cx,
+                       uint64_t *__restrict__ flags, unsigned long long *__restrict__ tile_counts) {
+    __shared__ uint32_t wave_count[TBK_DBT_WORDS];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t tile = blockIdx.x;
+    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
+        const uint32_t word = r * 4 + wave;
+        const uint64_t i = tile * TBK_DBT_TILE + (uint64_t)word * 64 + lane;
+        bool emit = false;
+        if (i < n_a) {
+            const uint64_t key = a_keys[i];
+            const uint32_t c = a_counts[i];
+            emit = c >= 2u && c >= ci && c <= cx;
+            if (emit) {
+                uint64_t lo = 0, hi = n_b;  // first element >= key
+                while (lo < hi) {
+                    const uint64_t mid = lo + (hi - lo) / 2;
+                    if (b_keys[mid] < key) lo = mid + 1; else hi = mid;
+                }
+                emit = !(lo < n_b && b_keys[lo] == key);
+            }
+        }
+        const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
+        if (lane == 0) {
+            flags[tile * TBK_DBT_WORDS + word] = mask;
+            wave_count[word] = (uint32_t)__popcll(mask);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (uint32_t w = 0; w < TBK_DBT_WORDS; w++) sum += wave_count[w];
+        tile_counts[tile] = sum;
+    }
+}
+
+// the key in the classifier's form (base i at bits 2i..2i+1, tbk_kmer_to_int) of a lexicographic rank: lex_rank's inverse
+__device__ __forceinline__ uint64_t key_of_rank(uint64_t rank, int k) {
+    const uint64_t lex = rank << (64 - 2 * k);  // (k = 32: a shift by 0)
+    return ((uint64_t)rev_pairs((uint32_t)lex) << 32) | (uint64_t)rev_pairs((uint32_t)(lex >> 32));
+}
+
+// Entry i of A goes to tile_offsets[its tile] + the flagged entries before it in the tile, converted on the way.
+__global__ void __launch_bounds__(256)
+tbk_kmerdb_scatter_kernel(const uint64_t *__restrict__ a_keys, uint64_t n_a, const uint64_t *__restrict__ flags,
+                          const unsigned long long *__restrict__ tile_offsets, int k, uint64_t *__restrict__ out, uint64_t n_out) {
+    __shared__ uint64_t word_mask[TBK_DBT_WORDS];
+    __shared__ uint32_t word_before[TBK_DBT_WORDS];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t tile = blockIdx.x;
+    if (threadIdx.x < TBK_DBT_WORDS) word_mask[threadIdx.x] = flags[tile * TBK_DBT_WORDS + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (uint32_t w = 0; w < TBK_DBT_WORDS; w++) {
+            word_before[w] = sum;
+            sum += (uint32_t)__popcll(word_mask[w]);
+        }
+    }
+    __syncthreads();
+    const uint64_t base = tile_offsets[tile];
+    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
+        const uint32_t word = r * 4 + wave;
+        const uint64_t mask = word_mask[word];
+        const uint64_t i = tile * TBK_DBT_TILE + (uint64_t)word * 64 + lane;
+        if (((mask >> lane) & 1ull) && i < n_a) {
+            const uint64_t at = base + word_before[word] + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+            if (at < n_out) out[at] = key_of_rank(a_keys[i], k);
+        }
+    }
+}
+
 // =======================================================================================
 // launchers (called from tbk_count.cpp)
 // =======================================================================================
@@ -698,5 +783,44 @@ extern "C" hipError_t tbk_launch_kmerdb_unique(const uint64_t *a_keys, const uin
     const uint64_t blocks = (n_a + 255) / 256;
     hipLaunchKernelGGL(tbk_kmerdb_unique_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, a_keys, a_counts, n_a, b_keys, n_b,
                        ci, cx, d_out, capacity, d_n);
+    return hipGetLastError();
+}
+
+// ---- tbk_kmerdb_unique_table: flag, scan, scatter ----------------------------------------------------------------
+extern "C" uint64_t tbk_kmerdb_table_tiles(uint64_t n_a) { return (n_a + TBK_DBT_TILE - 1) / TBK_DBT_TILE; }
+extern "C" uint64_t tbk_kmerdb_table_flag_words(uint64_t n_a) { return tbk_kmerdb_table_tiles(n_a) * TBK_DBT_WORDS; }
+
+// d_flags: tbk_kmerdb_table_flag_words(n_a) words; d_tile_counts: one per tile.  One block per tile: no grid stride.
+extern "C" hipError_t tbk_launch_kmerdb_flag(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *b_keys, uint64_t n_b,
+                                             uint32_t ci, uint32_t cx, uint64_t *d_flags, unsigned long long *d_tile_counts, hipStream_t stream) {
+    const uint64_t tiles = tbk_kmerdb_table_tiles(n_a);
+    if (!tiles) return hipSuccess;
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tbk_kmerdb_flag_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, a_counts, n_a, b_keys, n_b, ci, cx, d_flags,
+                       d_tile_counts);
+    return hipGetLastError();
+}
+
+// d_out[i] = d_in[0] + ... + d_in[i - 1], n elements; the caller passes one element more than it has tiles, so the last is the total
+extern "C" hipError_t tbk_launch_kmerdb_scan(const unsigned long long *d_in, unsigned long long *d_out, uint64_t n, hipStream_t stream) {
+    if (!n) return hipSuccess;
+    size_t tmp_bytes = 0;
+    void *d_tmp = nullptr;
+    hipError_t e = rocprim::exclusive_scan(nullptr, tmp_bytes, d_in, d_out, 0ull, (size_t)n, rocprim::plus<unsigned long long>(), stream);
+    if (e != hipSuccess) return e;
+    e = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16);
+    if (e != hipSuccess) return e;
+    e = rocprim::exclusive_scan(d_tmp, tmp_bytes, d_in, d_out, 0ull, (size_t)n, rocprim::plus<unsigned long long>(), stream);
+    const hipError_t e2 = hipStreamSynchronize(stream);
+    (void)hipFree(d_tmp);
+    return e != hipSuccess ? e : e2;
+}
+
+extern "C" hipError_t tbk_launch_kmerdb_scatter(const uint64_t *a_keys, uint64_t n_a, const uint64_t *d_flags, const unsigned long long *d_tile_offsets,
+                                                int k, uint64_t *d_out, uint64_t n_out, hipStream_t stream) {
+    const uint64_t tiles = tbk_kmerdb_table_tiles(n_a);
+    if (!tiles || !n_out) return hipSuccess;
+    if (tiles > 0x7FFFFFFFull || k < 1 || k > 32) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tbk_kmerdb_scatter_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, n_a, d_flags, d_tile_offsets, k, d_out, n_out);
     return hipGetLastError();
 }

@@ -313,7 +313,7 @@ struct tbk_table {
     int device = 0;
     int k = 0;
     uint64_t num_lines = 0;  // what the reference calls num_kmers (c/kmers.c:37)
-    int origin = 0;          // how the keys got here: 0 caller's keys / general host parser, 1 GPU parser, 2 binary key cache
+    int origin = 0;          // how the keys got here: 0 caller's keys / general host parser, 1 GPU parser, 2 binary key cache, 3 two count databases
     uint64_t *d_keys = nullptr;
     // lazily built standalone table
     uint64_t *d_slots = nullptr;
@@ -670,6 +670,17 @@ extern "C" int tbk_table_create_from_keys(const uint64_t *keys, uint64_t n, int 
     int rc = use_device(device);
     if (rc) return rc;
     return table_new(keys, false, n, k, n, device, out);
+}
+
+// (library-internal: tbk_count.cpp) A list around packed keys that already lie in device memory of `device`, n > 0 of them
+// in a hipMalloc'd block of exactly that size.  The block is the list's from here on; nothing is copied.
+extern "C" int tbk_table_adopt_device_keys_(uint64_t *d_keys, uint64_t n, int k, int device, int origin, tbk_table **out) {
+    if (!out || !d_keys || !n || k < 1 || k > 32) return fail(TBK_ERR_INVALID, "tbk_table_adopt_device_keys_: invalid argument");
+    tbk_table *t = new tbk_table();
+    t->device = device; t->k = k; t->num_lines = n; t->origin = origin;
+    t->d_keys = d_keys;
+    *out = t;
+    return TBK_OK;
 }
 
 // Text list -> packed keys with the reference's getline() rules (c/kmers.c:124-146,204-221):

@@ -133,8 +133,9 @@ class HashSet:
 
     @property
     def origin(self) -> str:
-        """Where the keys came from: "keys" (the caller's, or the general host parser), "gpu-parser", "cache"."""
-        return {0: "keys", 1: "gpu-parser", 2: "cache"}.get(lib.tbk_table_origin(self._h), "?")
+        """Where the keys came from: "keys" (the caller's, or the general host parser), "gpu-parser", "cache", "databases"
+        (``KmerDatabase.unique_set``)."""
+        return {0: "keys", 1: "gpu-parser", 2: "cache", 3: "databases"}.get(lib.tbk_table_origin(self._h), "?")
 
     def keys(self) -> np.ndarray:
         """The packed keys, one per list line, copied to the host."""
@@ -964,6 +965,14 @@ class KmerDatabase:
         n = C.c_uint64()
         check(lib.tbk_kmerdb_unique(self._h, other._h, min_count, max_count, os.fsencode(out_path), C.byref(n)))
         return n.value
+
+    def unique_set(self, other: "KmerDatabase", min_count: int, max_count: int) -> HashSet:
+        """The list ``unique`` would write, as the ``HashSet`` ``create_kmer_hash_set`` would make of that file - the same keys
+        in the same order - without the text in between (``tbk_kmerdb_unique_table``): selected, compacted and packed where
+        the databases lie.  ``ValueError`` ("empty k-mer list") when nothing is selected, as for an empty list file."""
+        h = C.c_void_p()
+        check(lib.tbk_kmerdb_unique_table(self._h, other._h, min_count, max_count, C.byref(h)))
+        return HashSet(h.value)
 
     def close(self) -> None:
         if self._h is not None and self._h.value:
