@@ -748,6 +748,23 @@ int tbk_kmerdb_unique(const tbk_kmerdb *a, const tbk_kmerdb *b, uint32_t min_cou
  * above.  An empty selection is TBK_ERR_FORMAT, "empty k-mer list", as an empty list file is.  TBK_ERR_NOMEM
  * leaves both databases as they were and the device usable.  *out is NULL after every error. */
 int tbk_kmerdb_unique_table(const tbk_kmerdb *a, const tbk_kmerdb *b, uint32_t min_count, uint32_t max_count, tbk_table **out);
+/* The same two calls with a third database, the child's: of the k-mers above (counter of `a` in [max(2, min_count),
+ * min(255, max_count)], not held by `b`) only those that `child` holds with a counter in [max(2, child_min),
+ * min(255, child_max)] - the parental k-mers the child inherited.  A child database, like any other, holds only
+ * k-mers seen at least twice.  tbk_kmerdb_inherited writes the file tbk_kmerdb_unique would write for that set
+ * (lexicographic, one k-mer per line; an empty selection is an empty file and TBK_OK); the set comes compacted in
+ * A's order, so nothing is sorted and no buffer is larger than the list.  tbk_kmerdb_inherited_table leaves it as
+ * the list tbk_kmerdb_unique_table would make of that set: the same order and key form, tbk_table_origin 3, an
+ * empty selection TBK_ERR_FORMAT "empty k-mer list".  One block flags a tile of 1024 entries of A: it first finds
+ * where the tile's first and last rank would stand in `b` and in `child`, and each entry then searches between
+ * those places only, `b` before `child`.  Beside the output both calls take n/8 + n/64 bytes for A's n entries,
+ * freed before they return.  A NULL database, a different k or a different device among the three is
+ * TBK_ERR_INVALID; TBK_ERR_NOMEM leaves all three databases as they were and the device usable; *out is NULL after
+ * every error. */
+int tbk_kmerdb_inherited(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kmerdb *child, uint32_t min_count, uint32_t max_count,
+                         uint32_t child_min, uint32_t child_max, const char *out_path, uint64_t *n_written);
+int tbk_kmerdb_inherited_table(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kmerdb *child, uint32_t min_count, uint32_t max_count,
+                               uint32_t child_min, uint32_t child_max, tbk_table **out);
 
 /* Host threads the library starts for its own host-side work (list parsing, gzip members,
  * scoring): hardware threads limited by the CPU affinity mask and the cgroup CPU quota, divided by the

@@ -10,14 +10,28 @@ bracketed with a device synchronisation:
   direct  KmerDatabase.unique_set() (tbk_kmerdb_unique_table: flag, scan, scatter in HBM).
 
 Both must give the same keys; the record also says how many bytes of text the direct route never writes or reads.
-Prints one JSON line; --out writes it to a file too."""
-import argparse, ctypes as C, json, os, struct, sys, time, zlib
+Prints one JSON line; --out writes it to a file too.
+
+--inherited measures the three-database selection instead (tbk_kmerdb_inherited_table), on the same A and B and a third
+crafted database of --n ranks: the child holds every second k-mer of A that unique_set(b) selects and, in place of every
+other entry of A, the rank above it; counters uniform in 2..40, the child's range [2,255].  Timed alternately after a warm-up:
+
+  unique_set   today's KmerDatabase.unique_set(b) on A and B, the same-box yardstick;
+  inherited    KmerDatabase.unique_set(b, child=child).
+
+The inherited keys must be every second key of unique_set's.  --full-depth-library names a variant of the library whose
+flag kernel bisects the whole of B and of the child for every entry (VARIANT_SRC=tbk_count_kernels tools/build_variant.sh
+inherited_full -DTBK_INHERITED_FULL_DEPTH): the same measurement is repeated with it in a fresh process, after this one's
+databases are closed, and joins the record as "full_depth"."""
+import argparse, ctypes as C, json, os, struct, subprocess, sys, time, zlib
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=100_000_000)
 ap.add_argument("-k", type=int, default=21)
 ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--tmp", default="/dev/shm")
 ap.add_argument("--out", default="")
+ap.add_argument("--inherited", action="store_true")
+ap.add_argument("--full-depth-library", default="")
 a = ap.parse_args()
 os.environ["TBK_LIST_CACHE"] = "0"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -51,18 +65,63 @@ paths = [os.path.join(a.tmp, "tbk_handoff_%d_%s.tbkdb" % (os.getpid(), h)) for h
 text_path = os.path.join(a.tmp, "tbk_handoff_%d.txt" % os.getpid())
 out = {"k": k, "n_per_database": n, "cutoffs": [LO, HI], "runs": a.runs}
 try:
-    write_db(paths[0], keys_a, rng.integers(2, 41, n).astype(np.uint8))
+    counts_a = rng.integers(2, 41, n).astype(np.uint8)
+    write_db(paths[0], keys_a, counts_a)
     write_db(paths[1], keys_b, rng.integers(2, 41, n).astype(np.uint8))
-    del keys_a, keys_b
+    if a.inherited:
+        selected = (counts_a >= LO) & (counts_a <= HI) & (np.arange(n, dtype=np.uint64) % np.uint64(4) != 0)
+        held = selected & (np.cumsum(selected) % 2 == 1)  # the 1st, 3rd, ... selected entry of A
+        paths.append(paths[0].replace("_a.tbkdb", "_child.tbkdb"))
+        write_db(paths[2], keys_a + (~held).astype(np.uint64), rng.integers(2, 41, n).astype(np.uint8))
+        out["selected"], out["held_by_child"] = int(selected.sum()), int(held.sum())
+        del selected, held
+    del keys_a, keys_b, counts_a
     out["craft_s"] = round(time.time() - t, 2)
     t = time.time()
     da, db = kmers.KmerDatabase.load(paths[0]), kmers.KmerDatabase.load(paths[1])
     out["load_both_s"] = round(time.time() - t, 2)
-    for p in paths:
+    for p in paths[:2]:
         os.remove(p)
 
     def sync():
         check(lib.tbk_device_sync(dev))
+
+    if a.inherited:
+        dc = kmers.KmerDatabase.load(paths[2])
+        os.remove(paths[2])
+        legs = {"unique_set": [], "inherited": []}
+        for run in range(a.runs + 1):  # run 0 warms up
+            for name, child in (("unique_set", {}), ("inherited", {"child": dc, "child_min": 2, "child_max": 255})):
+                sync(); t0 = time.time()
+                hs = da.unique_set(db, LO, HI, **child)
+                sync(); t1 = time.time()
+                if run == 0:
+                    legs[name + "_keys"] = hs.keys()
+                else:
+                    legs[name].append(round(t1 - t0, 5))
+                hs.close()
+        two, three = legs.pop("unique_set_keys"), legs.pop("inherited_keys")
+        same = two.size == out["selected"] and np.array_equal(three, two[::2])
+        del two, three
+        da.close(); db.close(); dc.close()
+        med = lambda rows: sorted(rows)[len(rows) // 2]
+        out.update({"same_keys": bool(same), "library": os.path.basename(os.environ.get("TBK_LIBRARY", "")), "device": kmers._lib.device_name(dev),
+                    "unique_set_s": med(legs["unique_set"]), "inherited_s": med(legs["inherited"]),
+                    "unique_set_all_s": legs["unique_set"], "inherited_all_s": legs["inherited"]})
+        out["inherited_over_unique_set"] = round(out["inherited_s"] / out["unique_set_s"], 2)
+        if a.full_depth_library and same:
+            cmd = [sys.executable, os.path.abspath(__file__), "--inherited", "--n", str(n), "-k", str(k), "--runs", str(a.runs), "--tmp", a.tmp]
+            done = subprocess.run(cmd, env=dict(os.environ, TBK_LIBRARY=os.path.abspath(a.full_depth_library)), stdout=subprocess.PIPE, timeout=600)
+            out["full_depth"] = json.loads(done.stdout.decode().strip().splitlines()[-1]) if done.returncode == 0 else {"returncode": done.returncode}
+            if done.returncode == 0:
+                out["full_depth_over_bounded"] = round(out["full_depth"]["inherited_s"] / out["inherited_s"], 2)
+        line = json.dumps(out)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                fh.write(line + "\n")
+        sys.exit(0 if same and out.get("full_depth", {}).get("same_keys", True) else 1)
 
     def text_route():
         sync(); t0 = time.time()

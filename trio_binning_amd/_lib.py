@@ -213,6 +213,9 @@ if HAS_KMERDB:
     _sig("tbk_kmerdb_unique", C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, C.c_char_p, _u64p)
     if hasattr(lib, "tbk_kmerdb_unique_table"):
         _sig("tbk_kmerdb_unique_table", C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, C.POINTER(_vp))
+    if hasattr(lib, "tbk_kmerdb_inherited"):
+        _sig("tbk_kmerdb_inherited", C.c_int, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, _u64p)
+        _sig("tbk_kmerdb_inherited_table", C.c_int, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp))
 _sig("tbk_calib_gather", C.c_int, C.c_int, _u64, C.c_int, C.c_int, C.c_int, _u64, C.c_int, _dp, _dp)
 _sig("tbk_calib_atomics", C.c_int, C.c_int, _u64, C.c_int, C.c_int, _dp)
 if hasattr(lib, "tbk_calib_atomics64"):

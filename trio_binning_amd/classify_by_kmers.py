@@ -18,7 +18,7 @@ import argparse
 import os
 import sys
 from os import path
-from typing import Tuple
+from typing import Optional, Tuple
 
 from . import _lib
 
@@ -33,32 +33,47 @@ _BATCH_READS = int(os.environ.get("TBK_BATCH_READS", str(1 << 20)))
 
 class DatabasePair:
     """Both parents given as count databases (``find-unique-kmers --keep-databases``): the paths and each parent's
-    cut-offs, settled from the files' headers alone.  ``load`` makes the two lists where the databases lie."""
+    cut-offs, settled from the files' headers alone.  ``load`` makes the two lists where the databases lie.  With the child's
+    database (``child_path``, its counts from ``child_min`` on) the lists hold only what the child inherited."""
 
-    def __init__(self, path_a: str, path_b: str, range_a: Tuple[int, int], range_b: Tuple[int, int]):
+    def __init__(self, path_a: str, path_b: str, range_a: Tuple[int, int], range_b: Tuple[int, int],
+                 child_path: Optional[str] = None, child_min: int = 2):
         self.paths = {"A": path_a, "B": path_b}
         self.ranges = {"A": range_a, "B": range_b}
+        self.child_path, self.child_min = child_path, child_min
 
     def load(self) -> Tuple[kmers.HashSet, kmers.HashSet]:
         """Each parent's k-mers with a counter in its range that the other parent does not hold, as the lists
-        find-unique-kmers would dump and ``create_kmer_hash_set`` read back - without the text.  Both databases are
-        closed before this returns: 9 bytes per kept k-mer must not stand beside the paired table."""
+        find-unique-kmers would dump and ``create_kmer_hash_set`` read back - without the text; with a child, those of them
+        that the child holds too.  All databases are closed before this returns: 9 bytes per kept k-mer must not stand beside
+        the paired table."""
         dbs, sets = {}, {}
         try:
             for hap in "AB":
                 print(f"Loading the k-mer database of haplotype {hap} from {self.paths[hap]}...", file=sys.stderr)
                 dbs[hap] = kmers.KmerDatabase.load(self.paths[hap])
+            third = {}
+            if self.child_path is not None:
+                print(f"Loading the k-mer database of the child from {self.child_path}...", file=sys.stderr)
+                dbs["child"] = kmers.KmerDatabase.load(self.child_path)
+                third = {"child": dbs["child"], "child_min": self.child_min, "child_max": 255}
             for hap, other in ("AB", "BA"):
                 lo, hi = self.ranges[hap]
                 try:
-                    sets[hap] = dbs[hap].unique_set(dbs[other], lo, hi)
+                    sets[hap] = dbs[hap].unique_set(dbs[other], lo, hi, **third)
                 except ValueError as exc:
                     if "empty k-mer list" not in str(exc):
                         raise
+                    if third:
+                        sys.exit(f"classify-by-kmers: haplotype {hap} has no k-mer with a count in [{lo},{hi}] that haplotype {other} lacks "
+                                 f"and the child holds with a count in [{self.child_min},255] ({self.paths[hap]} minus {self.paths[other]}, "
+                                 f"within {self.child_path}): nothing to classify by. Choose other cut-offs with --min-count-{hap.lower()}, "
+                                 f"--max-count-{hap.lower()} and --min-count-child.")
                     sys.exit(f"classify-by-kmers: haplotype {hap} has no k-mer with a count in [{lo},{hi}] that haplotype {other} lacks "
                              f"({self.paths[hap]} minus {self.paths[other]}): nothing to classify by. Choose other cut-offs with "
                              f"--min-count-{hap.lower()} and --max-count-{hap.lower()}.")
-                print(f"Found {sets[hap].num_kmers} {sets[hap].k}-mers unique to haplotype {hap} (in HBM on device {sets[hap].device}).", file=sys.stderr)
+                found = "unique to haplotype {} and inherited by the child".format(hap) if third else "unique to haplotype {}".format(hap)
+                print(f"Found {sets[hap].num_kmers} {sets[hap].k}-mers {found} (in HBM on device {sets[hap].device}).", file=sys.stderr)
         except BaseException:
             for hs in sets.values():
                 hs.close()
@@ -99,16 +114,32 @@ def _parser(kmer_list_type) -> argparse.ArgumentParser:
                 help="count databases only: count cut-offs of haplotype {} chosen by hand (give both) instead of the ones "
                      "find-unique-kmers would choose from its histogram".format(hap.upper()),
             )
+    parser.add_argument(
+        "--child-database", default=None, metavar="child.tbkdb",
+        help="count databases only: the child's count database (find-unique-kmers --child ... --keep-databases). The reads are "
+             "then classified by the parental k-mers the child inherited alone: those this database holds too",
+    )
+    parser.add_argument(
+        "--min-count-child", type=int, default=None, metavar="N",
+        help="with --child-database: the child's lower count cut-off chosen by hand instead of the one find-unique-kmers would "
+             "choose from its histogram (the upper one is 255)",
+    )
     return parser
 
 
 def _settle_databases(args) -> DatabasePair:
-    """Everything about a pair of databases that their headers decide - the same k, each parent's cut-offs - before any
-    device is touched; every refusal is a message."""
+    """Everything about a pair of databases, and the child's beside them, that their headers decide - the same k, each
+    library's cut-offs - before any device is touched; every refusal is a message."""
     paths = {"A": args.haplotype_a_kmers, "B": args.haplotype_b_kmers}
     infos = {hap: kmers.database_file_info(paths[hap]) for hap in "AB"}
     if infos["A"]["k"] != infos["B"]["k"]:
         sys.exit("classify-by-kmers: {} holds {}-mers, but {} holds {}-mers".format(paths["A"], infos["A"]["k"], paths["B"], infos["B"]["k"]))
+    child_info = None
+    if args.child_database is not None:
+        child_info = kmers.database_file_info(args.child_database)
+        if child_info["k"] != infos["A"]["k"]:
+            sys.exit("classify-by-kmers: {} holds {}-mers, but {} holds {}-mers".format(
+                paths["A"], infos["A"]["k"], args.child_database, child_info["k"]))
     ranges = {}
     for hap in "AB":
         given = getattr(args, "min_count_" + hap.lower()), getattr(args, "max_count_" + hap.lower())
@@ -122,6 +153,17 @@ def _settle_databases(args) -> DatabasePair:
                          "hand and give them with --min-count-a, --max-count-a, --min-count-b and --max-count-b.".format(paths[hap], hap))
         print("\033[92mUsing counts in range [{},{}].\033[0m".format(*given), file=sys.stderr)
         ranges[hap] = (int(given[0]), int(given[1]))
+    child_min = args.min_count_child
+    if child_info is not None and child_min is None:
+        rows = [(c, 0 if c == 1 else int(child_info["histogram"][c])) for c in range(1, 256)]
+        try:
+            child_min = fu.analyze_histogram(rows, args.child_database)[0]  # (its maximum is not used)
+        except fu.HistogramError:
+            sys.exit("classify-by-kmers: could not find the minimum count in the histogram of {} (the child). Choose it by hand and "
+                     "give it with --min-count-child.".format(args.child_database))
+    if child_info is not None:
+        print("\033[92mUsing counts in range [{},255] for the child.\033[0m".format(child_min), file=sys.stderr)
+        return DatabasePair(paths["A"], paths["B"], ranges["A"], ranges["B"], args.child_database, int(child_min))
     return DatabasePair(paths["A"], paths["B"], ranges["A"], ranges["B"])
 
 
@@ -147,6 +189,14 @@ def parse_args():
             parser.error("--min-count-{0} {1} --max-count-{0} {2}: need 1 <= min <= max".format(hap, lo, hi))
         if lo is not None and not is_db[0]:
             parser.error("--min-count-{0} and --max-count-{0} choose from a count database (*{1}); a k-mer list was given".format(hap, fu.DATABASE_SUFFIX))
+    if args.child_database is not None and not is_db[0]:
+        parser.error("--child-database selects from two count databases (*{}); k-mer lists were given".format(fu.DATABASE_SUFFIX))
+    if args.child_database is not None and not fu.is_database_path(args.child_database):
+        parser.error("--child-database {} is not a count database (*{})".format(args.child_database, fu.DATABASE_SUFFIX))
+    if args.min_count_child is not None and args.child_database is None:
+        parser.error("--min-count-child chooses from the child's counts: give --child-database too")
+    if args.min_count_child is not None and args.min_count_child < 1:
+        parser.error("--min-count-child {}: need 1 <= min".format(args.min_count_child))
     if is_db[0]:
         args.databases = _settle_databases(args)
         return args

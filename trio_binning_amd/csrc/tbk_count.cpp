@@ -1050,3 +1050,109 @@ extern "C" int tbk_kmerdb_unique_table(const tbk_kmerdb *a, const tbk_kmerdb *b,
     if (made) (void)hipFree(d_keys);
     return made;
 }
+
+// ---- three databases: what the child inherited of A's own k-mers --------------------------------------------------------
+extern "C" hipError_t tbk_launch_kmerdb_inherited_flag(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, const uint64_t *,
+                                                       const uint8_t *, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t *,
+                                                       unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_kmerdb_scatter_ranks(const uint64_t *, uint64_t, const uint64_t *, const unsigned long long *, uint64_t *, uint64_t,
+                                                      hipStream_t);
+
+static int inherited_check(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kmerdb *child) {
+    if (a->k != b->k || a->k != child->k)
+        return cfail(TBK_ERR_INVALID, "the databases have different k (%d, %d and the child's %d)", a->k, b->k, child->k);
+    if (a->device != b->device || a->device != child->device) return cfail(TBK_ERR_INVALID, "the databases live on different devices");
+    return TBK_OK;
+}
+
+// The k-mers of `a` with a counter in range that `b` lacks and `child` holds with a counter in its range, compacted in
+// A's order at their exact number: packed keys (as_keys) or ranks.  *n_out = 0 and *d_out = NULL when none is selected.
+// Flag, scan and scatter as in tbk_kmerdb_unique_table, with the same n/8 + n/64 bytes beside the output.
+static int inherited_select(const char *who, const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kmerdb *child, uint32_t min_count,
+                            uint32_t max_count, uint32_t child_min, uint32_t child_max, bool as_keys, uint64_t **d_out, uint64_t *n_out) {
+    *d_out = nullptr;
+    *n_out = 0;
+    // upper bound of what can come out: A's k-mers in range, and no more than the child holds in its own
+    uint64_t cap = 0, child_cap = 0;
+    for (uint32_t cnt = std::max<uint32_t>(2, min_count); cnt <= std::min<uint32_t>(255, max_count); cnt++) cap += a->hist[cnt];
+    for (uint32_t cnt = std::max<uint32_t>(2, child_min); cnt <= std::min<uint32_t>(255, child_max); cnt++) child_cap += child->hist[cnt];
+    cap = std::min(std::min(cap, a->n), std::min(child_cap, child->n));
+    if (!cap) return TBK_OK;
+    const int rc = kmerdb_device(a->device);
+    if (rc) return rc;
+    const uint64_t tiles = tbk_kmerdb_table_tiles(a->n), words = tbk_kmerdb_table_flag_words(a->n);
+    uint64_t *d_flags = nullptr, *d_sel = nullptr;
+    unsigned long long *d_tiles = nullptr, total = 0;  // tiles + 1 counts (the last one 0), then their tiles + 1 offsets (the last one the total)
+    hipError_t e = hipMalloc((void **)&d_flags, words * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_tiles, 2 * (tiles + 1) * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(d_tiles + tiles, 0, sizeof(unsigned long long));
+    if (e == hipSuccess)
+        e = tbk_launch_kmerdb_inherited_flag(a->d_keys, a->d_counts, a->n, b->d_keys, b->n, child->d_keys, child->d_counts, child->n, min_count,
+                                             max_count, child_min, child_max, d_flags, d_tiles, nullptr);
+    if (e == hipSuccess) e = tbk_launch_kmerdb_scan(d_tiles, d_tiles + tiles + 1, tiles + 1, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(&total, d_tiles + 2 * tiles + 1, sizeof total, hipMemcpyDeviceToHost);
+    const uint64_t n = std::min<uint64_t>(total, cap);  // (never more than the histograms allow: nothing is written past)
+    if (e == hipSuccess && n) e = hipMalloc((void **)&d_sel, n * sizeof(uint64_t));
+    if (e == hipSuccess && n)
+        e = as_keys ? tbk_launch_kmerdb_scatter(a->d_keys, a->n, d_flags, d_tiles + tiles + 1, a->k, d_sel, n, nullptr)
+                    : tbk_launch_kmerdb_scatter_ranks(a->d_keys, a->n, d_flags, d_tiles + tiles + 1, d_sel, n, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (d_flags) (void)hipFree(d_flags);
+    if (d_tiles) (void)hipFree(d_tiles);
+    if (e != hipSuccess) {
+        if (d_sel) (void)hipFree(d_sel);
+        (void)hipGetLastError();
+        return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "%s (%llu k-mers): %s", who, (unsigned long long)a->n, hipGetErrorString(e));
+    }
+    if (total > cap) {
+        if (d_sel) (void)hipFree(d_sel);
+        return cfail(TBK_ERR_HIP, "%s: %llu k-mers selected, the histograms allow %llu", who, total, (unsigned long long)cap);
+    }
+    *d_out = d_sel;
+    *n_out = n;
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_inherited(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kmerdb *child, uint32_t min_count, uint32_t max_count,
+                                    uint32_t child_min, uint32_t child_max, const char *out_path, uint64_t *n_written) {
+    if (!a || !b || !child || !out_path || !n_written) return cfail(TBK_ERR_INVALID, "NULL argument");
+    *n_written = 0;
+    int rc = inherited_check(a, b, child);
+    if (rc) return rc;
+    uint64_t *d_ranks = nullptr, n = 0;
+    rc = inherited_select("tbk_kmerdb_inherited", a, b, child, min_count, max_count, child_min, child_max, false, &d_ranks, &n);
+    if (rc) return rc;
+    std::vector<uint64_t> h_keys;
+    if (n) {
+        // (in A's order already: nothing to sort, and no buffer larger than the list)
+        h_keys.resize(n);
+        const hipError_t e = hipMemcpy(h_keys.data(), d_ranks, n * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        (void)hipFree(d_ranks);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return cfail(TBK_ERR_HIP, "tbk_kmerdb_inherited: %s", hipGetErrorString(e));
+        }
+    }
+    std::string err;
+    if (!write_list(out_path, h_keys.data(), n, a->k, err)) return cfail(TBK_ERR_IO, "%s", err.c_str());
+    *n_written = n;
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_inherited_table(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kmerdb *child, uint32_t min_count,
+                                          uint32_t max_count, uint32_t child_min, uint32_t child_max, tbk_table **out) {
+    if (out) *out = nullptr;
+    if (!a || !b || !child || !out) return cfail(TBK_ERR_INVALID, "NULL argument");
+    int rc = inherited_check(a, b, child);
+    if (rc) return rc;
+    uint64_t *d_keys = nullptr, n = 0;
+    rc = inherited_select("tbk_kmerdb_inherited_table", a, b, child, min_count, max_count, child_min, child_max, true, &d_keys, &n);
+    if (rc) return rc;
+    if (!n) return cfail(TBK_ERR_FORMAT, "empty k-mer list");
+    const int made = tbk_table_adopt_device_keys_(d_keys, n, a->k, a->device, 3, out);
+    if (made) {
+        (void)hipFree(d_keys);
+        *out = nullptr;
+    }
+    return made;
+}

@@ -648,6 +648,106 @@ tbk_kmerdb_scatter_kernel(const uint64_t *__restrict__ a_keys, uint64_t n_a, con
     }
 }
 
+// ---- three databases: the k-mers of A that B lacks and the child holds (tbk_kmerdb_inherited) -------------------
+// first element >= key among keys[lo .. hi), which ascend: hi when there is none
+__device__ __forceinline__ uint64_t db_lower_bound(const uint64_t *__restrict__ keys, uint64_t lo, uint64_t hi, uint64_t key) {
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// The flags and tile counts of tbk_kmerdb_flag_kernel for the three-way selection: counter of A in [ci, cx], not among
+// B's ranks, among the child's with a counter in [hi_ci, hi_cx] there.  A's ranks ascend within the tile, so every
+// entry's lower bound in B lies between those of the tile's first and last entry (i < n_a), and likewise in the child:
+// threads 0..3 find these four by bisection over the whole partner and leave them in LDS; after the one barrier an
+// entry in range bisects between its tile's two bounds only - about log2(tile * n_b / n_a) dependent loads, on lines
+// the block shares.  Equal bounds mean that nothing of the partner lies inside the tile's span: the search is then
+// no load at all, and the one comparison after it settles the entry.  B first; the child only for what B left.
+__global__ void __launch_bounds__(256)
+tbk_kmerdb_inherited_flag_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restrict__ a_counts, uint64_t n_a,
+                                 const uint64_t *__restrict__ b_keys, uint64_t n_b, const uint64_t *__restrict__ h_keys,
+                                 const uint8_t *__restrict__ h_counts, uint64_t n_h, uint32_t ci, uint32_t cx, uint32_t h_ci, uint32_t h_cx,
+                                 uint64_t *__restrict__ flags, unsigned long long *__restrict__ tile_counts) {
+    __shared__ uint64_t bound[4];  // B: first, last; child: first, last
+    __shared__ uint32_t tile_sum;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t tile = blockIdx.x;
+    const uint64_t first = tile * TBK_DBT_TILE;  // (< n_a: one block per tile of A)
+    if (threadIdx.x < 4) {
+#ifdef TBK_INHERITED_FULL_DEPTH  // (measurement only, tools/build_variant.sh: every entry bisects the whole partner)
+        bound[threadIdx.x] = (threadIdx.x & 1u) ? ((threadIdx.x & 2u) ? n_h : n_b) : 0;
+#else
+        const uint64_t last = (n_a - first < TBK_DBT_TILE ? n_a : first + TBK_DBT_TILE) - 1;
+        const uint64_t key = a_keys[(threadIdx.x & 1u) ? last : first];
+        bound[threadIdx.x] = (threadIdx.x & 2u) ? db_lower_bound(h_keys, 0, n_h, key) : db_lower_bound(b_keys, 0, n_b, key);
+#endif
+    }
+    if (threadIdx.x == 0) tile_sum = 0;
+    __syncthreads();
+    const uint64_t b_lo = bound[0], b_hi = bound[1], h_lo = bound[2], h_hi = bound[3];
+    uint32_t mine = 0;  // (the same in every lane of a wave)
+    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
+        const uint32_t word = r * 4 + wave;
+        const uint64_t i = first + (uint64_t)word * 64 + lane;
+        bool emit = false;
+        if (i < n_a) {
+            const uint64_t key = a_keys[i];
+            const uint32_t c = a_counts[i];
+            emit = c >= 2u && c >= ci && c <= cx;
+            if (emit) {
+                const uint64_t at = db_lower_bound(b_keys, b_lo, b_hi, key);  // (at <= b_hi <= n_b)
+                emit = !(at < n_b && b_keys[at] == key);
+            }
+            if (emit) {
+                const uint64_t at = db_lower_bound(h_keys, h_lo, h_hi, key);
+                emit = at < n_h && h_keys[at] == key;
+                if (emit) {
+                    const uint32_t hc = h_counts[at];
+                    emit = hc >= 2u && hc >= h_ci && hc <= h_cx;
+                }
+            }
+        }
+        const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
+        if (lane == 0) flags[tile * TBK_DBT_WORDS + word] = mask;
+        mine += (uint32_t)__popcll(mask);
+    }
+    if (lane == 0 && mine) atomicAdd(&tile_sum, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) tile_counts[tile] = tile_sum;
+}
+
+// tbk_kmerdb_scatter_kernel for a list that goes to a file: the flagged ranks as they are (write_list takes ranks).
+__global__ void __launch_bounds__(256)
+tbk_kmerdb_scatter_ranks_kernel(const uint64_t *__restrict__ a_keys, uint64_t n_a, const uint64_t *__restrict__ flags,
+                                const unsigned long long *__restrict__ tile_offsets, uint64_t *__restrict__ out, uint64_t n_out) {
+    __shared__ uint64_t word_mask[TBK_DBT_WORDS];
+    __shared__ uint32_t word_before[TBK_DBT_WORDS];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t tile = blockIdx.x;
+    if (threadIdx.x < TBK_DBT_WORDS) word_mask[threadIdx.x] = flags[tile * TBK_DBT_WORDS + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (uint32_t w = 0; w < TBK_DBT_WORDS; w++) {
+            word_before[w] = sum;
+            sum += (uint32_t)__popcll(word_mask[w]);
+        }
+    }
+    __syncthreads();
+    const uint64_t base = tile_offsets[tile];
+    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
+        const uint32_t word = r * 4 + wave;
+        const uint64_t mask = word_mask[word];
+        const uint64_t i = tile * TBK_DBT_TILE + (uint64_t)word * 64 + lane;
+        if (((mask >> lane) & 1ull) && i < n_a) {
+            const uint64_t at = base + word_before[word] + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+            if (at < n_out) out[at] = a_keys[i];
+        }
+    }
+}
+
 // =======================================================================================
 // launchers (called from tbk_count.cpp)
 // =======================================================================================
@@ -822,5 +922,28 @@ extern "C" hipError_t tbk_launch_kmerdb_scatter(const uint64_t *a_keys, uint64_t
     if (!tiles || !n_out) return hipSuccess;
     if (tiles > 0x7FFFFFFFull || k < 1 || k > 32) return hipErrorInvalidValue;
     hipLaunchKernelGGL(tbk_kmerdb_scatter_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, n_a, d_flags, d_tile_offsets, k, d_out, n_out);
+    return hipGetLastError();
+}
+
+// ---- tbk_kmerdb_inherited: its own flag kernel, then the scan above and one of the two scatters ------------------
+// d_flags and d_tile_counts as for tbk_launch_kmerdb_flag; the child's arrays may be NULL when n_h is 0 (as B's when n_b is)
+extern "C" hipError_t tbk_launch_kmerdb_inherited_flag(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *b_keys,
+                                                       uint64_t n_b, const uint64_t *h_keys, const uint8_t *h_counts, uint64_t n_h, uint32_t ci,
+                                                       uint32_t cx, uint32_t h_ci, uint32_t h_cx, uint64_t *d_flags,
+                                                       unsigned long long *d_tile_counts, hipStream_t stream) {
+    const uint64_t tiles = tbk_kmerdb_table_tiles(n_a);
+    if (!tiles) return hipSuccess;
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tbk_kmerdb_inherited_flag_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, a_counts, n_a, b_keys, n_b, h_keys,
+                       h_counts, n_h, ci, cx, h_ci, h_cx, d_flags, d_tile_counts);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t tbk_launch_kmerdb_scatter_ranks(const uint64_t *a_keys, uint64_t n_a, const uint64_t *d_flags,
+                                                      const unsigned long long *d_tile_offsets, uint64_t *d_out, uint64_t n_out, hipStream_t stream) {
+    const uint64_t tiles = tbk_kmerdb_table_tiles(n_a);
+    if (!tiles || !n_out) return hipSuccess;
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tbk_kmerdb_scatter_ranks_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, n_a, d_flags, d_tile_offsets, d_out, n_out);
     return hipGetLastError();
 }

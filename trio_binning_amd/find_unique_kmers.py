@@ -70,6 +70,17 @@ def parse_args(argv=None):
                      "analyzed".format(hap.upper()),
             )
     parser.add_argument(
+        "--child", default=None, metavar="FILES",
+        help="one comma-separated list of the child's short-read files, or its count database (one path ending in .tbkdb): "
+             "the output then holds only the parental k-mers the child inherited, those its library holds too (seen at least "
+             "twice, with a count from its own lower cut-off on). The child is counted third, through count databases; with "
+             "--keep-databases its database is left as <outpath>/child.tbkdb",
+    )
+    parser.add_argument(
+        "--min-count-child", type=int, default=None, metavar="N",
+        help="lower count cut-off of the child chosen by hand (the upper one is 255): its histogram is written but not analyzed",
+    )
+    parser.add_argument(
         "read_files", nargs=2,
         help="one comma-separated list of file paths for both libraries being compared. Files can "
              "be in fasta or fastq format, and uncompressed or gzipped. A single path ending in .tbkdb is a count "
@@ -82,6 +93,10 @@ def parse_args(argv=None):
             parser.error("--min-count-{0} and --max-count-{0} go together".format(hap))
         if lo is not None and not 1 <= lo <= hi:
             parser.error("--min-count-{0} {1} --max-count-{0} {2}: need 1 <= min <= max".format(hap, lo, hi))
+    if args.min_count_child is not None and args.child is None:
+        parser.error("--min-count-child chooses from the child's counts: give --child too")
+    if args.min_count_child is not None and args.min_count_child < 1:
+        parser.error("--min-count-child {}: need 1 <= min".format(args.min_count_child))
     return args
 
 
@@ -212,7 +227,7 @@ DATABASE_SHARE = 8         # 1 / this of a parent's distinct k-mers is planned t
 DATABASE_BYTES = 9         # ... and costs a key and a one-byte counter
 
 
-def choose_passes(capacity: int, bases_estimate: int, free_bytes: int) -> int:
+def choose_passes(capacity: int, bases_estimate: int, free_bytes: int, databases: int = 2) -> int:
     """The fewest passes in which one parent of `capacity` distinct k-mers and `bases_estimate` bases can be
     counted within `free_bytes` of HBM.  A pure function of its arguments; all arithmetic in integers.
 
@@ -223,14 +238,14 @@ def choose_passes(capacity: int, bases_estimate: int, free_bytes: int) -> int:
       table that doubles is held beside its twice as large successor) fits if 4 * table(1) <= budget;
     * P > 1 fits if  store + 3 * table(P) + databases <= budget, where store = ceil(bases_estimate / 2) (the
       reads of the parent being counted, 0.5 bytes per base), 3 * table(P) is one class's table beside its
-      doubling twin, and databases = 2 * 9 * (capacity // 8) is what both parents leave behind: a ninth byte on
-      every key seen at least twice, planned as an eighth of the distinct k-mers (the others are the k-mers
-      seen once that -ci2 drops).
+      doubling twin, and databases = `databases` * 9 * (capacity // 8) is what the libraries leave behind (two
+      parents; three with a child): a ninth byte on every key seen at least twice, planned as an eighth of the
+      distinct k-mers (the others are the k-mers seen once that -ci2 drops).
 
     Returns the smallest such P; ValueError when the store and the databases alone pass the budget, or when
     more than 1024 passes would be needed."""
-    if capacity < 1 or bases_estimate < 0 or free_bytes < 0:
-        raise ValueError("choose_passes: capacity must be positive, bases and free bytes not negative")
+    if capacity < 1 or bases_estimate < 0 or free_bytes < 0 or databases < 0:
+        raise ValueError("choose_passes: capacity must be positive, bases, free bytes and databases not negative")
     budget = free_bytes * PLAN_FRACTION[0] // PLAN_FRACTION[1]
 
     def table(p: int) -> int:
@@ -239,7 +254,7 @@ def choose_passes(capacity: int, bases_estimate: int, free_bytes: int) -> int:
     if 4 * table(1) <= budget:
         return 1
     store = -(-bases_estimate * STORE_BYTES[0] // STORE_BYTES[1])
-    fixed = store + 2 * DATABASE_BYTES * (capacity // DATABASE_SHARE)
+    fixed = store + databases * DATABASE_BYTES * (capacity // DATABASE_SHARE)
     if store > budget:
         raise ValueError(
             "the reads alone ({} bases, {} bytes packed) do not fit the {} bytes planned of {} free on the GPU: "
@@ -280,10 +295,14 @@ def main(argv=None):
         raise ValueError("--passes must be between 0 and {}".format(MAX_PASSES))
     hap_ids = ["A", "B"]
     from_file = [is_database_path(s) for s in args.read_files]
-    # with none of the database options both counters stay live until the dumps are written, as ever
-    by_database = args.keep_databases or any(from_file)
+    # with none of the database options both counters stay live until the dumps are written, as ever; a child is a third
+    # library, and three are only ever held as databases
+    by_database = args.keep_databases or any(from_file) or args.child is not None
     given = {"A": (args.min_count_a, args.max_count_a), "B": (args.min_count_b, args.max_count_b)}
-    for hap_id, path, is_db in zip(hap_ids, args.read_files, from_file):
+    counted = list(zip(args.read_files, from_file))  # every library: (its argument, whether that is a database)
+    if args.child is not None:
+        counted.append((args.child, is_database_path(args.child)))
+    for path, is_db in counted:
         if is_db:  # its header says what it holds: checked before anything is counted
             info = kmers.database_file_info(path)
             if info["k"] != k:
@@ -291,15 +310,16 @@ def main(argv=None):
     passes = args.passes
     if not passes:
         # both parents are counted in the same number of passes (their classes must match): the larger need decides
-        passes, free = 1, kmers.device_mem_info()[0] if not all(from_file) else 0
-        for files_string, is_db in zip(args.read_files, from_file):
+        passes, free = 1, kmers.device_mem_info()[0] if not all(is_db for _, is_db in counted) else 0
+        for files_string, is_db in counted:
             if is_db:
                 continue
             paths = [p for p in files_string.split(",") if os.path.isfile(p)]  # (a missing file is reported below, in its turn)
             bases = estimate_bases(paths)
-            passes = max(passes, choose_passes(args.capacity or max(1 << 16, bases), bases, free))
-    kept = {}      # haplotype -> the database file it can be dumped from again
-    held = None    # the first HistogramError of a --keep-databases run: raised once both databases are on disk
+            passes = max(passes, choose_passes(args.capacity or max(1 << 16, bases), bases, free, databases=len(counted)))
+    kept = {}      # haplotype (or "child") -> the database file it can be dumped from again
+    held = None    # the first HistogramError of a --keep-databases run: raised once every database is on disk
+    child = [None, args.min_count_child]  # the child's database and its lower cut-off
     try:
         for hap_id, files_string, is_db in zip(hap_ids, args.read_files, from_file):
             if is_db:
@@ -341,29 +361,71 @@ def main(argv=None):
                     continue
             print("\033[92mUsing counts in range [{},{}].\033[0m".format(min_count, max_count), file=sys.stderr)
             libraries[-1][1:] = [min_count, max_count]
+        if args.child is not None:
+            # third, when each parent's counter has become its database and is closed
+            if counted[2][1]:
+                print("\033[92mLoading the k-mer database of the child...\033[0m", file=sys.stderr)
+                child[0] = kmers.KmerDatabase.load(args.child)
+                kept["child"] = args.child
+            else:
+                print("\033[92mCounting k-mers in the child...\033[0m", file=sys.stderr)
+                paths = args.child.split(",")
+                for p in paths:
+                    if not os.path.isfile(p):
+                        raise IOError("no such file: {}".format(p))
+                capacity = args.capacity or (estimate_capacity(paths) if passes == 1 else max(1 << 16, estimate_bases(paths)))
+                counter = count_library(paths, k, capacity, passes)
+                try:
+                    child[0] = counter.database()
+                finally:
+                    counter.close()
+                if args.keep_databases:
+                    kept["child"] = os.path.join(args.outpath, "child" + DATABASE_SUFFIX)
+                    child[0].save(kept["child"])
+            print("\033[92mComputing and analyzing histogram...\033[0m", file=sys.stderr)
+            histogram_path = os.path.join(args.scratch_dir, "child.histogram")
+            rows = write_histogram(histogram_path, child[0].histogram())
+            if child[1] is None:
+                try:
+                    child[1] = analyze_histogram(rows, histogram_path)[0]  # (its maximum is not used: the child's range ends at 255)
+                except HistogramError as exc:
+                    if not args.keep_databases:
+                        raise
+                    held = held or exc
+            if child[1] is not None:
+                print("\033[92mUsing counts in range [{},255] for the child.\033[0m".format(child[1]), file=sys.stderr)
         if held is not None:
-            print(redump_advice(args, kept, libraries), file=sys.stderr)
+            print(redump_advice(args, kept, libraries, child[1]), file=sys.stderr)
             raise held
         (counter_a, min_a, max_a), (counter_b, min_b, max_b) = libraries
+        # (with a child all three are databases: only KmerDatabase.unique takes one)
+        third = {} if child[0] is None else {"child": child[0], "child_min": child[1], "child_max": 255}
         print("\033[92mFinding and dumping k-mers unique to haplotype A...\033[0m", file=sys.stderr)
-        n_a = counter_a.unique(counter_b, min_a, max_a, os.path.join(args.outpath, "hapA_only_kmers.txt"))
+        n_a = counter_a.unique(counter_b, min_a, max_a, os.path.join(args.outpath, "hapA_only_kmers.txt"), **third)
         print("\033[92mFinding and dumping k-mers unique to haplotype B...\033[0m", file=sys.stderr)
-        n_b = counter_b.unique(counter_a, min_b, max_b, os.path.join(args.outpath, "hapB_only_kmers.txt"))
+        n_b = counter_b.unique(counter_a, min_b, max_b, os.path.join(args.outpath, "hapB_only_kmers.txt"), **third)
     finally:
         for lib in libraries:
             lib[0].close()
-    print("\n\n\033[94m# of unique k-mers in haplotype A: {}\033[0m".format(n_a), file=sys.stderr)
-    print("\033[94m# of unique k-mers in haplotype B: {}\033[0m".format(n_b), file=sys.stderr)
+        if child[0] is not None:
+            child[0].close()
+    what = "unique k-mers" if args.child is None else "unique k-mers the child inherited"
+    print("\n\n\033[94m# of {} in haplotype A: {}\033[0m".format(what, n_a), file=sys.stderr)
+    print("\033[94m# of {} in haplotype B: {}\033[0m".format(what, n_b), file=sys.stderr)
 
 
-def redump_advice(args, kept, libraries) -> str:
+def redump_advice(args, kept, libraries, child_min=None) -> str:
     """What to run once cut-offs have been chosen by hand: the databases are on disk, nothing is counted again."""
     words = ["find-unique-kmers", "-k", str(args.kmer_size), "-o", args.outpath, "-s", args.scratch_dir]
     for hap_id, (_, lo, hi) in zip("AB", libraries):
         words += ["--min-count-" + hap_id.lower(), str(lo) if lo else "MIN", "--max-count-" + hap_id.lower(), str(hi) if hi else "MAX"]
+    where = "{} and {}".format(kept["A"], kept["B"])
+    if "child" in kept:
+        words += ["--child", kept["child"], "--min-count-child", str(child_min) if child_min else "MIN"]
+        where = "{}, {} and {}".format(kept["A"], kept["B"], kept["child"])
     words += [kept["A"], kept["B"]]
-    return ("The k-mer databases are kept in {} and {}. Choose the cut-offs marked MIN and MAX from the histograms and dump "
-            "again, without counting:\n  {}".format(kept["A"], kept["B"], " ".join(words)))
+    return ("The k-mer databases are kept in {}. Choose the cut-offs marked MIN and MAX from the histograms and dump "
+            "again, without counting:\n  {}".format(where, " ".join(words)))
 
 
 if __name__ == "__main__":

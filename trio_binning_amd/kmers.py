@@ -960,18 +960,29 @@ class KmerDatabase:
         check(lib.tbk_kmerdb_read(self._h, first, count, keys.ctypes.data, counts.ctypes.data))
         return keys, counts
 
-    def unique(self, other: "KmerDatabase", min_count: int, max_count: int, out_path: str) -> int:
-        """``KmerCounter.unique`` between two databases: the same file."""
+    def unique(self, other: "KmerDatabase", min_count: int, max_count: int, out_path: str,
+               child: Optional["KmerDatabase"] = None, child_min: int = 2, child_max: int = 255) -> int:
+        """``KmerCounter.unique`` between two databases: the same file.  With ``child`` (a third database) only the k-mers
+        that the child holds with a counter in [child_min, child_max] are written (``tbk_kmerdb_inherited``)."""
         n = C.c_uint64()
-        check(lib.tbk_kmerdb_unique(self._h, other._h, min_count, max_count, os.fsencode(out_path), C.byref(n)))
+        if child is None:
+            check(lib.tbk_kmerdb_unique(self._h, other._h, min_count, max_count, os.fsencode(out_path), C.byref(n)))
+        else:
+            check(lib.tbk_kmerdb_inherited(self._h, other._h, child._h, min_count, max_count, child_min, child_max,
+                                           os.fsencode(out_path), C.byref(n)))
         return n.value
 
-    def unique_set(self, other: "KmerDatabase", min_count: int, max_count: int) -> HashSet:
+    def unique_set(self, other: "KmerDatabase", min_count: int, max_count: int,
+                   child: Optional["KmerDatabase"] = None, child_min: int = 2, child_max: int = 255) -> HashSet:
         """The list ``unique`` would write, as the ``HashSet`` ``create_kmer_hash_set`` would make of that file - the same keys
         in the same order - without the text in between (``tbk_kmerdb_unique_table``): selected, compacted and packed where
-        the databases lie.  ``ValueError`` ("empty k-mer list") when nothing is selected, as for an empty list file."""
+        the databases lie.  ``ValueError`` ("empty k-mer list") when nothing is selected, as for an empty list file.  With
+        ``child`` the list holds the inherited k-mers only, as ``unique`` does (``tbk_kmerdb_inherited_table``)."""
         h = C.c_void_p()
-        check(lib.tbk_kmerdb_unique_table(self._h, other._h, min_count, max_count, C.byref(h)))
+        if child is None:
+            check(lib.tbk_kmerdb_unique_table(self._h, other._h, min_count, max_count, C.byref(h)))
+        else:
+            check(lib.tbk_kmerdb_inherited_table(self._h, other._h, child._h, min_count, max_count, child_min, child_max, C.byref(h)))
         return HashSet(h.value)
 
     def close(self) -> None:
