@@ -766,6 +766,34 @@ int tbk_kmerdb_inherited(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kme
 int tbk_kmerdb_inherited_table(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kmerdb *child, uint32_t min_count, uint32_t max_count,
                                uint32_t child_min, uint32_t child_max, tbk_table **out);
 
+/* ---- hit tracker: WHERE along a sequence the haplotype k-mers lie ------------------------ */
+/* The classifier answers with two numbers per read; the tracker keeps the positions.  A window start is a MARKER of
+ * hapA or hapB by the rule of tbk_count_kmers_in_read: windows 0 .. len - k, key = min(forward, reverse complement),
+ * a window holding a byte outside upper-case ACGT is none, hapA is asked first (a key both lists hold marks A only),
+ * lists hold their lines verbatim (a non-canonical line never hits).  ignore_case != 0 reads lower-case acgt as
+ * upper-case; 0 leaves them not-ACGT, as the classifier does.
+ * A raw RUN is a maximal sequence of one read's markers, in position order, that are of one haplotype: consecutive in
+ * marker order, however far apart, and never across a read boundary.  first / last: window starts of its first and
+ * last marker within the read; a run's extent in bases is last + k - first.
+ * The tracker borrows the two lists (they must outlive it; same k, same device, else TBK_ERR_INVALID), builds their
+ * standalone tables on first use and owns its device buffers, which grow to the largest batch seen.  One batch at a
+ * time per tracker.  The work is on the device: separation, marking (one wave per 2048 window starts, one bit per
+ * window start and list), then compaction of the markers and of the run heads, each as counts per tile, an
+ * exclusive scan and a scatter; only the runs (or the marks) travel home. */
+typedef struct tbk_hit_run { uint64_t read, first, last; uint32_t markers, hap; } tbk_hit_run;  /* hap: 0 = A, 1 = B */
+typedef struct tbk_hit_tracker tbk_hit_tracker;
+int tbk_hit_tracker_create(tbk_table *hap_a, tbk_table *hap_b, tbk_hit_tracker **out);
+void tbk_hit_tracker_destroy(tbk_hit_tracker *t);
+/* The batch's runs ordered by (read, first), in memory of tbk_host_alloc: *runs is the caller's to tbk_host_free (NULL
+ * when *n_runs is 0: an empty batch, reads shorter than k, no hit).  counts, when not NULL, gets the markers per read
+ * and list (n_reads x 2, what tbk_classify_batch counts), added up from the runs. */
+int tbk_hit_tracker_runs(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
+                         tbk_hit_run **runs, uint64_t *n_runs, int32_t *counts);
+/* One byte per base of the batch, in the batch's own coordinates: marks[offsets[r] + w] is 0 (none), 1 (A) or 2 (B)
+ * for window start w of read r; the last k - 1 bytes of a read are 0. */
+int tbk_hit_tracker_marks(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
+                          uint8_t *marks);
+
 /* Host threads the library starts for its own host-side work (list parsing, gzip members,
  * scoring): hardware threads limited by the CPU affinity mask and the cgroup CPU quota, divided by the
  * number of ranks the launcher started on this node (LOCAL_WORLD_SIZE, or TBK_LOCAL_RANKS): one process per GPU

@@ -216,6 +216,12 @@ if HAS_KMERDB:
     if hasattr(lib, "tbk_kmerdb_inherited"):
         _sig("tbk_kmerdb_inherited", C.c_int, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, _u64p)
         _sig("tbk_kmerdb_inherited_table", C.c_int, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp))
+HAS_HIT_TRACKER = hasattr(lib, "tbk_hit_tracker_create")  # (variant builds of tools/build_variant.sh may predate the hit tracker)
+if HAS_HIT_TRACKER:
+    _sig("tbk_hit_tracker_create", C.c_int, _vp, _vp, C.POINTER(_vp))
+    _sig("tbk_hit_tracker_destroy", None, _vp)
+    _sig("tbk_hit_tracker_runs", C.c_int, _vp, _vp, _vp, _u64, C.c_int, C.POINTER(_vp), _u64p, _vp)
+    _sig("tbk_hit_tracker_marks", C.c_int, _vp, _vp, _vp, _u64, C.c_int, _vp)
 _sig("tbk_calib_gather", C.c_int, C.c_int, _u64, C.c_int, C.c_int, C.c_int, _u64, C.c_int, _dp, _dp)
 _sig("tbk_calib_atomics", C.c_int, C.c_int, _u64, C.c_int, C.c_int, _dp)
 if hasattr(lib, "tbk_calib_atomics64"):

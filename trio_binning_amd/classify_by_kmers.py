@@ -37,7 +37,8 @@ class DatabasePair:
     database (``child_path``, its counts from ``child_min`` on) the lists hold only what the child inherited."""
 
     def __init__(self, path_a: str, path_b: str, range_a: Tuple[int, int], range_b: Tuple[int, int],
-                 child_path: Optional[str] = None, child_min: int = 2):
+                 child_path: Optional[str] = None, child_min: int = 2, prog: str = "classify-by-kmers"):
+        self.prog = prog  # the command its refusals speak for
         self.paths = {"A": path_a, "B": path_b}
         self.ranges = {"A": range_a, "B": range_b}
         self.child_path, self.child_min = child_path, child_min
@@ -65,11 +66,11 @@ class DatabasePair:
                     if "empty k-mer list" not in str(exc):
                         raise
                     if third:
-                        sys.exit(f"classify-by-kmers: haplotype {hap} has no k-mer with a count in [{lo},{hi}] that haplotype {other} lacks "
+                        sys.exit(f"{self.prog}: haplotype {hap} has no k-mer with a count in [{lo},{hi}] that haplotype {other} lacks "
                                  f"and the child holds with a count in [{self.child_min},255] ({self.paths[hap]} minus {self.paths[other]}, "
                                  f"within {self.child_path}): nothing to classify by. Choose other cut-offs with --min-count-{hap.lower()}, "
                                  f"--max-count-{hap.lower()} and --min-count-child.")
-                    sys.exit(f"classify-by-kmers: haplotype {hap} has no k-mer with a count in [{lo},{hi}] that haplotype {other} lacks "
+                    sys.exit(f"{self.prog}: haplotype {hap} has no k-mer with a count in [{lo},{hi}] that haplotype {other} lacks "
                              f"({self.paths[hap]} minus {self.paths[other]}): nothing to classify by. Choose other cut-offs with "
                              f"--min-count-{hap.lower()} and --max-count-{hap.lower()}.")
                 found = "unique to haplotype {} and inherited by the child".format(hap) if third else "unique to haplotype {}".format(hap)
@@ -107,6 +108,12 @@ def _parser(kmer_list_type) -> argparse.ArgumentParser:
     parser.add_argument("--haplotype-b-out-prefix", default="hapB", help="prefix for haplotype B output file")
     parser.add_argument("--unclassified-out-prefix", default="unclassified", help="prefix for unclassified output file")
     parser.add_argument("--no-gzip-output", action="store_true", default=False, help="don't gzip the output")
+    _add_database_options(parser)
+    return parser
+
+
+def _add_database_options(parser) -> None:
+    """The options that choose from count databases (shared with phase_blocks)."""
     for hap in "ab":
         for bound in ("min", "max"):
             parser.add_argument(
@@ -124,21 +131,20 @@ def _parser(kmer_list_type) -> argparse.ArgumentParser:
         help="with --child-database: the child's lower count cut-off chosen by hand instead of the one find-unique-kmers would "
              "choose from its histogram (the upper one is 255)",
     )
-    return parser
 
 
-def _settle_databases(args) -> DatabasePair:
+def _settle_databases(args, prog: str = "classify-by-kmers") -> DatabasePair:
     """Everything about a pair of databases, and the child's beside them, that their headers decide - the same k, each
     library's cut-offs - before any device is touched; every refusal is a message."""
     paths = {"A": args.haplotype_a_kmers, "B": args.haplotype_b_kmers}
     infos = {hap: kmers.database_file_info(paths[hap]) for hap in "AB"}
     if infos["A"]["k"] != infos["B"]["k"]:
-        sys.exit("classify-by-kmers: {} holds {}-mers, but {} holds {}-mers".format(paths["A"], infos["A"]["k"], paths["B"], infos["B"]["k"]))
+        sys.exit(prog + ": {} holds {}-mers, but {} holds {}-mers".format(paths["A"], infos["A"]["k"], paths["B"], infos["B"]["k"]))
     child_info = None
     if args.child_database is not None:
         child_info = kmers.database_file_info(args.child_database)
         if child_info["k"] != infos["A"]["k"]:
-            sys.exit("classify-by-kmers: {} holds {}-mers, but {} holds {}-mers".format(
+            sys.exit(prog + ": {} holds {}-mers, but {} holds {}-mers".format(
                 paths["A"], infos["A"]["k"], args.child_database, child_info["k"]))
     ranges = {}
     for hap in "AB":
@@ -149,7 +155,7 @@ def _settle_databases(args) -> DatabasePair:
             try:
                 given = fu.analyze_histogram(rows, paths[hap])
             except fu.HistogramError:
-                sys.exit("classify-by-kmers: could not find min and max counts in the histogram of {} (haplotype {}). Choose cut-offs by "
+                sys.exit(prog + ": could not find min and max counts in the histogram of {} (haplotype {}). Choose cut-offs by "
                          "hand and give them with --min-count-a, --max-count-a, --min-count-b and --max-count-b.".format(paths[hap], hap))
         print("\033[92mUsing counts in range [{},{}].\033[0m".format(*given), file=sys.stderr)
         ranges[hap] = (int(given[0]), int(given[1]))
@@ -159,12 +165,12 @@ def _settle_databases(args) -> DatabasePair:
         try:
             child_min = fu.analyze_histogram(rows, args.child_database)[0]  # (its maximum is not used)
         except fu.HistogramError:
-            sys.exit("classify-by-kmers: could not find the minimum count in the histogram of {} (the child). Choose it by hand and "
+            sys.exit(prog + ": could not find the minimum count in the histogram of {} (the child). Choose it by hand and "
                      "give it with --min-count-child.".format(args.child_database))
     if child_info is not None:
         print("\033[92mUsing counts in range [{},255] for the child.\033[0m".format(child_min), file=sys.stderr)
-        return DatabasePair(paths["A"], paths["B"], ranges["A"], ranges["B"], args.child_database, int(child_min))
-    return DatabasePair(paths["A"], paths["B"], ranges["A"], ranges["B"])
+        return DatabasePair(paths["A"], paths["B"], ranges["A"], ranges["B"], args.child_database, int(child_min), prog=prog)
+    return DatabasePair(paths["A"], paths["B"], ranges["A"], ranges["B"], prog=prog)
 
 
 def parse_args():
@@ -176,9 +182,20 @@ def parse_args():
     tables - or two count databases, which are settled from their headers (``args.databases``) and loaded by ``main``."""
     parser = _parser(str)
     args = parser.parse_args()
+    if _check_kmer_arguments(parser, args):
+        args.databases = _settle_databases(args)
+        return args
+    args = _parser(kmers.create_kmer_hash_set).parse_args()
+    args.databases = None
+    return args
+
+
+def _check_kmer_arguments(parser, args, prog: str = "classify-by-kmers") -> bool:
+    """What the two k-mer arguments name - True: two count databases, False: two text lists - and every refusal of the
+    options beside them that needs no file opened (shared with phase_blocks)."""
     is_db = [fu.is_database_path(args.haplotype_a_kmers), fu.is_database_path(args.haplotype_b_kmers)]
     if is_db[0] != is_db[1]:
-        sys.exit("classify-by-kmers: {} is a {} and {} is a {}: give two k-mer lists or two count databases (*{})".format(
+        sys.exit(prog + ": {} is a {} and {} is a {}: give two k-mer lists or two count databases (*{})".format(
             args.haplotype_a_kmers, "count database" if is_db[0] else "k-mer list", args.haplotype_b_kmers,
             "count database" if is_db[1] else "k-mer list", fu.DATABASE_SUFFIX))
     for hap in "ab":
@@ -197,12 +214,7 @@ def parse_args():
         parser.error("--min-count-child chooses from the child's counts: give --child-database too")
     if args.min_count_child is not None and args.min_count_child < 1:
         parser.error("--min-count-child {}: need 1 <= min".format(args.min_count_child))
-    if is_db[0]:
-        args.databases = _settle_databases(args)
-        return args
-    args = _parser(kmers.create_kmer_hash_set).parse_args()
-    args.databases = None
-    return args
+    return is_db[0]
 
 
 def calculate_scaling_factors(haplotype_a_kmers: kmers.HashSet, haplotype_b_kmers: kmers.HashSet) -> Tuple[float, float]:

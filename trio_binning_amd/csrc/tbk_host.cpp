@@ -3157,3 +3157,165 @@ extern "C" int tbk_calib_stream(int device, uint64_t footprint, int reps, double
     if (bytes_per_sec) *bytes_per_sec = (double)footprint * reps / (ms * 1e-3);
     return TBK_OK;
 }
+
+// ---- hit tracker (kernels: tbk_track.hip) ------------------------------------------------------------------------
+// Positions of the haplotype k-mers along the reads of a batch: marks (one byte per window start) or raw runs.  The
+// lists' standalone tables (table_hash) answer membership, A before B; everything between the upload of the batch
+// and the download of the runs is on the device, two counts read back on the way (markers, runs) to size what follows.
+extern "C" hipError_t tbk_launch_track_separate(const uint8_t *, const uint64_t *, uint64_t, int, uint8_t *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_track_mark(const uint8_t *, uint64_t, uint64_t, int, const uint64_t *, uint32_t, const uint64_t *, uint32_t, uint32_t *,
+                                            uint32_t *, unsigned long long *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_track_marks(const uint32_t *, const uint32_t *, const uint64_t *, uint64_t, uint8_t *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_track_markers(const uint32_t *, const uint32_t *, uint64_t, const unsigned long long *, uint64_t *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_track_heads(const uint64_t *, uint64_t, const uint64_t *, uint64_t, uint64_t *, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_track_runs(const uint64_t *, uint64_t, const uint64_t *, uint64_t, const uint64_t *, const unsigned long long *,
+                                            tbk_hit_run *, uint64_t *, uint64_t, int32_t *, hipStream_t);
+extern "C" uint64_t tbk_track_tiles(uint64_t n_markers);
+extern "C" uint64_t tbk_track_flag_words(uint64_t n_markers);
+extern "C" hipError_t tbk_launch_kmerdb_scan(const unsigned long long *, unsigned long long *, uint64_t, hipStream_t);
+
+// a device buffer that only ever grows
+struct TrackBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+struct tbk_hit_tracker {
+    tbk_table *a = nullptr, *b = nullptr;  // borrowed
+    int device = 0, k = 0;
+    uint64_t wave_slots = 0;  // waves the device holds at once: the grid of the launches that stride over reads or passes
+    TrackBuf bases, offsets, sep, bits_a, bits_b, pass_count, pass_offsets, markers, flags, tile_count, tile_offsets, runs, head_index, counts, marks;
+};
+
+static int track_reserve(TrackBuf &b, size_t need) {
+    need = (need + 255) & ~(size_t)255;
+    if (need <= b.cap) return TBK_OK;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr; b.cap = 0;
+    hipError_t e = hipMalloc(&b.p, need);
+    if (e != hipSuccess) { b.p = nullptr; return fail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "hit tracker buffer (%zu bytes): %s", need, hipGetErrorString(e)); }
+    b.cap = need;
+    return TBK_OK;
+}
+
+extern "C" int tbk_hit_tracker_create(tbk_table *hap_a, tbk_table *hap_b, tbk_hit_tracker **out) {
+    if (!out) return fail(TBK_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!hap_a || !hap_b) return fail(TBK_ERR_INVALID, "table is NULL");
+    if (hap_a->device != hap_b->device) return fail(TBK_ERR_INVALID, "tables live on different devices (%d, %d)", hap_a->device, hap_b->device);
+    if (hap_a->k != hap_b->k) return fail(TBK_ERR_INVALID, "the two k-mer lists have different k (%d and %d)", hap_a->k, hap_b->k);
+    int rc = use_device(hap_a->device);
+    if (rc) return rc;
+    if ((rc = table_hash(hap_a)) || (rc = table_hash(hap_b))) return rc;
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, hap_a->device));
+    tbk_hit_tracker *t = new tbk_hit_tracker();
+    t->a = hap_a; t->b = hap_b;
+    t->device = hap_a->device; t->k = hap_a->k;
+    t->wave_slots = (uint64_t)std::max(cus, 1) * 32;  // 4 SIMDs x 8 waves per compute unit
+    *out = t;
+    return TBK_OK;
+}
+
+extern "C" void tbk_hit_tracker_destroy(tbk_hit_tracker *t) {
+    if (!t) return;
+    if (hipSetDevice(t->device) == hipSuccess)
+        for (TrackBuf *b : {&t->bases, &t->offsets, &t->sep, &t->bits_a, &t->bits_b, &t->pass_count, &t->pass_offsets, &t->markers, &t->flags,
+                            &t->tile_count, &t->tile_offsets, &t->runs, &t->head_index, &t->counts, &t->marks})
+            if (b->p) (void)hipFree(b->p);
+    delete t;
+}
+
+// Upload, separate, mark: leaves the batch's offsets in t->offsets, the two bitmaps and the markers per pass, one zero
+// behind them for the scan.  *n_passes = 0: the batch has no window (fewer than k bases in all).
+static int track_mark(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case, uint64_t *n_passes) {
+    *n_passes = 0;
+    int rc = tbk_check_offsets_(offsets, n_reads);
+    if (rc) return rc;
+    const uint64_t total = offsets[n_reads];
+    if (total && !bases) return fail(TBK_ERR_INVALID, "bases is NULL");
+    if (total < (uint64_t)t->k) return TBK_OK;
+    if ((rc = use_device(t->device))) return rc;
+    const uint64_t sep_total = total + n_reads;  // one 'N' behind every read
+    const uint64_t passes = tbk_probe_passes(sep_total);
+    if ((rc = track_reserve(t->bases, total)) || (rc = track_reserve(t->offsets, (n_reads + 1) * 8)) || (rc = track_reserve(t->sep, sep_total)) ||
+        (rc = track_reserve(t->bits_a, passes * 64 * 4)) || (rc = track_reserve(t->bits_b, passes * 64 * 4)) ||
+        (rc = track_reserve(t->pass_count, (passes + 1) * 8)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(t->bases.p, bases, total, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(t->offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(hipMemsetAsync(t->pass_count.as<unsigned long long>() + passes, 0, 8, nullptr));
+    HIP_TRY(tbk_launch_track_separate(t->bases.as<uint8_t>(), t->offsets.as<uint64_t>(), n_reads, ignore_case, t->sep.as<uint8_t>(), t->wave_slots, nullptr));
+    HIP_TRY(tbk_launch_track_mark(t->sep.as<uint8_t>(), sep_total, passes, t->k, t->a->d_slots, t->a->n_buckets, t->b->d_slots, t->b->n_buckets,
+                                  t->bits_a.as<uint32_t>(), t->bits_b.as<uint32_t>(), t->pass_count.as<unsigned long long>(), t->wave_slots, nullptr));
+    *n_passes = passes;
+    return TBK_OK;
+}
+
+extern "C" int tbk_hit_tracker_marks(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
+                                     uint8_t *marks) {
+    if (!t) return fail(TBK_ERR_INVALID, "tracker is NULL");
+    if (!n_reads) return TBK_OK;
+    uint64_t passes = 0;
+    int rc = track_mark(t, bases, offsets, n_reads, ignore_case, &passes);
+    if (rc) return rc;
+    const uint64_t total = offsets[n_reads];
+    if (total && !marks) return fail(TBK_ERR_INVALID, "marks is NULL");
+    if (!passes) { if (total) memset(marks, 0, total); return TBK_OK; }
+    if ((rc = track_reserve(t->marks, total))) return rc;
+    HIP_TRY(tbk_launch_track_marks(t->bits_a.as<uint32_t>(), t->bits_b.as<uint32_t>(), t->offsets.as<uint64_t>(), n_reads, t->marks.as<uint8_t>(),
+                                   t->wave_slots, nullptr));
+    HIP_TRY(hipMemcpy(marks, t->marks.p, total, hipMemcpyDeviceToHost));
+    return TBK_OK;
+}
+
+extern "C" int tbk_hit_tracker_runs(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
+                                    tbk_hit_run **runs, uint64_t *n_runs, int32_t *counts) {
+    if (!t || !runs || !n_runs) return fail(TBK_ERR_INVALID, "NULL argument");
+    *runs = nullptr;
+    *n_runs = 0;
+    if (!n_reads) return TBK_OK;
+    uint64_t passes = 0;
+    int rc = track_mark(t, bases, offsets, n_reads, ignore_case, &passes);
+    if (rc) return rc;
+    if (counts) memset(counts, 0, n_reads * 2 * sizeof(int32_t));
+    if (!passes) return TBK_OK;
+    // the markers: pass counts -> pass offsets, the total behind them
+    unsigned long long n_markers = 0, n_heads = 0;
+    if ((rc = track_reserve(t->pass_offsets, (passes + 1) * 8))) return rc;
+    HIP_TRY(tbk_launch_kmerdb_scan(t->pass_count.as<unsigned long long>(), t->pass_offsets.as<unsigned long long>(), passes + 1, nullptr));
+    HIP_TRY(hipMemcpy(&n_markers, t->pass_offsets.as<unsigned long long>() + passes, 8, hipMemcpyDeviceToHost));
+    if (!n_markers) return TBK_OK;
+    if (n_markers > offsets[n_reads]) return fail(TBK_ERR_HIP, "hit tracker: %llu markers in %llu bases", n_markers, (unsigned long long)offsets[n_reads]);
+    if ((rc = track_reserve(t->markers, n_markers * 8))) return rc;
+    HIP_TRY(tbk_launch_track_markers(t->bits_a.as<uint32_t>(), t->bits_b.as<uint32_t>(), passes, t->pass_offsets.as<unsigned long long>(),
+                                     t->markers.as<uint64_t>(), n_markers, nullptr));
+    // the run heads: flags and tile counts -> tile offsets, the total behind them
+    const uint64_t tiles = tbk_track_tiles(n_markers);
+    if ((rc = track_reserve(t->flags, tbk_track_flag_words(n_markers) * 8)) || (rc = track_reserve(t->tile_count, (tiles + 1) * 8)) ||
+        (rc = track_reserve(t->tile_offsets, (tiles + 1) * 8)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(t->tile_count.as<unsigned long long>() + tiles, 0, 8, nullptr));
+    HIP_TRY(tbk_launch_track_heads(t->markers.as<uint64_t>(), n_markers, t->offsets.as<uint64_t>(), n_reads, t->flags.as<uint64_t>(),
+                                   t->tile_count.as<unsigned long long>(), nullptr));
+    HIP_TRY(tbk_launch_kmerdb_scan(t->tile_count.as<unsigned long long>(), t->tile_offsets.as<unsigned long long>(), tiles + 1, nullptr));
+    HIP_TRY(hipMemcpy(&n_heads, t->tile_offsets.as<unsigned long long>() + tiles, 8, hipMemcpyDeviceToHost));
+    if (!n_heads || n_heads > n_markers) return fail(TBK_ERR_HIP, "hit tracker: %llu runs of %llu markers", n_heads, n_markers);
+    if ((rc = track_reserve(t->runs, n_heads * sizeof(tbk_hit_run))) || (rc = track_reserve(t->head_index, n_heads * 8))) return rc;
+    if (counts) {
+        if ((rc = track_reserve(t->counts, n_reads * 2 * sizeof(int32_t)))) return rc;
+        HIP_TRY(hipMemsetAsync(t->counts.p, 0, n_reads * 2 * sizeof(int32_t), nullptr));
+    }
+    HIP_TRY(tbk_launch_track_runs(t->markers.as<uint64_t>(), n_markers, t->offsets.as<uint64_t>(), n_reads, t->flags.as<uint64_t>(),
+                                  t->tile_offsets.as<unsigned long long>(), t->runs.as<tbk_hit_run>(), t->head_index.as<uint64_t>(), n_heads,
+                                  counts ? t->counts.as<int32_t>() : nullptr, nullptr));
+    tbk_hit_run *home = static_cast<tbk_hit_run *>(tbk_host_alloc(n_heads * sizeof(tbk_hit_run)));
+    if (!home) return TBK_ERR_NOMEM;
+    hipError_t e = hipMemcpy(home, t->runs.p, n_heads * sizeof(tbk_hit_run), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && counts) e = hipMemcpy(counts, t->counts.p, n_reads * 2 * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { tbk_host_free(home); return fail(TBK_ERR_HIP, "hit tracker: %s", hipGetErrorString(e)); }
+    *runs = home;
+    *n_runs = n_heads;
+    return TBK_OK;
+}

@@ -559,6 +559,90 @@ class Classifier:
         self.close()
 
 
+# one raw run or phase block: tbk_hit_run (include/tbk.h), 32 bytes
+HIT_RUN_DTYPE = [("read", "<u8"), ("first", "<u8"), ("last", "<u8"), ("markers", "<u4"), ("hap", "<u4")]
+
+
+class HitTracker:
+    """WHERE along each read of a batch the haplotype k-mers lie (``tbk_hit_tracker``).
+
+    A window start is a marker of hapA or hapB by the rule of ``count_kmers_in_read`` (hapA first); a raw run is a
+    maximal sequence of one read's markers, in position order, of one haplotype.  The lists are borrowed, as a
+    ``Classifier`` borrows them; the tracker owns its device buffers."""
+
+    def __init__(self, kmers_hap_a: HashSet, kmers_hap_b: HashSet):
+        h = C.c_void_p()
+        check(lib.tbk_hit_tracker_create(kmers_hap_a._h, kmers_hap_b._h, C.byref(h)))
+        self._h = h
+        self._a, self._b = kmers_hap_a, kmers_hap_b  # keep the tables alive
+        self.k = kmers_hap_a.k
+
+    def runs(self, bases: np.ndarray, offsets: np.ndarray, ignore_case: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """(runs, counts): the batch's raw runs ordered by (read, first) - a structured array with the fields read, first,
+        last (window starts of the first and last marker within the read), markers and hap (0 = A, 1 = B) - and the
+        markers per read and list, ``Classifier.classify_batch``'s (n_reads, 2) array."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        counts = np.zeros((n, 2), dtype=np.int32)
+        ptr, n_runs = C.c_void_p(), C.c_uint64()
+        check(lib.tbk_hit_tracker_runs(self._h, bases.ctypes.data, offsets.ctypes.data, n, int(bool(ignore_case)), C.byref(ptr), C.byref(n_runs),
+                                       counts.ctypes.data))
+        runs = np.zeros(n_runs.value, dtype=HIT_RUN_DTYPE)
+        if n_runs.value:
+            C.memmove(runs.ctypes.data, ptr.value, runs.nbytes)
+        lib.tbk_host_free(ptr)
+        return runs, counts
+
+    def marks(self, bases: np.ndarray, offsets: np.ndarray, ignore_case: bool = False) -> np.ndarray:
+        """One byte per base of the batch: 0 none, 1 A, 2 B for the window that starts there (a read's last k - 1 bytes are 0)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        marks = np.zeros(int(offsets[-1]) if offsets.size else 0, dtype=np.uint8)
+        check(lib.tbk_hit_tracker_marks(self._h, bases.ctypes.data, offsets.ctypes.data, n, int(bool(ignore_case)), marks.ctypes.data))
+        return marks
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            lib.tbk_hit_tracker_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def phase_blocks(runs: np.ndarray, min_run: int = 1) -> np.ndarray:
+    """Raw runs -> phase blocks, on the host.  Every raw run with fewer than ``min_run`` markers is dropped, in one pass
+    that is not repeated; surviving runs that are now neighbours in the same read and of the same haplotype merge into
+    one block: ``first`` of the first, ``last`` of the last, the markers added up.  (This project's rule - an isolated
+    hit of an error k-mer is one window, a real variant up to k neighbouring ones - not Merqury's short-range-switch rule.)"""
+    if min_run < 1:
+        raise ValueError("min_run must be at least 1")
+    runs = np.asarray(runs, dtype=HIT_RUN_DTYPE)
+    kept = runs[runs["markers"] >= min_run]
+    if kept.size == 0:
+        return kept.copy()
+    head = np.ones(kept.size, dtype=bool)
+    head[1:] = (kept["read"][1:] != kept["read"][:-1]) | (kept["hap"][1:] != kept["hap"][:-1])
+    starts = np.nonzero(head)[0]
+    ends = np.append(starts[1:], kept.size) - 1
+    blocks = kept[starts].copy()
+    blocks["last"] = kept["last"][ends]
+    total = np.add.reduceat(kept["markers"].astype(np.uint64), starts)
+    blocks["markers"] = np.minimum(total, 0xFFFFFFFF).astype(np.uint32)
+    return blocks
+
+
 def visible_devices() -> list:
     """Device indices a multi-device run uses: TBK_DEVICES ("0,1,2", a device may repeat), else
     every visible device."""
