@@ -794,6 +794,48 @@ int tbk_hit_tracker_runs(tbk_hit_tracker *t, const uint8_t *bases, const uint64_
 int tbk_hit_tracker_marks(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
                           uint8_t *marks);
 
+/* ---- database query: how often did the reads see the k-mers of a sequence? --------------- */
+/* A query session scores sequences (an assembly's contigs) against ONE count database.  A window start of a sequence
+ * is CLEAN when its k bases are all ACGT, either case: case is folded as the counter folds it (the database was
+ * counted that way, so a database queried with its own reads finds them).  A clean window's k-mer is the counter's
+ * canonical one - the lexicographic minimum of the window and its reverse complement - and its counter c is the
+ * database's, 2..255, or 0 when the database does not hold it (a k-mer the reads hold once is in no database).
+ * The session borrows the database (it must outlive the session) and owns, on the database's device:
+ *   - a DIRECTORY over the top P bits of the 2k-bit rank: 2^P + 1 32-bit offsets, dir[p] = the first entry whose
+ *     rank has prefix >= p, built once at creation by one bisection per prefix.  P = floor(log2 n) - 1, so that a
+ *     bucket holds 2 to 4 entries on average, at most 2k and at most 28: the directory takes 4 (2^P + 1) bytes -
+ *     at most 2n + 4 beside the database's 9n for n >= 4, and never more than 1 GiB + 4.  A lookup reads two
+ *     neighbouring offsets and bisects the bucket between them.  Offsets are 32 bits wide: a database of 2^32 or
+ *     more entries is refused at creation (TBK_ERR_INVALID);
+ *   - the SEEN bitmap, one bit per entry (n / 8 bytes): set when any clean window so far was that entry;
+ *   - with copies != 0, COPIES, one 32-bit counter per entry (4n bytes): the clean windows so far that were that
+ *     entry, whichever strand (a k-mer that is its own reverse complement counts once per window);
+ *   - the HISTOGRAM of c over the clean windows so far (row 0: absent) and the running total of window starts;
+ *   - batch buffers that grow to the largest batch seen.  One batch at a time per session.
+ * A batch that would take the running total of window starts (sum of max(len - k + 1, 0)) past 2^32 - 1 is refused
+ * with TBK_ERR_INVALID before anything is counted, so no copy counter can wrap.  An empty database (n = 0) is valid:
+ * every window is absent.  TBK_ERR_NOMEM at creation leaves the database usable and *out NULL. */
+typedef struct tbk_kmerdb_query tbk_kmerdb_query;
+int tbk_kmerdb_query_create(const tbk_kmerdb *db, int copies, tbk_kmerdb_query **out);
+void tbk_kmerdb_query_destroy(tbk_kmerdb_query *q);
+/* Look up every window of a batch (reads back to back, offsets as for tbk_counter_add_batch) and add it to the
+ * session's histogram, seen bits and copies.  per_read (n_reads x 2, may be NULL): the sequence's clean windows and,
+ * of those, the FOUND ones, c >= max(2, min_count).  counts (may be NULL): one byte per base in the batch's own
+ * coordinates, like tbk_hit_tracker_marks - counts[offsets[r] + w] = c of window w of read r, 0 for a window that is
+ * absent or not clean; the last k - 1 bytes of a sequence are 0.  min_count does not change counts. */
+int tbk_kmerdb_query_add(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t min_count,
+                         uint64_t *per_read, uint8_t *counts);
+/* The clean windows so far by counter; row 0: absent. */
+int tbk_kmerdb_query_histogram(tbk_kmerdb_query *q, uint64_t hist[256]);
+/* k-mer completeness: *solid = entries whose counter lies in [max(2, min_count), min(255, max_count)], *seen = those
+ * of them that a window so far was. */
+int tbk_kmerdb_query_completeness(tbk_kmerdb_query *q, uint32_t min_count, uint32_t max_count, uint64_t *seen, uint64_t *solid);
+/* The copy spectrum: spec[min(copies, 5)][counter] = entries, over all n entries (rows 0..4: that many windows; row 5:
+ * more than four).  TBK_ERR_INVALID for a session made without copies. */
+int tbk_kmerdb_query_copy_spectrum(tbk_kmerdb_query *q, uint64_t spec[6][256]);
+/* Clears seen, copies, the histogram and the window total: the next assembly against the same database. */
+int tbk_kmerdb_query_reset(tbk_kmerdb_query *q);
+
 /* Host threads the library starts for its own host-side work (list parsing, gzip members,
  * scoring): hardware threads limited by the CPU affinity mask and the cgroup CPU quota, divided by the
  * number of ranks the launcher started on this node (LOCAL_WORLD_SIZE, or TBK_LOCAL_RANKS): one process per GPU

@@ -222,6 +222,16 @@ if HAS_HIT_TRACKER:
     _sig("tbk_hit_tracker_destroy", None, _vp)
     _sig("tbk_hit_tracker_runs", C.c_int, _vp, _vp, _vp, _u64, C.c_int, C.POINTER(_vp), _u64p, _vp)
     _sig("tbk_hit_tracker_marks", C.c_int, _vp, _vp, _vp, _u64, C.c_int, _vp)
+HAS_DB_QUERY = hasattr(lib, "tbk_kmerdb_query_create")  # (variant builds of tools/build_variant.sh may predate the database query)
+if HAS_DB_QUERY:
+    _sig("tbk_kmerdb_query_create", C.c_int, _vp, C.c_int, C.POINTER(_vp))
+    _sig("tbk_kmerdb_query_destroy", None, _vp)
+    _sig("tbk_kmerdb_query_add", C.c_int, _vp, _vp, _vp, _u64, C.c_uint32, _vp, _vp)
+    _sig("tbk_kmerdb_query_histogram", C.c_int, _vp, _vp)
+    _sig("tbk_kmerdb_query_completeness", C.c_int, _vp, C.c_uint32, C.c_uint32, _u64p, _u64p)
+    _sig("tbk_kmerdb_query_copy_spectrum", C.c_int, _vp, _vp)
+    _sig("tbk_kmerdb_query_reset", C.c_int, _vp)
+    _sig("tbk_kmerdb_query_set_windows_", C.c_int, _vp, _u64)  # (test hook: the running total of window starts)
 _sig("tbk_calib_gather", C.c_int, C.c_int, _u64, C.c_int, C.c_int, C.c_int, _u64, C.c_int, _dp, _dp)
 _sig("tbk_calib_atomics", C.c_int, C.c_int, _u64, C.c_int, C.c_int, _dp)
 if hasattr(lib, "tbk_calib_atomics64"):

@@ -1156,3 +1156,211 @@ extern "C" int tbk_kmerdb_inherited_table(const tbk_kmerdb *a, const tbk_kmerdb 
     }
     return made;
 }
+
+// =====================================================================================================================
+// Database query (tbk_kmerdb_query; kernels: tbk_query.hip): the counter the database holds for every window of a
+// batch of sequences - per-sequence totals, a histogram, the entries seen, their copies.  include/tbk.h has the rules.
+// =====================================================================================================================
+extern "C" hipError_t tbk_launch_query_directory(const uint64_t *, uint64_t, int, int, uint32_t *, hipStream_t);
+extern "C" hipError_t tbk_launch_query_lookup(const uint8_t *, uint64_t, uint64_t, int, const uint64_t *, const uint8_t *, const uint32_t *, uint64_t, int,
+                                              uint32_t, uint32_t *, uint32_t *, uint8_t *, unsigned long long *, uint32_t *, uint32_t *, uint64_t,
+                                              hipStream_t);
+extern "C" hipError_t tbk_launch_query_totals(const uint32_t *, const uint32_t *, const uint64_t *, uint64_t, unsigned long long *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_query_counts(const uint8_t *, const uint64_t *, uint64_t, uint8_t *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_query_completeness(const uint8_t *, const uint32_t *, uint64_t, uint32_t, uint32_t, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_query_spectrum(const uint8_t *, const uint32_t *, uint64_t, unsigned long long *, hipStream_t);
+
+constexpr uint64_t TBK_QUERY_MAX_WINDOWS = 0xFFFFFFFFull;  // window starts of a session: a 32-bit copy counter cannot wrap
+constexpr int TBK_QUERY_MAX_PREFIX_BITS = 28;              // a directory of at most 1 GiB + 4 bytes
+
+// a device buffer that only ever grows
+struct QueryBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+struct tbk_kmerdb_query {
+    const tbk_kmerdb *db = nullptr;  // borrowed
+    int device = 0, k = 0, prefix_bits = 0;
+    bool with_copies = false;
+    uint64_t wave_slots = 0;  // waves the device holds at once: the grid of the launches that stride over reads or passes
+    uint64_t windows = 0;     // window starts added since creation or the last reset
+    uint32_t *d_dir = nullptr, *d_seen = nullptr, *d_copies = nullptr;
+    unsigned long long *d_sums = nullptr;  // 256 histogram rows, then 2 + 6 x 256 for the per-entry tallies
+    void *d_pad = nullptr;                 // one zero entry that stands for the arrays of an empty database
+    QueryBuf bases, offsets, sep, clean_bits, found_bits, bytes, totals, counts;
+    size_t seen_bytes() const { return (size_t)((db->n + 31) / 32 + 1) * 4; }
+};
+
+static int query_reserve(QueryBuf &b, size_t need) {
+    need = (need + 255) & ~(size_t)255;
+    if (need <= b.cap) return TBK_OK;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr; b.cap = 0;
+    const hipError_t e = hipMalloc(&b.p, need);
+    if (e != hipSuccess) {
+        b.p = nullptr;
+        (void)hipGetLastError();
+        return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "database query buffer (%zu bytes): %s", need, hipGetErrorString(e));
+    }
+    b.cap = need;
+    return TBK_OK;
+}
+
+// P = floor(log2 n) - 1: a mean bucket of 2 to 4 entries; no more bits than a rank has, nor than the directory's cap
+static int query_prefix_bits(uint64_t n, int k) {
+    int log2n = 0;
+    while ((n >> (log2n + 1)) != 0) log2n++;
+    return std::max(0, std::min(std::min(log2n - 1, 2 * k), TBK_QUERY_MAX_PREFIX_BITS));
+}
+
+extern "C" void tbk_kmerdb_query_destroy(tbk_kmerdb_query *q) {
+    if (!q) return;
+    if (hipSetDevice(q->device) == hipSuccess) {
+        for (void *p : {(void *)q->d_dir, (void *)q->d_seen, (void *)q->d_copies, (void *)q->d_sums, q->d_pad})
+            if (p) (void)hipFree(p);
+        for (QueryBuf *b : {&q->bases, &q->offsets, &q->sep, &q->clean_bits, &q->found_bits, &q->bytes, &q->totals, &q->counts})
+            if (b->p) (void)hipFree(b->p);
+    }
+    delete q;
+}
+
+constexpr size_t TBK_QUERY_SUMS = 256 + 2 + 6 * 256;
+
+extern "C" int tbk_kmerdb_query_reset(tbk_kmerdb_query *q) {
+    if (!q) return cfail(TBK_ERR_INVALID, "query is NULL");
+    const int rc = kmerdb_device(q->device);
+    if (rc) return rc;
+    CHIP(hipMemsetAsync(q->d_seen, 0, q->seen_bytes(), nullptr));
+    if (q->with_copies) CHIP(hipMemsetAsync(q->d_copies, 0, (size_t)(q->db->n + 1) * 4, nullptr));
+    CHIP(hipMemsetAsync(q->d_sums, 0, TBK_QUERY_SUMS * sizeof(unsigned long long), nullptr));
+    q->windows = 0;
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_query_create(const tbk_kmerdb *db, int copies, tbk_kmerdb_query **out) {
+    if (!out) return cfail(TBK_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!db) return cfail(TBK_ERR_INVALID, "database is NULL");
+    if (db->n > 0xFFFFFFFFull)
+        return cfail(TBK_ERR_INVALID, "a query's directory holds 32-bit offsets: a database of %llu k-mers (2^32 or more) cannot be queried", (unsigned long long)db->n);
+    int rc = kmerdb_device(db->device);
+    if (rc) return rc;
+    int cus = 0;
+    CHIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, db->device));
+    tbk_kmerdb_query *q = new tbk_kmerdb_query();
+    q->db = db; q->device = db->device; q->k = db->k;
+    q->with_copies = copies != 0;
+    q->prefix_bits = query_prefix_bits(db->n, db->k);
+    q->wave_slots = (uint64_t)std::max(cus, 1) * 32;  // 4 SIMDs x 8 waves per compute unit
+    hipError_t e = hipMalloc((void **)&q->d_dir, (((size_t)1 << q->prefix_bits) + 1) * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&q->d_seen, q->seen_bytes());
+    if (e == hipSuccess && q->with_copies) e = hipMalloc((void **)&q->d_copies, (size_t)(db->n + 1) * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&q->d_sums, TBK_QUERY_SUMS * sizeof(unsigned long long));
+    if (e == hipSuccess && !db->n) e = hipMalloc(&q->d_pad, 16);
+    if (e == hipSuccess && !db->n) e = hipMemsetAsync(q->d_pad, 0, 16, nullptr);
+    if (e == hipSuccess && db->n) e = tbk_launch_query_directory(db->d_keys, db->n, db->k, q->prefix_bits, q->d_dir, nullptr);
+    if (e == hipSuccess && !db->n) e = hipMemsetAsync(q->d_dir, 0, 2 * 4, nullptr);  // (P = 0: both offsets 0)
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        tbk_kmerdb_query_destroy(q);
+        (void)hipGetLastError();
+        return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "tbk_kmerdb_query_create (%llu k-mers): %s", (unsigned long long)db->n, hipGetErrorString(e));
+    }
+    rc = tbk_kmerdb_query_reset(q);
+    if (rc) { tbk_kmerdb_query_destroy(q); return rc; }
+    *out = q;
+    return TBK_OK;
+}
+
+// (test hook, not in tbk.h: the running total of window starts, so that the cap can be met without 4 G windows)
+extern "C" int tbk_kmerdb_query_set_windows_(tbk_kmerdb_query *q, uint64_t windows) {
+    if (!q) return cfail(TBK_ERR_INVALID, "query is NULL");
+    q->windows = windows;
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_query_add(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t min_count,
+                                    uint64_t *per_read, uint8_t *counts) {
+    if (!q) return cfail(TBK_ERR_INVALID, "query is NULL");
+    if (!n_reads) return TBK_OK;
+    int rc = tbk_check_offsets_(offsets, n_reads);
+    if (rc) return rc;
+    const uint64_t total = offsets[n_reads];
+    if (total && !bases) return cfail(TBK_ERR_INVALID, "bases is NULL");
+    uint64_t windows = 0;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t len = offsets[r + 1] - offsets[r];
+        if (len >= (uint64_t)q->k) windows += len - (uint64_t)q->k + 1;
+    }
+    if (windows > TBK_QUERY_MAX_WINDOWS || q->windows > TBK_QUERY_MAX_WINDOWS - windows)
+        return cfail(TBK_ERR_INVALID, "a query session takes at most 2^32 - 1 window starts: %llu so far, %llu in this batch (reset the session, or make another)",
+                     (unsigned long long)q->windows, (unsigned long long)windows);
+    if (per_read) memset(per_read, 0, n_reads * 2 * sizeof(uint64_t));
+    if (counts && total) memset(counts, 0, total);
+    if (!windows) return TBK_OK;
+    if ((rc = kmerdb_device(q->device))) return rc;
+    const uint64_t sep_total = total + n_reads;  // one 'N' behind every read
+    const uint64_t passes = tbk_probe_passes(sep_total);
+    if ((rc = query_reserve(q->bases, total + 16)) || (rc = query_reserve(q->offsets, (n_reads + 1) * 8)) || (rc = query_reserve(q->sep, sep_total + 16)) ||
+        (rc = query_reserve(q->clean_bits, passes * 64 * 4)) || (rc = query_reserve(q->found_bits, passes * 64 * 4)) ||
+        (rc = query_reserve(q->totals, n_reads * 2 * 8)))
+        return rc;
+    if (counts && ((rc = query_reserve(q->bytes, passes * 2048)) || (rc = query_reserve(q->counts, total)))) return rc;
+    CHIP(hipMemcpyAsync(q->bases.p, bases, total, hipMemcpyHostToDevice, nullptr));
+    CHIP(hipMemcpyAsync(q->offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, nullptr));
+    CHIP(tbk_launch_separate(q->bases.as<uint8_t>(), q->offsets.as<uint64_t>(), n_reads, q->sep.as<uint8_t>(), nullptr));
+    const tbk_kmerdb *db = q->db;
+    CHIP(tbk_launch_query_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, db->n ? db->d_keys : (const uint64_t *)q->d_pad,
+                                 db->n ? db->d_counts : (const uint8_t *)q->d_pad, q->d_dir, db->n, q->prefix_bits, std::max<uint32_t>(2, min_count),
+                                 q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(), counts ? q->bytes.as<uint8_t>() : nullptr, q->d_sums, q->d_seen,
+                                 q->with_copies ? q->d_copies : nullptr, q->wave_slots, nullptr));
+    q->windows += windows;  // (the launch is in the stream: what follows can only fail to bring the answers home)
+    CHIP(tbk_launch_query_totals(q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(), q->offsets.as<uint64_t>(), n_reads,
+                                 q->totals.as<unsigned long long>(), q->wave_slots, nullptr));
+    if (counts)
+        CHIP(tbk_launch_query_counts(q->bytes.as<uint8_t>(), q->offsets.as<uint64_t>(), n_reads, q->counts.as<uint8_t>(), q->wave_slots, nullptr));
+    if (per_read) CHIP(hipMemcpy(per_read, q->totals.p, n_reads * 2 * 8, hipMemcpyDeviceToHost));
+    if (counts) CHIP(hipMemcpy(counts, q->counts.p, total, hipMemcpyDeviceToHost));
+    if (!per_read && !counts) CHIP(hipStreamSynchronize(nullptr));  // (the caller's arrays are free to go)
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_query_histogram(tbk_kmerdb_query *q, uint64_t hist[256]) {
+    if (!q || !hist) return cfail(TBK_ERR_INVALID, "NULL argument");
+    const int rc = kmerdb_device(q->device);
+    if (rc) return rc;
+    CHIP(hipMemcpy(hist, q->d_sums, 256 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_query_completeness(tbk_kmerdb_query *q, uint32_t min_count, uint32_t max_count, uint64_t *seen, uint64_t *solid) {
+    if (!q || !seen || !solid) return cfail(TBK_ERR_INVALID, "NULL argument");
+    *seen = *solid = 0;
+    const uint32_t ci = std::max<uint32_t>(2, min_count), cx = std::min<uint32_t>(255, max_count);
+    if (!q->db->n || ci > cx) return TBK_OK;
+    const int rc = kmerdb_device(q->device);
+    if (rc) return rc;
+    unsigned long long *d_out = q->d_sums + 256, got[2] = {0, 0};
+    CHIP(hipMemsetAsync(d_out, 0, sizeof got, nullptr));
+    CHIP(tbk_launch_query_completeness(q->db->d_counts, q->d_seen, q->db->n, ci, cx, d_out, nullptr));
+    CHIP(hipMemcpy(got, d_out, sizeof got, hipMemcpyDeviceToHost));
+    *seen = got[0];
+    *solid = got[1];
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_query_copy_spectrum(tbk_kmerdb_query *q, uint64_t spec[6][256]) {
+    if (!q || !spec) return cfail(TBK_ERR_INVALID, "NULL argument");
+    if (!q->with_copies) return cfail(TBK_ERR_INVALID, "the query session was made without copies: it keeps no copy spectrum");
+    memset(spec, 0, 6 * 256 * sizeof(uint64_t));
+    if (!q->db->n) return TBK_OK;
+    const int rc = kmerdb_device(q->device);
+    if (rc) return rc;
+    unsigned long long *d_spec = q->d_sums + 256 + 2;
+    CHIP(hipMemsetAsync(d_spec, 0, 6 * 256 * sizeof(unsigned long long), nullptr));
+    CHIP(tbk_launch_query_spectrum(q->db->d_counts, q->d_copies, q->db->n, d_spec, nullptr));
+    CHIP(hipMemcpy(spec, d_spec, 6 * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return TBK_OK;
+}

@@ -443,12 +443,7 @@ tbk_db_unique_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restr
 // prints and write_list takes.  The kernels below make one from a counter, check one that came from a file
 // and subtract two.
 
-// the lexicographic rank (base 0 in the top bits of the 2k) of a key in the table's form
-__device__ __forceinline__ uint64_t lex_rank(uint64_t key, int k) {
-    const uint64_t lex = ((uint64_t)rev_pairs((uint32_t)key) << 32) | (uint64_t)rev_pairs((uint32_t)(key >> 32));
-    return lex >> (64 - 2 * k);
-}
-
+// (lex_rank, the lexicographic rank of a key in the table's form: tbk_device.h)
 // A live one-pass table to (rank, capped counter) pairs: tbk_count_distil_kernel without its stores to the
 // table, which is only read.  Appends are per wave; the order is the sort's business.
 __global__ void __launch_bounds__(256)
@@ -649,15 +644,7 @@ tbk_kmerdb_scatter_kernel(const uint64_t *__restrict__ a_keys, uint64_t n_a, con
 }
 
 // ---- three databases: the k-mers of A that B lacks and the child holds (tbk_kmerdb_inherited) -------------------
-// first element >= key among keys[lo .. hi), which ascend: hi when there is none
-__device__ __forceinline__ uint64_t db_lower_bound(const uint64_t *__restrict__ keys, uint64_t lo, uint64_t hi, uint64_t key) {
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
+// (db_lower_bound, the bisection of a database's ranks: tbk_device.h)
 // The flags and tile counts of tbk_kmerdb_flag_kernel for the three-way selection: counter of A in [ci, cx], not among
 // B's ranks, among the child's with a counter in [hi_ci, hi_cx] there.  A's ranks ascend within the tile, so every
 // entry's lower bound in B lies between those of the tile's first and last entry (i < n_a), and likewise in the child:

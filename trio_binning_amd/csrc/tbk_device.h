@@ -60,3 +60,18 @@ __device__ __forceinline__ uint32_t rev_pairs(uint32_t x) {
     return ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
 }
 
+// ---- count databases (tbk_kmerdb): shared by tbk_count_kernels.hip and tbk_query.hip ----------------------------
+// the lexicographic rank (base 0 in the top bits of the 2k) of a key in the table's form
+__device__ __forceinline__ uint64_t lex_rank(uint64_t key, int k) {
+    const uint64_t lex = ((uint64_t)rev_pairs((uint32_t)key) << 32) | (uint64_t)rev_pairs((uint32_t)(key >> 32));
+    return lex >> (64 - 2 * k);
+}
+
+// first element >= key among keys[lo .. hi), which ascend: hi when there is none
+__device__ __forceinline__ uint64_t db_lower_bound(const uint64_t *__restrict__ keys, uint64_t lo, uint64_t hi, uint64_t key) {
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}

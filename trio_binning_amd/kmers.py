@@ -1069,6 +1069,11 @@ class KmerDatabase:
             check(lib.tbk_kmerdb_inherited_table(self._h, other._h, child._h, min_count, max_count, child_min, child_max, C.byref(h)))
         return HashSet(h.value)
 
+    def query(self, copies: bool = False) -> "DatabaseQuery":
+        """A session that scores sequences against this database (``DatabaseQuery``); ``copies`` keeps a 32-bit counter
+        per entry for the copy spectrum (4 bytes per k-mer more)."""
+        return DatabaseQuery(self, copies)
+
     def close(self) -> None:
         if self._h is not None and self._h.value:
             h, self._h = self._h, None
@@ -1085,6 +1090,93 @@ class KmerDatabase:
             self.close()
         except Exception:
             pass
+
+
+class DatabaseQuery:
+    """How often did the reads see the k-mers of these sequences?  (``tbk_kmerdb_query``, include/tbk.h.)
+
+    Every window start of a sequence whose k bases are ACGT, either case, is *clean*; its canonical k-mer's counter in
+    the database is ``c``, 2..255, or 0 when the database does not hold it.  The session borrows the database and keeps
+    on its device a directory over the ranks, one *seen* bit per entry, the histogram of ``c`` over all clean windows
+    added so far and, with ``copies``, a copy counter per entry.  At most 2^32 - 1 window starts between two resets."""
+
+    def __init__(self, database: "KmerDatabase", copies: bool = False):
+        h = C.c_void_p()
+        check(lib.tbk_kmerdb_query_create(database._h, int(bool(copies)), C.byref(h)))
+        self._h = h
+        self._db = database  # keep the database alive
+        self.k = database.k
+        self.copies = bool(copies)
+
+    def add(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 2, return_counts: bool = False):
+        """Look a batch up and add it to the session.  (n, 2) uint64: per sequence its clean windows and, of those, the found
+        ones (``c >= min_count``).  With ``return_counts`` the pair (that array, the bytes of ``counts``) from one lookup."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.size - 1, 0)
+        per_read = np.zeros((n, 2), dtype=np.uint64)
+        counts = np.zeros(int(offsets[-1]) if offsets.size else 0, dtype=np.uint8) if return_counts else None
+        check(lib.tbk_kmerdb_query_add(self._h, bases.ctypes.data, offsets.ctypes.data, n, min_count, per_read.ctypes.data,
+                                       counts.ctypes.data if return_counts else None))
+        return (per_read, counts) if return_counts else per_read
+
+    def counts(self, bases: np.ndarray, offsets: np.ndarray) -> np.ndarray:
+        """One byte per base of the batch: ``c`` of the window that starts there, 0 when it is absent or not clean (a
+        sequence's last k - 1 bytes are 0).  This is ``add`` bringing other answers home: the batch is added to the session."""
+        return self.add(bases, offsets, 2, True)[1]
+
+    def histogram(self) -> np.ndarray:
+        """The clean windows added so far by their counter, 256 rows; row 0: absent."""
+        hist = np.zeros(256, dtype=np.uint64)
+        check(lib.tbk_kmerdb_query_histogram(self._h, hist.ctypes.data))
+        return hist
+
+    def completeness(self, min_count: int = 2, max_count: int = 255) -> Tuple[int, int]:
+        """(seen, solid): the database's k-mers with a counter in [min_count, max_count] (clamped to 2..255), and those of
+        them that a window added so far was."""
+        seen, solid = C.c_uint64(), C.c_uint64()
+        check(lib.tbk_kmerdb_query_completeness(self._h, min_count, max_count, C.byref(seen), C.byref(solid)))
+        return seen.value, solid.value
+
+    def copy_spectrum(self) -> np.ndarray:
+        """(6, 256) uint64: ``[min(copies, 5), counter]`` = k-mers of the database that the sequences hold that many times
+        (row 5: more than four) - the assembly's k-mer spectrum.  ``ValueError`` for a session made without ``copies``."""
+        spec = np.zeros((6, 256), dtype=np.uint64)
+        check(lib.tbk_kmerdb_query_copy_spectrum(self._h, spec.ctypes.data))
+        return spec
+
+    def reset(self) -> None:
+        """Forget every batch: the next assembly against the same database."""
+        check(lib.tbk_kmerdb_query_reset(self._h))
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            h, self._h = self._h, None
+            lib.tbk_kmerdb_query_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def qv(found: int, clean: int, k: int) -> float:
+    """Merqury's consensus quality value from k-mer counts: ``-10 log10(1 - (found / clean) ** (1 / k))`` - ``inf`` when
+    every clean window was found, ``nan`` when there is none."""
+    import math
+
+    if clean == 0:
+        return float("nan")
+    if found >= clean:
+        return float("inf")
+    return -10.0 * math.log10(1.0 - (found / clean) ** (1.0 / k)) + 0.0  # (+ 0.0: nothing found is 0.0, not -0.0)
 
 
 def pinned_empty(shape, dtype) -> np.ndarray:
