@@ -647,8 +647,12 @@ typedef struct tbk_counter_options {
     int32_t passes;             /* >= 1 */
     uint64_t store_limit_bytes; /* most the kept reads may take; 0: whatever HBM gives.  A batch that would pass
                                  * it (or that HBM cannot take) is TBK_ERR_NOMEM; nothing spills to the host. */
+    int32_t compress;           /* != 0: count in homopolymer-compressed space (tbk_hpc below, fold_case = 1): every batch,
+                                 * host or device, is compressed before it is separated; in passes mode the kept reads are
+                                 * the compressed ones.  reads_added counts the reads as given, bases_added the bases after
+                                 * compression, the ones windows came from.  A caller with the older, shorter struct gets 0. */
 } tbk_counter_options;
-void tbk_counter_options_init(tbk_counter_options *o);  /* passes = 1, no limit */
+void tbk_counter_options_init(tbk_counter_options *o);  /* passes = 1, no limit, no compression */
 /* opts may be NULL (= tbk_counter_create). */
 int tbk_counter_create_opts(int k, uint64_t capacity_kmers, const tbk_counter_options *opts, int device, tbk_counter **out);
 /* No more batches: adding to a finished counter is TBK_ERR_INVALID.  With passes > 1 this counts the remaining
@@ -691,7 +695,8 @@ int tbk_counter_params(const tbk_counter *c, int *w, int *m, int *o, int *t);
 /* kmers_subtract + kmc_dump: write to out_path, one k-mer per line in lexicographic order, the
  * k-mers of `a` seen at least twice whose counter lies in [min_count, max_count] and that `b` has
  * seen at most once.  Both counters must work in the same number of passes (TBK_ERR_INVALID otherwise: their
- * classes would not match); counters working in passes are finished first, and the file is the same. */
+ * classes would not match); counters working in passes are finished first, and the file is the same.  A compressing
+ * counter against a plain one is TBK_ERR_INVALID too: their k-mers live in different spaces. */
 int tbk_counter_unique(tbk_counter *a, tbk_counter *b, uint32_t min_count, uint32_t max_count, const char *out_path,
                        uint64_t *n_written);
 
@@ -714,7 +719,11 @@ void tbk_kmerdb_destroy(tbk_kmerdb *db);
 /* The file (*.tbkdb, little-endian; INTEGRATION.md has the table): a 2096-byte header - magic "TBKKMDB1", header
  * size, k, n, reads, bases, the histogram, CRC-32 of all that, a zero word - then n keys, then n counters: exactly
  * 2096 + 9n bytes.  Written to path + ".tmp" in pieces and renamed, so an interrupted save leaves no file of the
- * right name; no time stamp, no host name: equal databases give equal bytes. */
+ * right name; no time stamp, no host name: equal databases give equal bytes.
+ * The database of a compressing counter (tbk_counter_options.compress) is a different thing from a plain one of the
+ * same k, and its file says so: magic "TBKKMDH1", otherwise the identical layout - a build that does not know
+ * compressed databases refuses the file instead of mixing the two spaces.  tbk_counter_export carries the flag,
+ * tbk_kmerdb_save writes the matching magic, tbk_kmerdb_load accepts both and remembers which it was. */
 int tbk_kmerdb_save(const tbk_kmerdb *db, const char *path);
 /* A file is checked before it is used.  On the host: magic, header size, k in 1..32, CRC, zero pad, file size
  * against n, sum(hist[2..255]) == n, hist[0] >= hist[1] + n.  On the device, in one pass before anything
@@ -724,6 +733,10 @@ int tbk_kmerdb_save(const tbk_kmerdb *db, const char *path);
 int tbk_kmerdb_load(const char *path, int device, tbk_kmerdb **out);
 /* The header alone, with the host-side checks above; needs no device.  Any out pointer may be NULL. */
 int tbk_kmerdb_file_info(const char *path, int *k, uint64_t *n, uint64_t hist[256], uint64_t *reads, uint64_t *bases);
+/* *flag = 1 when the database was counted in homopolymer-compressed space, else 0: of a database in HBM, and of a file
+ * (the host-side checks of tbk_kmerdb_file_info; needs no device). */
+int tbk_kmerdb_compressed(const tbk_kmerdb *db, int *flag);
+int tbk_kmerdb_file_compressed(const char *path, int *flag);
 /* bytes: HBM the database holds (9n).  Any out pointer may be NULL. */
 int tbk_kmerdb_info(const tbk_kmerdb *db, int *k, uint64_t *n, int *device, uint64_t *bytes);
 int tbk_kmerdb_stats(const tbk_kmerdb *db, uint64_t *reads_added, uint64_t *bases_added);
@@ -733,7 +746,9 @@ int tbk_kmerdb_histogram(const tbk_kmerdb *db, uint64_t hist[256]);
 int tbk_kmerdb_read(const tbk_kmerdb *db, uint64_t first, uint64_t count, uint64_t *keys, uint8_t *counts);
 /* tbk_counter_unique between two databases: the k-mers of `a` whose counter lies in [max(2, min_count),
  * min(255, max_count)] and that `b` does not hold, one per line in lexicographic order - the same file.  An
- * empty range or an empty `a` gives an empty file and TBK_OK; a different k or device is TBK_ERR_INVALID. */
+ * empty range or an empty `a` gives an empty file and TBK_OK; a different k or device is TBK_ERR_INVALID, and so
+ * is a compressed database against a plain one - here and in the three calls below, the child's database included -
+ * with the reason in tbk_last_error(). */
 int tbk_kmerdb_unique(const tbk_kmerdb *a, const tbk_kmerdb *b, uint32_t min_count, uint32_t max_count, const char *out_path,
                       uint64_t *n_written);
 /* The same selection as a k-mer list in HBM on the databases' device, without the text: for every consumer
@@ -765,6 +780,37 @@ int tbk_kmerdb_inherited(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kme
                          uint32_t child_min, uint32_t child_max, const char *out_path, uint64_t *n_written);
 int tbk_kmerdb_inherited_table(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kmerdb *child, uint32_t min_count, uint32_t max_count,
                                uint32_t child_min, uint32_t child_max, tbk_table **out);
+
+/* ---- homopolymer compression: every run of equal bases written once, before k-mers are cut --------------------
+ * The dominant error of ONT and HiFi reads is the length of a homopolymer run; pipelines beside this one bin in
+ * homopolymer-compressed space for that reason (meryl `count compress`, Canu's and Verkko's trio modes): parental
+ * libraries and reads then agree wherever they differ in run length only.
+ * compress(read, fold_case) keeps byte i of a read iff i == 0 or f(b[i]) != f(b[i-1]).  With fold_case, f clears bit
+ * 5 of ASCII letters (a compares equal to A); without it f is the identity.  A kept byte is written verbatim: the
+ * first byte of its run, in its own case.  A run never crosses a read boundary.  Bytes outside ACGT are compared like
+ * any others (NNNN becomes N, which still breaks windows downstream).  An empty read stays empty; read count and order
+ * are unchanged.  The counter folds case (fold_case = 1); the classifier does not (0: lower case stays not-ACGT).
+ * A session lives on one device and owns a stream and its buffers, which grow to the largest batch seen; one batch at
+ * a time per session.  The result is a batch in the usual layout, left in HBM: bases back to back (16-byte aligned,
+ * 64 zero bytes behind the last), uint64 offsets with offsets[0] == 0 - what tbk_classify_device,
+ * tbk_stream_submit_device and tbk_counter_add_device take.  Both compress calls return when the result is complete;
+ * it is valid until the session's next call.  n_reads == 0 or no bases at all: TBK_OK and an empty result.  Offsets
+ * that do not ascend (for a device batch: not from 0 to total_bases; checked on the device, nothing is written out of
+ * bounds): TBK_ERR_INVALID.  TBK_ERR_NOMEM leaves the session usable.  After an error the out pointers are NULL.
+ * On the device (csrc/tbk_hpc.hip): one bit per base for read starts; one bit per base for `keep` and a count per
+ * tile of 4096 bases, read as 16-byte vectors; an exclusive scan of the tile counts; a scatter of the kept bytes; one
+ * thread per read turning offsets[r] into its rank among the kept bits.  No block waits for another. */
+typedef struct tbk_hpc tbk_hpc;
+int tbk_hpc_create(int device, tbk_hpc **out);
+void tbk_hpc_destroy(tbk_hpc *h);
+int tbk_hpc_compress(tbk_hpc *h, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int fold_case, void **d_bases,
+                     void **d_offsets, uint64_t *total_out);
+/* The same for a batch already in HBM: d_bases 16-byte aligned and readable up to total_bases, d_offsets[n_reads] == total_bases. */
+int tbk_hpc_compress_device(tbk_hpc *h, const void *d_bases, const void *d_offsets, uint64_t n_reads, uint64_t total_bases, int fold_case,
+                            void **d_bases_out, void **d_offsets_out, uint64_t *total_out);
+/* The last result to host memory: total_out bytes to `bases` (cap: its room; too little is TBK_ERR_INVALID) and
+ * n_reads + 1 offsets to `offsets` (may be NULL). */
+int tbk_hpc_fetch(tbk_hpc *h, uint8_t *bases, uint64_t cap, uint64_t *offsets);
 
 /* ---- hit tracker: WHERE along a sequence the haplotype k-mers lie ------------------------ */
 /* The classifier answers with two numbers per read; the tracker keeps the positions.  A window start is a MARKER of

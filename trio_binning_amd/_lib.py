@@ -176,7 +176,7 @@ _sig("tbk_counter_destroy", None, _vp)
 
 class CounterOptions(C.Structure):
     """tbk_counter_options (include/tbk.h)."""
-    _fields_ = [("size", C.c_uint32), ("passes", C.c_int32), ("store_limit_bytes", C.c_uint64)]
+    _fields_ = [("size", C.c_uint32), ("passes", C.c_int32), ("store_limit_bytes", C.c_uint64), ("compress", C.c_int32)]
 
 
 class CounterInfo(C.Structure):
@@ -216,6 +216,15 @@ if HAS_KMERDB:
     if hasattr(lib, "tbk_kmerdb_inherited"):
         _sig("tbk_kmerdb_inherited", C.c_int, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, _u64p)
         _sig("tbk_kmerdb_inherited_table", C.c_int, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp))
+HAS_HPC = hasattr(lib, "tbk_hpc_create")  # (variant builds of tools/build_variant.sh may predate homopolymer compression)
+if HAS_HPC:
+    _sig("tbk_hpc_create", C.c_int, C.c_int, C.POINTER(_vp))
+    _sig("tbk_hpc_destroy", None, _vp)
+    _sig("tbk_hpc_compress", C.c_int, _vp, _vp, _vp, _u64, C.c_int, C.POINTER(_vp), C.POINTER(_vp), _u64p)
+    _sig("tbk_hpc_compress_device", C.c_int, _vp, _vp, _vp, _u64, _u64, C.c_int, C.POINTER(_vp), C.POINTER(_vp), _u64p)
+    _sig("tbk_hpc_fetch", C.c_int, _vp, _vp, _u64, _vp)
+    _sig("tbk_kmerdb_compressed", C.c_int, _vp, C.POINTER(C.c_int))
+    _sig("tbk_kmerdb_file_compressed", C.c_int, C.c_char_p, C.POINTER(C.c_int))
 HAS_HIT_TRACKER = hasattr(lib, "tbk_hit_tracker_create")  # (variant builds of tools/build_variant.sh may predate the hit tracker)
 if HAS_HIT_TRACKER:
     _sig("tbk_hit_tracker_create", C.c_int, _vp, _vp, C.POINTER(_vp))

@@ -76,6 +76,9 @@ def parse_args(argv=None):
         args.info = kmers.database_file_info(args.database)
     except (IOError, ValueError) as exc:
         sys.exit("{}: {}: {}".format(PROG, args.database, exc))
+    if args.info["compressed"]:
+        sys.exit("{}: {} holds homopolymer-compressed k-mers (find-unique-kmers --compress): a QV is not defined in compressed "
+                 "space. Give a plain database.".format(PROG, args.database))
     return args
 
 

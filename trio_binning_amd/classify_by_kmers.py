@@ -37,8 +37,9 @@ class DatabasePair:
     database (``child_path``, its counts from ``child_min`` on) the lists hold only what the child inherited."""
 
     def __init__(self, path_a: str, path_b: str, range_a: Tuple[int, int], range_b: Tuple[int, int],
-                 child_path: Optional[str] = None, child_min: int = 2, prog: str = "classify-by-kmers"):
+                 child_path: Optional[str] = None, child_min: int = 2, prog: str = "classify-by-kmers", compressed: bool = False):
         self.prog = prog  # the command its refusals speak for
+        self.compressed = compressed  # what the headers say, all alike: the databases hold homopolymer-compressed k-mers
         self.paths = {"A": path_a, "B": path_b}
         self.ranges = {"A": range_a, "B": range_b}
         self.child_path, self.child_min = child_path, child_min
@@ -108,6 +109,11 @@ def _parser(kmer_list_type) -> argparse.ArgumentParser:
     parser.add_argument("--haplotype-b-out-prefix", default="hapB", help="prefix for haplotype B output file")
     parser.add_argument("--unclassified-out-prefix", default="unclassified", help="prefix for unclassified output file")
     parser.add_argument("--no-gzip-output", action="store_true", default=False, help="don't gzip the output")
+    parser.add_argument(
+        "--compress", action="store_true", default=False,
+        help="k-mer lists made by find-unique-kmers --compress: every run of equal bases of a read is written once before it is "
+             "probed (the bins still hold the reads as they came). Count databases say by themselves which space they are in",
+    )
     _add_database_options(parser)
     return parser
 
@@ -140,9 +146,17 @@ def _settle_databases(args, prog: str = "classify-by-kmers") -> DatabasePair:
     infos = {hap: kmers.database_file_info(paths[hap]) for hap in "AB"}
     if infos["A"]["k"] != infos["B"]["k"]:
         sys.exit(prog + ": {} holds {}-mers, but {} holds {}-mers".format(paths["A"], infos["A"]["k"], paths["B"], infos["B"]["k"]))
+    spaces = {False: "plain (uncompressed)", True: "homopolymer-compressed"}
+    compressed = infos["A"]["compressed"]
+    if infos["B"]["compressed"] != compressed:
+        sys.exit(prog + ": {} holds {} k-mers, but {} holds {} ones: count both parents the same way".format(
+            paths["A"], spaces[compressed], paths["B"], spaces[not compressed]))
     child_info = None
     if args.child_database is not None:
         child_info = kmers.database_file_info(args.child_database)
+        if child_info["compressed"] != compressed:
+            sys.exit(prog + ": {} holds {} k-mers, but the child's {} holds {} ones: count all three the same way".format(
+                paths["A"], spaces[compressed], args.child_database, spaces[not compressed]))
         if child_info["k"] != infos["A"]["k"]:
             sys.exit(prog + ": {} holds {}-mers, but {} holds {}-mers".format(
                 paths["A"], infos["A"]["k"], args.child_database, child_info["k"]))
@@ -169,8 +183,35 @@ def _settle_databases(args, prog: str = "classify-by-kmers") -> DatabasePair:
                      "give it with --min-count-child.".format(args.child_database))
     if child_info is not None:
         print("\033[92mUsing counts in range [{},255] for the child.\033[0m".format(child_min), file=sys.stderr)
-        return DatabasePair(paths["A"], paths["B"], ranges["A"], ranges["B"], args.child_database, int(child_min), prog=prog)
-    return DatabasePair(paths["A"], paths["B"], ranges["A"], ranges["B"], prog=prog)
+        return DatabasePair(paths["A"], paths["B"], ranges["A"], ranges["B"], args.child_database, int(child_min), prog=prog, compressed=compressed)
+    return DatabasePair(paths["A"], paths["B"], ranges["A"], ranges["B"], prog=prog, compressed=compressed)
+
+
+def refuse_compressed(databases: Optional[DatabasePair], prog: str) -> None:
+    """For the commands that report coordinates or a QV: neither is defined in homopolymer-compressed space."""
+    if databases is not None and databases.compressed:
+        sys.exit(prog + ": {} and {} hold homopolymer-compressed k-mers (find-unique-kmers --compress): positions along a "
+                 "sequence are not defined in compressed space. Give plain databases.".format(databases.paths["A"], databases.paths["B"]))
+
+
+_LIST_LINES_CHECKED = 1000
+
+
+def check_compressed_list(list_path: str, prog: str = "classify-by-kmers") -> None:
+    """A k-mer with two equal adjacent bases cannot occur in a compressed read: a list that has one among its first
+    lines was made without --compress, and every read would score (0, 0) against it."""
+    try:
+        fh = open(list_path, "r", errors="replace")
+    except OSError:
+        return  # (the table's own constructor reports a file that cannot be read, in the usual words)
+    with fh:
+        for number, line in enumerate(fh, 1):
+            if number > _LIST_LINES_CHECKED:
+                break
+            kmer = line.strip().upper()
+            if any(x == y for x, y in zip(kmer, kmer[1:])):
+                sys.exit(prog + ": --compress: line {} of {} ({}) has two equal adjacent bases: this list was not made with --compress".format(
+                    number, list_path, kmer))
 
 
 def parse_args():
@@ -184,7 +225,14 @@ def parse_args():
     args = parser.parse_args()
     if _check_kmer_arguments(parser, args):
         args.databases = _settle_databases(args)
+        if args.compress and not args.databases.compressed:
+            sys.exit("classify-by-kmers: --compress was given, but {} and {} hold plain (uncompressed) k-mers: count the parents "
+                     "with find-unique-kmers --compress".format(args.haplotype_a_kmers, args.haplotype_b_kmers))
+        args.compress = args.databases.compressed  # the mode follows the headers
         return args
+    if args.compress:
+        for list_path in (args.haplotype_a_kmers, args.haplotype_b_kmers):
+            check_compressed_list(list_path)
     args = _parser(kmers.create_kmer_hash_set).parse_args()
     args.databases = None
     return args
@@ -249,6 +297,80 @@ def make_classifier(haplotype_a_kmers, haplotype_b_kmers):
     return classifier
 
 
+def classify_compressed(args, num_a: int, num_b: int) -> dict:
+    """The loop in homopolymer-compressed space, in Python over native pieces as phase_blocks runs its own: the reader
+    fills a batch, a compressor session writes every run of equal bases once on the device (case as it came: lower case
+    stays not-ACGT for the probe), the classifier probes the compressed batch where it lies, and the ORIGINAL batch is
+    scored, binned, printed and written.  Two batches and two sessions take turns, so batch i + 1 is read and compressed
+    while batch i is probed.  One device: the first of TBK_DEVICES."""
+    import time
+
+    import numpy as np
+
+    devices = kmers.visible_devices()
+    if len(devices) > 1:
+        print("classify-by-kmers: compressed mode runs on one device; using device {} of {}.".format(devices[0], devices), file=sys.stderr)
+    options = kmers.Options.from_env() if _lib.HAS_OPTIONS else None
+    spent = {"read_s": 0.0, "compress_s": 0.0, "probe_wait_s": 0.0, "write_s": 0.0, "bases": 0, "compressed_bases": 0, "reads": 0}
+    t_start = time.perf_counter()
+    classifier = kmers.Classifier(args.haplotype_a_kmers, args.haplotype_b_kmers, options=options)
+    spent["table_build_s"] = time.perf_counter() - t_start
+    device = classifier.device
+    print("Classifying in homopolymer-compressed space: the reads are compressed on device {} before they are probed.".format(device), file=sys.stderr)
+    gzip_output = not args.no_gzip_output
+    writer = seq.BinWriter(args.haplotype_a_out_prefix, args.haplotype_b_out_prefix, args.unclassified_out_prefix, output_extension(args.reads),
+                           gzip_output, int(os.environ.get("TBK_GZIP_LEVEL", "-1")), device=device if gzip_output else None)
+    batches = [seq.Batch(), seq.Batch()]
+    sessions = [kmers.HomopolymerCompressor(device), kmers.HomopolymerCompressor(device)]
+    out = sys.stdout
+
+    def finish(ticket, batch):
+        t0 = time.perf_counter()
+        counts = classifier.wait(ticket)
+        t1 = time.perf_counter()
+        score_a, score_b, bins = kmers.score_and_bin(counts, num_a, num_b)
+        out.write(seq.format_tsv(batch, bins, score_a, score_b))
+        writer.write(batch, bins)
+        spent["probe_wait_s"] += t1 - t0
+        spent["write_s"] += time.perf_counter() - t1
+
+    try:
+        with seq.BatchReader(args.reads) as reader:
+            pending, turn = None, 0
+            while True:
+                batch, session = batches[turn], sessions[turn]
+                t0 = time.perf_counter()
+                n = reader.next_batch(batch, _BATCH_BASES, _BATCH_READS)
+                t1 = time.perf_counter()
+                spent["read_s"] += t1 - t0
+                if not n:
+                    break
+                d_bases, d_offsets, total = session.compress_batch(batch, False)
+                spent["compress_s"] += time.perf_counter() - t1
+                spent["reads"] += n
+                spent["bases"] += int(batch.arrays()[1][-1])
+                spent["compressed_bases"] += total
+                ticket = classifier.submit_device(d_bases, d_offsets, n, total, np.zeros((n, 2), dtype=np.int32))
+                if pending is not None:
+                    finish(*pending)
+                pending, turn = (ticket, batch), 1 - turn
+            if pending is not None:
+                finish(*pending)
+        out.flush()
+        t0 = time.perf_counter()
+        writer.close()
+        spent["write_s"] += time.perf_counter() - t0
+    finally:
+        for session in sessions:
+            session.close()
+        for batch in batches:
+            batch.close()
+        classifier.close()
+    spent["total_s"] = time.perf_counter() - t_start
+    spent["devices"] = [device]
+    return spent
+
+
 def main():
     """Main method of program"""
     args = parse_args()
@@ -257,6 +379,14 @@ def main():
 
     num_a = kmers.get_number_kmers_in_set(args.haplotype_a_kmers)
     num_b = kmers.get_number_kmers_in_set(args.haplotype_b_kmers)
+    if args.compress:
+        stats = classify_compressed(args, num_a, num_b)
+        if os.environ.get("TBK_STATS"):
+            import json
+
+            stats["gbases_per_s"] = stats["bases"] / stats["total_s"] / 1e9 if stats["total_s"] > 0 else 0.0
+            print("tbk-stats " + json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in stats.items()}), file=sys.stderr)
+        return
     import time
 
     t_start = time.perf_counter()

@@ -104,6 +104,8 @@ struct tbk_counter {
     unsigned long long *d_hist = nullptr;       // running histogram of the classes distilled so far
     uint64_t hist[256] = {0};                   // its host copy
     uint64_t distinct_done = 0;                 // distinct k-mers of the classes distilled so far
+    bool compress = false;                      // tbk_counter_options.compress: the k-mers are those of the homopolymer-compressed reads
+    tbk_hpc *hpc = nullptr;                     // its session: every batch goes through it (freed with the store when a counter in passes finishes)
 };
 
 static int counter_device(const tbk_counter *c) {
@@ -170,6 +172,11 @@ extern "C" int tbk_counter_create_opts(int k, uint64_t capacity_kmers, const tbk
     tbk_counter *c = new tbk_counter();
     c->device = device; c->k = k;
     c->passes = o.passes; c->store_limit = o.store_limit_bytes;
+    c->compress = o.compress != 0;
+    if (c->compress) {
+        const int made = tbk_hpc_create(device, &c->hpc);
+        if (made) { delete c; return made; }
+    }
     if (c->passes > 1) capacity_kmers = std::max<uint64_t>(1, capacity_kmers / (uint64_t)c->passes);  // the table holds one class
     const char *ev = getenv("TBK_COUNT_LOAD");
     c->load = ev ? atof(ev) : 0.6;
@@ -225,6 +232,7 @@ extern "C" void tbk_counter_destroy(tbk_counter *c) {
             if (d.d_counts) (void)hipFree(d.d_counts);
         }
     }
+    tbk_hpc_destroy(c->hpc);
     delete c;
 }
 
@@ -366,6 +374,8 @@ static int counter_finish(tbk_counter *c) {
         *p = nullptr;
     }
     c->n_buckets = 0; c->cap_raw = 0; c->cap_sep = 0; c->cap_reads = 0;
+    tbk_hpc_destroy(c->hpc);
+    c->hpc = nullptr;
     c->broken = false;
     c->finished = true;
     return TBK_OK;
@@ -377,6 +387,14 @@ extern "C" int tbk_counter_finish(tbk_counter *c) {
 }
 
 static int counter_run(tbk_counter *c, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t total) {
+    if (c->hpc) {
+        // compressed space: the batch that is separated, counted and (in passes mode) kept is the compressed one
+        void *d_cb = nullptr, *d_co = nullptr;
+        const int rc = tbk_hpc_compress_device(c->hpc, d_bases, d_offsets, n_reads, total, 1, &d_cb, &d_co, &total);
+        if (rc) return rc;
+        d_bases = (const uint8_t *)d_cb;
+        d_offsets = (const uint64_t *)d_co;
+    }
     const size_t need_sep = (size_t)total + n_reads + 64;
     if (need_sep > c->cap_sep) {
         if (c->d_sep) CHIP(hipFree(c->d_sep));
@@ -573,6 +591,8 @@ extern "C" int tbk_counter_unique(tbk_counter *a, tbk_counter *b, uint32_t min_c
     if (a->device != b->device) return cfail(TBK_ERR_INVALID, "the counters live on different devices");
     if (a->passes != b->passes)
         return cfail(TBK_ERR_INVALID, "the counters count in different numbers of passes (%d and %d): their classes do not match", a->passes, b->passes);
+    if (a->compress != b->compress)
+        return cfail(TBK_ERR_INVALID, "one counter counts homopolymer-compressed k-mers, the other plain ones: they cannot be subtracted");
     *n_written = 0;
     int rc = counter_device(a);
     if (rc) return rc;
@@ -653,7 +673,15 @@ struct tbk_kmerdb {
     uint8_t *d_counts = nullptr;  // their counters, 2..255
     uint64_t hist[256] = {0};     // the counter's whole histogram (tbk_counter_histogram)
     uint64_t reads_added = 0, bases_added = 0;
+    bool compressed = false;      // counted in homopolymer-compressed space: another magic in the file, no mixing with plain ones
 };
+
+// two databases in different spaces share no k-mer worth comparing
+static int kmerdb_same_space(const tbk_kmerdb *a, const tbk_kmerdb *b, const char *what_b) {
+    if (a->compressed == b->compressed) return TBK_OK;
+    return cfail(TBK_ERR_INVALID, "the first database holds %s k-mers, %s %s ones: they cannot be compared",
+                 a->compressed ? "homopolymer-compressed" : "plain", what_b, b->compressed ? "homopolymer-compressed" : "plain");
+}
 
 static int kmerdb_device(int device) {
     int n = 0;
@@ -689,6 +717,7 @@ extern "C" int tbk_counter_export(tbk_counter *c, tbk_kmerdb **out) {
     tbk_kmerdb *db = new tbk_kmerdb();
     db->device = c->device; db->k = c->k; db->n = n;
     db->reads_added = c->reads_added; db->bases_added = c->bases_added;
+    db->compressed = c->compress;
     memcpy(db->hist, hist, sizeof hist);
     if (n) {
         // the pairs as they come out of the table or the classes, then ordered by rank into the database's own arrays
@@ -730,11 +759,13 @@ extern "C" int tbk_counter_export(tbk_counter *c, tbk_kmerdb **out) {
 
 // ---- the file (*.tbkdb; INTEGRATION.md has the table) ---------------------------------------------------------------------
 static const char TBK_KMERDB_MAGIC[8] = {'T', 'B', 'K', 'K', 'M', 'D', 'B', '1'};
+static const char TBK_KMERDB_MAGIC_HPC[8] = {'T', 'B', 'K', 'K', 'M', 'D', 'H', '1'};  // a compressed database: the same layout under another name
 constexpr size_t TBK_KMERDB_HEADER = 2096;
 
 struct KmerdbHeader {
     int k = 0;
     uint64_t n = 0, reads = 0, bases = 0, hist[256] = {0};
+    bool compressed = false;
 };
 
 // little-endian hosts only (as the rest of the library: x86-64 beside the MI355X)
@@ -771,7 +802,8 @@ static int kmerdb_read_header(int fd, const char *path, KmerdbHeader *h) {
     if (size < TBK_KMERDB_HEADER) return cfail(TBK_ERR_FORMAT, "%s: %llu bytes are less than the header of a k-mer database (%zu)", path, (unsigned long long)size, TBK_KMERDB_HEADER);
     uint8_t b[TBK_KMERDB_HEADER];
     if (!read_all(fd, b, sizeof b)) return cfail(TBK_ERR_IO, "%s: cannot read the header: %s", path, strerror(errno));
-    if (memcmp(b, TBK_KMERDB_MAGIC, 8) != 0) return cfail(TBK_ERR_FORMAT, "%s: not a k-mer database (magic)", path);
+    h->compressed = memcmp(b, TBK_KMERDB_MAGIC_HPC, 8) == 0;
+    if (!h->compressed && memcmp(b, TBK_KMERDB_MAGIC, 8) != 0) return cfail(TBK_ERR_FORMAT, "%s: not a k-mer database (magic)", path);
     if (get_le<uint32_t>(b + 8) != TBK_KMERDB_HEADER) return cfail(TBK_ERR_FORMAT, "%s: header size %u, expected %zu", path, get_le<uint32_t>(b + 8), TBK_KMERDB_HEADER);
     const uint32_t k = get_le<uint32_t>(b + 12);
     if (k < 1 || k > 32) return cfail(TBK_ERR_FORMAT, "%s: k = %u out of range (1..32)", path, k);
@@ -813,6 +845,24 @@ extern "C" int tbk_kmerdb_file_info(const char *path, int *k, uint64_t *n, uint6
     return TBK_OK;
 }
 
+extern "C" int tbk_kmerdb_file_compressed(const char *path, int *flag) {
+    if (!path || !flag) return cfail(TBK_ERR_INVALID, "NULL argument");
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return cfail(TBK_ERR_IO, "cannot open %s: %s", path, strerror(errno));
+    KmerdbHeader h;
+    const int rc = kmerdb_read_header(fd, path, &h);
+    ::close(fd);
+    if (rc) return rc;
+    *flag = h.compressed ? 1 : 0;
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_compressed(const tbk_kmerdb *db, int *flag) {
+    if (!db || !flag) return cfail(TBK_ERR_INVALID, "NULL argument");
+    *flag = db->compressed ? 1 : 0;
+    return TBK_OK;
+}
+
 constexpr uint64_t TBK_KMERDB_PIECE = (uint64_t)1 << 22;  // k-mers per piece of a save or a load
 
 extern "C" int tbk_kmerdb_save(const tbk_kmerdb *db, const char *path) {
@@ -823,7 +873,7 @@ extern "C" int tbk_kmerdb_save(const tbk_kmerdb *db, const char *path) {
     }
     uint8_t b[TBK_KMERDB_HEADER];
     memset(b, 0, sizeof b);
-    memcpy(b, TBK_KMERDB_MAGIC, 8);
+    memcpy(b, db->compressed ? TBK_KMERDB_MAGIC_HPC : TBK_KMERDB_MAGIC, 8);
     put_le<uint32_t>(b + 8, (uint32_t)TBK_KMERDB_HEADER);
     put_le<uint32_t>(b + 12, (uint32_t)db->k);
     put_le<uint64_t>(b + 16, db->n);
@@ -870,6 +920,7 @@ extern "C" int tbk_kmerdb_load(const char *path, int device, tbk_kmerdb **out) {
     tbk_kmerdb *db = new tbk_kmerdb();
     db->device = device; db->k = h.k; db->n = h.n;
     db->reads_added = h.reads; db->bases_added = h.bases;
+    db->compressed = h.compressed;
     memcpy(db->hist, h.hist, sizeof h.hist);
     if (h.n) {
         unsigned long long *d_tally = nullptr, tally[3 + 256];
@@ -956,6 +1007,7 @@ extern "C" int tbk_kmerdb_unique(const tbk_kmerdb *a, const tbk_kmerdb *b, uint3
     if (!a || !b || !out_path || !n_written) return cfail(TBK_ERR_INVALID, "NULL argument");
     if (a->k != b->k) return cfail(TBK_ERR_INVALID, "the databases have different k (%d and %d)", a->k, b->k);
     if (a->device != b->device) return cfail(TBK_ERR_INVALID, "the databases live on different devices");
+    if (kmerdb_same_space(a, b, "the second")) return TBK_ERR_INVALID;
     *n_written = 0;
     // upper bound of what can come out: k-mers of A with a counter in range
     uint64_t cap = 0;
@@ -1014,6 +1066,7 @@ extern "C" int tbk_kmerdb_unique_table(const tbk_kmerdb *a, const tbk_kmerdb *b,
     *out = nullptr;
     if (a->k != b->k) return cfail(TBK_ERR_INVALID, "the databases have different k (%d and %d)", a->k, b->k);
     if (a->device != b->device) return cfail(TBK_ERR_INVALID, "the databases live on different devices");
+    if (kmerdb_same_space(a, b, "the second")) return TBK_ERR_INVALID;
     // upper bound of what can come out, as in tbk_kmerdb_unique: none in range means nothing to launch
     uint64_t cap = 0;
     for (uint32_t cnt = std::max<uint32_t>(2, min_count); cnt <= std::min<uint32_t>(255, max_count); cnt++) cap += a->hist[cnt];
@@ -1062,6 +1115,7 @@ static int inherited_check(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_k
     if (a->k != b->k || a->k != child->k)
         return cfail(TBK_ERR_INVALID, "the databases have different k (%d, %d and the child's %d)", a->k, b->k, child->k);
     if (a->device != b->device || a->device != child->device) return cfail(TBK_ERR_INVALID, "the databases live on different devices");
+    if (kmerdb_same_space(a, b, "the second") || kmerdb_same_space(a, child, "the child's")) return TBK_ERR_INVALID;
     return TBK_OK;
 }
 

@@ -81,6 +81,13 @@ def parse_args(argv=None):
         help="lower count cut-off of the child chosen by hand (the upper one is 255): its histogram is written but not analyzed",
     )
     parser.add_argument(
+        "--compress", action="store_true",
+        help="count in homopolymer-compressed space: every run of equal bases of a read is written once before k-mers are cut "
+             "(for parents that will bin ONT or HiFi reads, whose dominant error is the length of such runs). Both parents and "
+             "the child are counted that way, --keep-databases leaves compressed databases, and the lists hold compressed "
+             "k-mers: give them to classify-by-kmers --compress. A database given in place of reads must agree with the run",
+    )
+    parser.add_argument(
         "read_files", nargs=2,
         help="one comma-separated list of file paths for both libraries being compared. Files can "
              "be in fasta or fastq format, and uncompressed or gzipped. A single path ending in .tbkdb is a count "
@@ -137,14 +144,14 @@ def analyze_histogram(rows: Sequence[Tuple[int, int]], histogram_path: str = "")
     return min_coverage, max_coverage
 
 
-def count_library(paths: List[str], k: int, capacity: int, passes: int = 1) -> "kmers.KmerCounter":
+def count_library(paths: List[str], k: int, capacity: int, passes: int = 1, compress: bool = False) -> "kmers.KmerCounter":
     """Count the canonical k-mers of all files of one library (what `kmc -k<k> @files` does).
     The files are read side by side, one reader thread each (a gzip stream inflates on one core, but
     a library usually comes as many files); this thread feeds their batches to the GPU."""
     import queue
     import threading
 
-    counter = kmers.KmerCounter(k, capacity, passes=passes)
+    counter = kmers.KmerCounter(k, capacity, passes=passes, compress=compress)
     n_readers = max(1, min(len(paths), kmers.host_threads()))
     todo: "queue.Queue" = queue.Queue()
     for p in paths:
@@ -307,6 +314,10 @@ def main(argv=None):
             info = kmers.database_file_info(path)
             if info["k"] != k:
                 sys.exit("find-unique-kmers: {} holds {}-mers, but -k {} was given".format(path, info["k"], k))
+            if info["compressed"] != args.compress:
+                sys.exit("find-unique-kmers: {} holds {} k-mers, but this run {}".format(
+                    path, "homopolymer-compressed" if info["compressed"] else "plain (uncompressed)",
+                    "was not given --compress" if info["compressed"] else "was given --compress"))
     passes = args.passes
     if not passes:
         # both parents are counted in the same number of passes (their classes must match): the larger need decides
@@ -334,7 +345,7 @@ def main(argv=None):
                         raise IOError("no such file: {}".format(p))
                 # (in passes the table holds one class and is not bound by what two resident tables may take)
                 capacity = args.capacity or (estimate_capacity(paths) if passes == 1 else max(1 << 16, estimate_bases(paths)))
-                counter = count_library(paths, k, capacity, passes)
+                counter = count_library(paths, k, capacity, passes, args.compress)
                 if by_database:
                     # the database takes the counter's place: its table leaves the HBM before the other parent is counted
                     try:
@@ -374,7 +385,7 @@ def main(argv=None):
                     if not os.path.isfile(p):
                         raise IOError("no such file: {}".format(p))
                 capacity = args.capacity or (estimate_capacity(paths) if passes == 1 else max(1 << 16, estimate_bases(paths)))
-                counter = count_library(paths, k, capacity, passes)
+                counter = count_library(paths, k, capacity, passes, args.compress)
                 try:
                     child[0] = counter.database()
                 finally:

@@ -896,19 +896,24 @@ class KmerCounter:
     ``passes`` > 1 counts a library whose distinct k-mers outgrow one table: the k-mers fall into that many
     classes, the reads are kept on the device in packed form (0.5 bytes per base, at most ``store_limit`` bytes if
     given), and one class at a time goes through a table sized for a class (``tbk_counter_create_opts`` in
-    include/tbk.h).  Results are those of one pass; ``unique`` needs both counters made with the same ``passes``."""
+    include/tbk.h).  Results are those of one pass; ``unique`` needs both counters made with the same ``passes``.
 
-    def __init__(self, k: int, capacity: int, device: Optional[int] = None, passes: int = 1, store_limit: int = 0):
+    ``compress`` counts in homopolymer-compressed space: every batch goes through ``HomopolymerCompressor`` (case folded)
+    before its k-mers are cut, ``bases_added`` counts the bases that are left, and the database says so (``KmerDatabase.compressed``);
+    ``unique`` needs both counters to agree on it."""
+
+    def __init__(self, k: int, capacity: int, device: Optional[int] = None, passes: int = 1, store_limit: int = 0, compress: bool = False):
         self._h = C.c_void_p()
         self.k = k
         self.passes = passes
+        self.compress = bool(compress)
         self.device = default_device() if device is None else device
-        if passes == 1 and not store_limit:
+        if passes == 1 and not store_limit and not compress:
             check(lib.tbk_counter_create(k, capacity, self.device, C.byref(self._h)))
         else:
             opts = _lib.CounterOptions()
             lib.tbk_counter_options_init(C.byref(opts))
-            opts.passes, opts.store_limit_bytes = passes, store_limit
+            opts.passes, opts.store_limit_bytes, opts.compress = passes, store_limit, int(self.compress)
             check(lib.tbk_counter_create_opts(k, capacity, C.byref(opts), self.device, C.byref(self._h)))
 
     def add_reads(self, reads: Sequence[str]) -> None:
@@ -997,7 +1002,10 @@ def database_file_info(path: str) -> dict:
     hist = np.zeros(256, dtype=np.uint64)
     check(lib.tbk_kmerdb_file_info(os.fsencode(path), C.byref(k), C.byref(n), hist.ctypes.data_as(C.POINTER(C.c_uint64)),
                                    C.byref(reads), C.byref(bases)))
-    return {"k": k.value, "n": n.value, "histogram": hist, "reads_added": reads.value, "bases_added": bases.value}
+    flag = C.c_int()
+    check(lib.tbk_kmerdb_file_compressed(os.fsencode(path), C.byref(flag)))
+    return {"k": k.value, "n": n.value, "histogram": hist, "reads_added": reads.value, "bases_added": bases.value,
+            "compressed": bool(flag.value)}
 
 
 class KmerDatabase:
@@ -1011,6 +1019,9 @@ class KmerDatabase:
         k, n, device = C.c_int(), C.c_uint64(), C.c_int()
         check(lib.tbk_kmerdb_info(self._h, C.byref(k), C.byref(n), C.byref(device), None))
         self.k, self._n, self.device = k.value, n.value, device.value
+        flag = C.c_int()
+        check(lib.tbk_kmerdb_compressed(self._h, C.byref(flag)))
+        self.compressed = bool(flag.value)  # counted in homopolymer-compressed space: its file has another magic, and it mixes with no plain one
 
     @classmethod
     def load(cls, path: str, device: Optional[int] = None) -> "KmerDatabase":
@@ -1078,6 +1089,70 @@ class KmerDatabase:
         if self._h is not None and self._h.value:
             h, self._h = self._h, None
             lib.tbk_kmerdb_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HomopolymerCompressor:
+    """Every run of equal bases of a read written once, on the device (``tbk_hpc``, include/tbk.h): byte i of a read is kept
+    iff it is the read's first or differs from the byte before it - with ``fold_case`` compared as if letters were upper
+    case, but written as it came.  Runs end at read boundaries; empty reads stay; bytes outside ACGT are compared like any
+    others.  The counter compresses with ``fold_case`` on, the classifier with it off (lower case stays not-ACGT there).
+    The session owns its buffers; a result stays valid until the session's next call."""
+
+    def __init__(self, device: Optional[int] = None):
+        self._h = C.c_void_p()
+        self.device = default_device() if device is None else device
+        check(lib.tbk_hpc_create(self.device, C.byref(self._h)))
+        self._n_reads = 0
+
+    def _call(self, fn, n_reads, *args):
+        d_bases, d_offsets, total = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        check(fn(self._h, *args, C.byref(d_bases), C.byref(d_offsets), C.byref(total)))
+        self._n_reads = n_reads
+        return d_bases.value or 0, d_offsets.value or 0, total.value
+
+    def compress_host(self, bases: np.ndarray, offsets: np.ndarray, fold_case: bool = False) -> Tuple[int, int, int]:
+        """A host batch in, the result left on the device: (d_bases, d_offsets, total) for ``Classifier.submit_device``,
+        ``KmerCounter.add_device`` and the like."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.size - 1, 0)
+        return self._call(lib.tbk_hpc_compress, n, bases.ctypes.data, offsets.ctypes.data, n, int(bool(fold_case)))
+
+    def compress_batch(self, batch, fold_case: bool = False) -> Tuple[int, int, int]:
+        """``compress_host`` for a ``seq.Batch``, straight from its (pinned) buffers."""
+        bases_ptr, off_ptr = batch.pointers()
+        return self._call(lib.tbk_hpc_compress, batch.n_reads, C.c_void_p(bases_ptr), C.c_void_p(off_ptr), batch.n_reads, int(bool(fold_case)))
+
+    def compress_device(self, d_bases: int, d_offsets: int, n_reads: int, total_bases: int, fold_case: bool = False) -> Tuple[int, int, int]:
+        """The same for a batch already in HBM (``d_bases`` 16-byte aligned)."""
+        return self._call(lib.tbk_hpc_compress_device, n_reads, C.c_void_p(d_bases), C.c_void_p(d_offsets), n_reads, total_bases, int(bool(fold_case)))
+
+    def fetch(self, total: int) -> Tuple[np.ndarray, np.ndarray]:
+        """The last result as numpy arrays (``total``: what the compress call returned)."""
+        bases, offsets = np.zeros(total, dtype=np.uint8), np.zeros(self._n_reads + 1, dtype=np.uint64)
+        check(lib.tbk_hpc_fetch(self._h, bases.ctypes.data, total, offsets.ctypes.data))
+        return bases, offsets
+
+    def compress(self, bases: np.ndarray, offsets: np.ndarray, fold_case: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """(bases, offsets) of the compressed batch, as numpy."""
+        return self.fetch(self.compress_host(bases, offsets, fold_case)[2])
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            h, self._h = self._h, None
+            lib.tbk_hpc_destroy(h)
 
     def __enter__(self):
         return self

@@ -65,6 +65,7 @@ def parse_args(argv=None):
         if what is not None and not isfile(what):
             sys.exit("{}: {} does not exist or is not a file".format(PROG, what))
     args.databases = cbk._settle_databases(args, PROG) if is_db else None
+    cbk.refuse_compressed(args.databases, PROG)
     return args
 
 
