@@ -651,8 +651,14 @@ typedef struct tbk_counter_options {
                                  * host or device, is compressed before it is separated; in passes mode the kept reads are
                                  * the compressed ones.  reads_added counts the reads as given, bases_added the bases after
                                  * compression, the ones windows came from.  A caller with the older, shorter struct gets 0. */
+    int32_t keep_singletons;    /* != 0: the database this counter leaves (tbk_counter_export, and in passes mode every class's)
+                                 * is a FULL one: it keeps the k-mers seen once too, counters 1..255 (see tbk_kmerdb below).
+                                 * Histogram, tbk_counter_unique and tbk_counter_distinct answer as without it.  The field lies
+                                 * in what was the struct's tail padding (sizeof stays 24), so its size cannot tell an older
+                                 * caller from a newer one: tbk_counter_options_init writes 0 here, and a caller who fills the
+                                 * struct by hand has to zero it (the whole struct, padding included, before setting fields). */
 } tbk_counter_options;
-void tbk_counter_options_init(tbk_counter_options *o);  /* passes = 1, no limit, no compression */
+void tbk_counter_options_init(tbk_counter_options *o);  /* passes = 1, no limit, no compression, once-seen k-mers not kept */
 /* opts may be NULL (= tbk_counter_create). */
 int tbk_counter_create_opts(int k, uint64_t capacity_kmers, const tbk_counter_options *opts, int device, tbk_counter **out);
 /* No more batches: adding to a finished counter is TBK_ERR_INVALID.  With passes > 1 this counts the remaining
@@ -667,7 +673,8 @@ typedef struct tbk_counter_info {
     uint64_t store_bytes;       /* HBM held by the kept reads (0 once finished, and with passes = 1) */
     uint64_t store_used_bytes;  /* of which filled: 8 bytes per 16 bases of the separated stream, each batch rounded up */
     uint64_t peak_table_bytes;  /* the largest table held at any time (while it is rebuilt, the old one is held too) */
-    uint64_t database_bytes;    /* 9 bytes per k-mer seen at least twice, over the classes distilled so far */
+    uint64_t database_bytes;    /* 9 bytes per kept k-mer, over the classes distilled so far: the k-mers seen at least twice,
+                                 * or with keep_singletons every distinct k-mer */
     uint64_t distinct;          /* distinct k-mers met: the classes distilled so far plus the class in the table;
                                  * never finishes the counter (tbk_counter_distinct does) */
 } tbk_counter_info;
@@ -707,8 +714,13 @@ int tbk_counter_unique(tbk_counter *a, tbk_counter *b, uint32_t min_count, uint3
  * ascending - n one-byte counters in 2..255, the whole 256-row histogram of the counter it came from (row 1 the
  * k-mers seen once, row 0 all distinct k-mers, as tbk_counter_histogram defines them) and the reads and bases
  * that were counted.  9 bytes of HBM per k-mer; twice that while tbk_counter_export orders one.  It outlives
- * its counter.  Uniting two databases is not offered: a k-mer seen once in each half is in neither, so a union
- * would not equal one count of both halves. */
+ * its counter.
+ * A database has a FLOOR, the lowest counter it holds.  2 is the form above.  1 is a FULL database, what a counter with
+ * keep_singletons leaves: the k-mers seen once are entries too, counters lie in 1..255, and n == hist[0] ==
+ * sum(hist[1..255]).  Two databases of floor 2 cannot be united - a k-mer seen once in each half is in neither, so a
+ * union would not equal one count of both halves - but two full ones can, exactly (tbk_kmerdb_union), and
+ * tbk_kmerdb_solid takes a full database back to floor 2.  The query session takes either form; the subtractions and
+ * list builders below take floor 2 only. */
 typedef struct tbk_kmerdb tbk_kmerdb;
 /* Finishes the counter (no more batches: tbk_counter_add_batch is TBK_ERR_INVALID afterwards; a counter in passes
  * counts its remaining classes first) and makes its database.  A one-pass counter's table is only read:
@@ -737,6 +749,29 @@ int tbk_kmerdb_file_info(const char *path, int *k, uint64_t *n, uint64_t hist[25
  * (the host-side checks of tbk_kmerdb_file_info; needs no device). */
 int tbk_kmerdb_compressed(const tbk_kmerdb *db, int *flag);
 int tbk_kmerdb_file_compressed(const char *path, int *flag);
+/* A full database's file has a magic of its own, "TBKKMFB1" (plain) or "TBKKMFH1" (compressed), and otherwise the identical
+ * 2096 + 9n layout; a build that does not know full databases refuses it at the magic.  Its header must state rows 1..255
+ * summing to n and row 0 == n; on the device no counter may be below 1 and the tally of rows 1..255 must equal the header's.
+ * tbk_kmerdb_save writes the magic that matches floor and space. */
+int tbk_kmerdb_floor(const tbk_kmerdb *db, int *floor);      /* 2, or 1: the database holds the k-mers seen once */
+int tbk_kmerdb_file_floor(const char *path, int *floor);     /* host-side checks only, needs no device */
+/* The database of both read sets: what one counter with keep_singletons, fed the reads of `a` and then those of `b`, would
+ * export, byte for byte - the ascending union of the keys, min(255, ca + cb) for a key both hold (added in 32 bits) and the
+ * own counter otherwise, reads and bases summed, the histogram tallied from the merged counters on the device (rows 1..255;
+ * row 0 = n).  Exact because min(255, min(255, x) + min(255, y)) == min(255, x + y).  Both must be full, of one k, one device
+ * and one space: anything else is TBK_ERR_INVALID with the reason in tbk_last_error() - for a floor-2 argument, that it was
+ * kept without the once-seen k-mers and cannot be united exactly.  Either may be empty.  Nothing is sorted or concatenated:
+ * both inputs ascend, so every entry's place is its index plus its lower bound in the other database less the shared keys
+ * before it.  Launches: flag the entries of A that B holds (a bit per entry, a count per tile of 1024), scan the counts,
+ * scatter A, scatter B (B's copy of a shared key writes nothing), tally.  The output is allocated at its exact size once the
+ * number of shared keys is known; beside it the call takes n_a/8 + n_a/64 bytes and 2 KiB, freed before it returns.
+ * TBK_ERR_NOMEM leaves both inputs as they were and the device usable; *out is NULL after every error. */
+int tbk_kmerdb_union(const tbk_kmerdb *a, const tbk_kmerdb *b, tbk_kmerdb **out);
+/* From a full database the floor-2 database of the same reads: the entries with a counter of 2 or more, in place order (flag,
+ * scan, scatter of keys and counters); histogram, reads and bases carried over - row 1 stays the number of once-seen k-mers,
+ * row 0 all distinct ones.  Saved, it is byte for byte the file the same counter without keep_singletons would have left.  A
+ * floor-2 argument is TBK_ERR_INVALID.  n/8 + n/64 bytes beside the output; *out is NULL after every error. */
+int tbk_kmerdb_solid(const tbk_kmerdb *db, tbk_kmerdb **out);
 /* bytes: HBM the database holds (9n).  Any out pointer may be NULL. */
 int tbk_kmerdb_info(const tbk_kmerdb *db, int *k, uint64_t *n, int *device, uint64_t *bytes);
 int tbk_kmerdb_stats(const tbk_kmerdb *db, uint64_t *reads_added, uint64_t *bases_added);
@@ -748,7 +783,8 @@ int tbk_kmerdb_read(const tbk_kmerdb *db, uint64_t first, uint64_t count, uint64
  * min(255, max_count)] and that `b` does not hold, one per line in lexicographic order - the same file.  An
  * empty range or an empty `a` gives an empty file and TBK_OK; a different k or device is TBK_ERR_INVALID, and so
  * is a compressed database against a plain one - here and in the three calls below, the child's database included -
- * with the reason in tbk_last_error(). */
+ * with the reason in tbk_last_error().  So is a full database in any position of these four calls: membership in `b` is
+ * tested by key alone, and a full `b` would subtract the k-mers it saw once; the message names tbk_kmerdb_solid. */
 int tbk_kmerdb_unique(const tbk_kmerdb *a, const tbk_kmerdb *b, uint32_t min_count, uint32_t max_count, const char *out_path,
                       uint64_t *n_written);
 /* The same selection as a k-mer list in HBM on the databases' device, without the text: for every consumer
@@ -845,7 +881,9 @@ int tbk_hit_tracker_marks(tbk_hit_tracker *t, const uint8_t *bases, const uint64
  * is CLEAN when its k bases are all ACGT, either case: case is folded as the counter folds it (the database was
  * counted that way, so a database queried with its own reads finds them).  A clean window's k-mer is the counter's
  * canonical one - the lexicographic minimum of the window and its reverse complement - and its counter c is the
- * database's, 2..255, or 0 when the database does not hold it (a k-mer the reads hold once is in no database).
+ * database's, 2..255, or 0 when the database does not hold it (a k-mer the reads hold once is in no floor-2 database;
+ * a full database holds it, and c is then 1..255: wherever "max(2, min_count)" stands below, a full database has
+ * max(1, min_count), so min_count = 1 counts presence).
  * The session borrows the database (it must outlive the session) and owns, on the database's device:
  *   - a DIRECTORY over the top P bits of the 2k-bit rank: 2^P + 1 32-bit offsets, dir[p] = the first entry whose
  *     rank has prefix >= p, built once at creation by one bisection per prefix.  P = floor(log2 n) - 1, so that a

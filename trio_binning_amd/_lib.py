@@ -176,7 +176,8 @@ _sig("tbk_counter_destroy", None, _vp)
 
 class CounterOptions(C.Structure):
     """tbk_counter_options (include/tbk.h)."""
-    _fields_ = [("size", C.c_uint32), ("passes", C.c_int32), ("store_limit_bytes", C.c_uint64), ("compress", C.c_int32)]
+    _fields_ = [("size", C.c_uint32), ("passes", C.c_int32), ("store_limit_bytes", C.c_uint64), ("compress", C.c_int32),
+                ("keep_singletons", C.c_int32)]  # (in what was the tail padding: sizeof stays 24)
 
 
 class CounterInfo(C.Structure):
@@ -231,6 +232,12 @@ if HAS_HIT_TRACKER:
     _sig("tbk_hit_tracker_destroy", None, _vp)
     _sig("tbk_hit_tracker_runs", C.c_int, _vp, _vp, _vp, _u64, C.c_int, C.POINTER(_vp), _u64p, _vp)
     _sig("tbk_hit_tracker_marks", C.c_int, _vp, _vp, _vp, _u64, C.c_int, _vp)
+HAS_KMERDB_FULL = hasattr(lib, "tbk_kmerdb_union")  # (variant builds of tools/build_variant.sh may predate full databases)
+if HAS_KMERDB_FULL:
+    _sig("tbk_kmerdb_floor", C.c_int, _vp, C.POINTER(C.c_int))
+    _sig("tbk_kmerdb_file_floor", C.c_int, C.c_char_p, C.POINTER(C.c_int))
+    _sig("tbk_kmerdb_union", C.c_int, _vp, _vp, C.POINTER(_vp))
+    _sig("tbk_kmerdb_solid", C.c_int, _vp, C.POINTER(_vp))
 HAS_DB_QUERY = hasattr(lib, "tbk_kmerdb_query_create")  # (variant builds of tools/build_variant.sh may predate the database query)
 if HAS_DB_QUERY:
     _sig("tbk_kmerdb_query_create", C.c_int, _vp, C.c_int, C.POINTER(_vp))

@@ -11,8 +11,10 @@ Floats have a fixed format: ``qv`` four decimals (``inf`` when every clean windo
 window), ``completeness`` six decimals (``nan`` when nothing is solid), ``error_rate`` six significant digits as
 ``d.ddddde-xx`` (``nan`` without a clean window).
 
-Deviation from Merqury: a database holds only k-mers the reads hold at least twice (kmc's -ci2), so a k-mer the reads hold
-once counts as absent here and as found there.  The QV is therefore a lower bound of Merqury's at the same k.
+Merqury counts presence: a k-mer the reads hold once is found.  A database kept with find-unique-kmers --keep-singletons (a
+full one) holds those k-mers, and ``--min-count 1`` then is Merqury's definition.  A database kept without the flag holds only
+k-mers the reads hold at least twice (kmc's -ci2): there a k-mer seen once counts as absent, --min-count starts at 2 and the
+QV is a lower bound of Merqury's at the same k.
 """
 # Run as ``python -m trio_binning_amd.assembly_qv``.  The lookup is on the device (kmers.DatabaseQuery: a directory over the
 # database's ranks, one wave per 2048 window starts); the QV arithmetic, the absent stretches and the tables run on the host.
@@ -45,7 +47,8 @@ def _parser() -> argparse.ArgumentParser:
     parser.add_argument("assembly", help="contigs (or reads) to score, in fasta/q format. Can be gzipped.")
     parser.add_argument("database", help="the count database of the reads (*.tbkdb, kept by find-unique-kmers --keep-databases)")
     parser.add_argument("--min-count", type=int, default=2, metavar="N",
-                        help="the counter a k-mer needs to count as found, and as solid for completeness (2..255; default 2)")
+                        help="the counter a k-mer needs to count as found, and as solid for completeness (2..255; default 2). "
+                             "1 - presence, Merqury's definition - needs a full database, kept with find-unique-kmers --keep-singletons")
     parser.add_argument("--max-count", type=int, default=255, metavar="N", help="completeness only: the largest counter of a solid k-mer (2..255; default 255)")
     parser.add_argument("--spectrum", default=None, metavar="PATH",
                         help="write the copy spectrum: one line 'counter copies kmers' per non-empty cell, copies 0..4 and >4 "
@@ -61,8 +64,9 @@ def parse_args(argv=None):
     that header (``kmers.database_file_info``).  No device is touched."""
     parser = _parser()
     args = parser.parse_args(argv)
+    presence = args.min_count == 1  # k-mers seen once count as found: only a full database holds them (checked below, by its header)
     for name in ("min_count", "max_count"):
-        if not 2 <= getattr(args, name) <= 255:
+        if not 2 <= getattr(args, name) <= 255 and not (name == "min_count" and presence):
             parser.error("--{} {}: need 2 <= N <= 255".format(name.replace("_", "-"), getattr(args, name)))
     if args.min_count > args.max_count:
         parser.error("--min-count {} is larger than --max-count {}".format(args.min_count, args.max_count))
@@ -79,6 +83,9 @@ def parse_args(argv=None):
     if args.info["compressed"]:
         sys.exit("{}: {} holds homopolymer-compressed k-mers (find-unique-kmers --compress): a QV is not defined in compressed "
                  "space. Give a plain database.".format(PROG, args.database))
+    if presence and args.info["floor"] != 1:
+        parser.error("--min-count 1: need 2 <= N <= 255 with this database, which was kept without the k-mers seen once; keep it "
+                     "with find-unique-kmers --keep-databases --keep-singletons to count presence")
     return args
 
 

@@ -53,11 +53,11 @@ class DatabasePair:
         try:
             for hap in "AB":
                 print(f"Loading the k-mer database of haplotype {hap} from {self.paths[hap]}...", file=sys.stderr)
-                dbs[hap] = kmers.KmerDatabase.load(self.paths[hap])
+                dbs[hap] = kmers.load_solid_database(self.paths[hap])  # (a full file: its solid form)
             third = {}
             if self.child_path is not None:
                 print(f"Loading the k-mer database of the child from {self.child_path}...", file=sys.stderr)
-                dbs["child"] = kmers.KmerDatabase.load(self.child_path)
+                dbs["child"] = kmers.load_solid_database(self.child_path)
                 third = {"child": dbs["child"], "child_min": self.child_min, "child_max": 255}
             for hap, other in ("AB", "BA"):
                 lo, hi = self.ranges[hap]

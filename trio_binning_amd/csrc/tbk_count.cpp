@@ -44,7 +44,8 @@ extern "C" hipError_t tbk_launch_sort_u64(const uint64_t *, uint64_t *, uint64_t
 extern "C" hipError_t tbk_launch_retain(const uint8_t *, uint64_t, uint64_t *, uint64_t, hipStream_t);
 extern "C" hipError_t tbk_launch_count_class(const uint64_t *, uint64_t, uint64_t, uint64_t, int, uint64_t *, uint32_t, TbkMz, int *, unsigned long long *,
                                              uint32_t, uint32_t, hipStream_t);
-extern "C" hipError_t tbk_launch_count_distil(uint64_t *, uint32_t, TbkMz, uint64_t *, uint8_t *, uint64_t, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_count_distil(uint64_t *, uint32_t, TbkMz, uint32_t, uint64_t *, uint8_t *, uint64_t, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_db_solid_keys(const uint64_t *, const uint8_t *, uint64_t, uint64_t *, uint64_t, unsigned long long *, hipStream_t);
 extern "C" hipError_t tbk_launch_db_unique(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, int, uint32_t, uint32_t, uint64_t *,
                                            uint64_t, unsigned long long *, hipStream_t);
 
@@ -106,6 +107,8 @@ struct tbk_counter {
     uint64_t distinct_done = 0;                 // distinct k-mers of the classes distilled so far
     bool compress = false;                      // tbk_counter_options.compress: the k-mers are those of the homopolymer-compressed reads
     tbk_hpc *hpc = nullptr;                     // its session: every batch goes through it (freed with the store when a counter in passes finishes)
+    bool keep_singletons = false;               // tbk_counter_options.keep_singletons: the database (and every class's) holds the k-mers seen once too
+    uint32_t floor() const { return keep_singletons ? 1u : 2u; }  // the lowest counter a database of this counter holds
 };
 
 static int counter_device(const tbk_counter *c) {
@@ -173,6 +176,7 @@ extern "C" int tbk_counter_create_opts(int k, uint64_t capacity_kmers, const tbk
     c->device = device; c->k = k;
     c->passes = o.passes; c->store_limit = o.store_limit_bytes;
     c->compress = o.compress != 0;
+    c->keep_singletons = o.keep_singletons != 0;
     if (c->compress) {
         const int made = tbk_hpc_create(device, &c->hpc);
         if (made) { delete c; return made; }
@@ -326,7 +330,7 @@ static int distil_class(tbk_counter *c) {
     unsigned long long h[256];
     CHIP(hipMemcpy(h, c->d_hist, sizeof h, hipMemcpyDeviceToHost));
     uint64_t keep = 0;
-    for (int i = 2; i < 256; i++) keep += h[i] - c->hist[i];
+    for (int i = (int)c->floor(); i < 256; i++) keep += h[i] - c->hist[i];
     c->distinct_done += h[0] - c->hist[0];
     for (int i = 0; i < 256; i++) c->hist[i] = h[i];
     tbk_counter::ClassDb d;
@@ -338,10 +342,10 @@ static int distil_class(tbk_counter *c) {
     }
     unsigned long long got = 0;
     CHIP(hipMemset(c->d_used, 0, sizeof got));  // [0] doubles as the append cursor: the class's slot count has been read
-    CHIP(tbk_launch_count_distil(c->d_lines, c->n_buckets, c->mz, db.d_keys, db.d_counts, keep, c->d_used, nullptr));
+    CHIP(tbk_launch_count_distil(c->d_lines, c->n_buckets, c->mz, c->floor(), db.d_keys, db.d_counts, keep, c->d_used, nullptr));
     CHIP(hipMemcpy(&got, c->d_used, sizeof got, hipMemcpyDeviceToHost));
     CHIP(hipMemset(c->d_used, 0, sizeof got));
-    if (got != keep) return cfail(TBK_ERR_HIP, "distilling a class: %llu k-mers seen twice in the histogram, %llu in the table", (unsigned long long)keep, got);
+    if (got != keep) return cfail(TBK_ERR_HIP, "distilling a class: %llu k-mers to keep by the histogram, %llu in the table", (unsigned long long)keep, got);
     db.n = keep;
     c->database_bytes += keep * 9;
     c->used = 0;
@@ -622,18 +626,33 @@ extern "C" int tbk_counter_unique(tbk_counter *a, tbk_counter *b, uint32_t min_c
                                         d_out, cap, d_n, nullptr);
         if (e == hipSuccess && by_class) {
             // class by class: B's keys of the class sorted (keys alone), A's looked up among them
-            uint64_t most = 0, *d_bs = nullptr;
+            // (a B that keeps its once-seen k-mers holds them in its classes: they are left out first - B "holds" what it saw twice)
+            uint64_t most = 0, *d_bs = nullptr, *d_b2 = nullptr;
+            unsigned long long *d_nb = nullptr;
             for (const tbk_counter::ClassDb &d : b->db) most = std::max(most, d.n);
             if (most) e = hipMalloc((void **)&d_bs, most * sizeof(uint64_t));
+            if (e == hipSuccess && most && b->keep_singletons) e = hipMalloc((void **)&d_b2, most * sizeof(uint64_t));
+            if (e == hipSuccess && most && b->keep_singletons) e = hipMalloc((void **)&d_nb, sizeof(unsigned long long));
             for (size_t p = 0; e == hipSuccess && p < a->db.size(); p++) {
                 const tbk_counter::ClassDb &da = a->db[p], &db = b->db[p];
                 if (!da.n) continue;
-                if (db.n) e = tbk_launch_sort_u64(db.d_keys, d_bs, db.n, 2 * a->k, nullptr);
+                const uint64_t *b_keys = db.d_keys;
+                uint64_t b_n = db.n;
+                if (db.n && b->keep_singletons) {
+                    unsigned long long solid = 0;
+                    e = hipMemset(d_nb, 0, sizeof solid);
+                    if (e == hipSuccess) e = tbk_launch_db_solid_keys(db.d_keys, db.d_counts, db.n, d_b2, db.n, d_nb, nullptr);
+                    if (e == hipSuccess) e = hipMemcpy(&solid, d_nb, sizeof solid, hipMemcpyDeviceToHost);
+                    b_keys = d_b2;
+                    b_n = std::min<uint64_t>(solid, db.n);
+                }
+                if (e == hipSuccess && b_n) e = tbk_launch_sort_u64(b_keys, d_bs, b_n, 2 * a->k, nullptr);
                 if (e == hipSuccess)
-                    e = tbk_launch_db_unique(da.d_keys, da.d_counts, da.n, d_bs, db.n, a->k, min_count, max_count, d_out, cap, d_n, nullptr);
+                    e = tbk_launch_db_unique(da.d_keys, da.d_counts, da.n, d_bs, b_n, a->k, min_count, max_count, d_out, cap, d_n, nullptr);
             }
             if (e == hipSuccess) e = hipDeviceSynchronize();
-            if (d_bs) (void)hipFree(d_bs);
+            for (void *q : {(void *)d_bs, (void *)d_b2, (void *)d_nb})
+                if (q) (void)hipFree(q);
         }
         if (e == hipSuccess) e = hipMemcpy(&got, d_n, sizeof got, hipMemcpyDeviceToHost);
         n = std::min<uint64_t>(got, cap);
@@ -659,9 +678,9 @@ extern "C" int tbk_counter_unique(tbk_counter *a, tbk_counter *b, uint32_t min_c
 // and comes back, and is subtracted from another at cut-offs the caller names.  Keys are lexicographic ranks in
 // ascending order, so subtraction is a bisection and a dump needs no conversion.
 // =====================================================================================================================
-extern "C" hipError_t tbk_launch_count_export(uint64_t *, uint32_t, TbkMz, int, uint64_t *, uint8_t *, uint64_t, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_count_export(uint64_t *, uint32_t, TbkMz, int, uint32_t, uint64_t *, uint8_t *, uint64_t, unsigned long long *, hipStream_t);
 extern "C" hipError_t tbk_launch_db_rank(const uint64_t *, const uint8_t *, uint64_t, int, uint64_t *, uint8_t *, hipStream_t);
-extern "C" hipError_t tbk_launch_kmerdb_check(const uint64_t *, const uint8_t *, uint64_t, int, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_kmerdb_check(const uint64_t *, const uint8_t *, uint64_t, int, uint32_t, unsigned long long *, hipStream_t);
 extern "C" hipError_t tbk_launch_kmerdb_unique(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, uint32_t, uint32_t, uint64_t *,
                                                uint64_t, unsigned long long *, hipStream_t);
 extern "C" hipError_t tbk_launch_sort_u64_u8(const uint64_t *, uint64_t *, const uint8_t *, uint8_t *, uint64_t, int, hipStream_t);
@@ -670,11 +689,19 @@ struct tbk_kmerdb {
     int device = 0, k = 0;
     uint64_t n = 0;
     uint64_t *d_keys = nullptr;   // n ranks, strictly ascending
-    uint8_t *d_counts = nullptr;  // their counters, 2..255
+    uint8_t *d_counts = nullptr;  // their counters, floor..255
     uint64_t hist[256] = {0};     // the counter's whole histogram (tbk_counter_histogram)
     uint64_t reads_added = 0, bases_added = 0;
     bool compressed = false;      // counted in homopolymer-compressed space: another magic in the file, no mixing with plain ones
+    uint32_t floor = 2;           // the lowest counter held: 2, or 1 for a FULL database (the k-mers seen once are entries too: n == hist[0])
 };
+
+// The subtractions test membership in `b` by key alone and the list builders select from counter 2 up: a full database
+// among their arguments would silently count its once-seen k-mers as held.
+static int kmerdb_not_full(const tbk_kmerdb *db, const char *which, const char *who) {
+    if (db->floor >= 2) return TBK_OK;
+    return cfail(TBK_ERR_INVALID, "%s: %s database is a full one (it holds the k-mers seen once): make its solid form with tbk_kmerdb_solid first", who, which);
+}
 
 // two databases in different spaces share no k-mer worth comparing
 static int kmerdb_same_space(const tbk_kmerdb *a, const tbk_kmerdb *b, const char *what_b) {
@@ -713,9 +740,10 @@ extern "C" int tbk_counter_export(tbk_counter *c, tbk_kmerdb **out) {
     rc = tbk_counter_histogram(c, hist);
     if (rc) return rc;
     uint64_t n = 0;
-    for (int i = 2; i < 256; i++) n += hist[i];
+    for (int i = (int)c->floor(); i < 256; i++) n += hist[i];
     tbk_kmerdb *db = new tbk_kmerdb();
     db->device = c->device; db->k = c->k; db->n = n;
+    db->floor = c->floor();
     db->reads_added = c->reads_added; db->bases_added = c->bases_added;
     db->compressed = c->compress;
     memcpy(db->hist, hist, sizeof hist);
@@ -731,7 +759,7 @@ extern "C" int tbk_counter_export(tbk_counter *c, tbk_kmerdb **out) {
         if (e == hipSuccess && c->passes == 1) {
             e = hipMalloc((void **)&d_n, sizeof got);  // (a cursor of its own: the counter's d_used stays as it is)
             if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof got);
-            if (e == hipSuccess) e = tbk_launch_count_export(c->d_lines, c->n_buckets, c->mz, c->k, d_rk, d_rc, n, d_n, nullptr);
+            if (e == hipSuccess) e = tbk_launch_count_export(c->d_lines, c->n_buckets, c->mz, c->k, c->floor(), d_rk, d_rc, n, d_n, nullptr);
             if (e == hipSuccess) e = hipMemcpy(&got, d_n, sizeof got, hipMemcpyDeviceToHost);
         } else if (e == hipSuccess) {
             for (const tbk_counter::ClassDb &d : c->db) {
@@ -749,7 +777,7 @@ extern "C" int tbk_counter_export(tbk_counter *c, tbk_kmerdb **out) {
             tbk_kmerdb_destroy(db);
             (void)hipGetLastError();
             if (e != hipSuccess) return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "tbk_counter_export (%llu k-mers): %s", (unsigned long long)n, hipGetErrorString(e));
-            return cfail(TBK_ERR_HIP, "tbk_counter_export: %llu k-mers seen twice in the histogram, %llu in the counter", (unsigned long long)n, got);
+            return cfail(TBK_ERR_HIP, "tbk_counter_export: %llu k-mers to keep by the histogram, %llu in the counter", (unsigned long long)n, got);
         }
     }
     c->finished = true;  // (a counter in passes is already)
@@ -760,12 +788,16 @@ extern "C" int tbk_counter_export(tbk_counter *c, tbk_kmerdb **out) {
 // ---- the file (*.tbkdb; INTEGRATION.md has the table) ---------------------------------------------------------------------
 static const char TBK_KMERDB_MAGIC[8] = {'T', 'B', 'K', 'K', 'M', 'D', 'B', '1'};
 static const char TBK_KMERDB_MAGIC_HPC[8] = {'T', 'B', 'K', 'K', 'M', 'D', 'H', '1'};  // a compressed database: the same layout under another name
+// full databases (the k-mers seen once are entries): two more names for the same layout, which an older build refuses at the magic
+static const char TBK_KMERDB_MAGIC_FULL[8] = {'T', 'B', 'K', 'K', 'M', 'F', 'B', '1'};
+static const char TBK_KMERDB_MAGIC_FULL_HPC[8] = {'T', 'B', 'K', 'K', 'M', 'F', 'H', '1'};
 constexpr size_t TBK_KMERDB_HEADER = 2096;
 
 struct KmerdbHeader {
     int k = 0;
     uint64_t n = 0, reads = 0, bases = 0, hist[256] = {0};
     bool compressed = false;
+    uint32_t floor = 2;
 };
 
 // little-endian hosts only (as the rest of the library: x86-64 beside the MI355X)
@@ -802,8 +834,9 @@ static int kmerdb_read_header(int fd, const char *path, KmerdbHeader *h) {
     if (size < TBK_KMERDB_HEADER) return cfail(TBK_ERR_FORMAT, "%s: %llu bytes are less than the header of a k-mer database (%zu)", path, (unsigned long long)size, TBK_KMERDB_HEADER);
     uint8_t b[TBK_KMERDB_HEADER];
     if (!read_all(fd, b, sizeof b)) return cfail(TBK_ERR_IO, "%s: cannot read the header: %s", path, strerror(errno));
-    h->compressed = memcmp(b, TBK_KMERDB_MAGIC_HPC, 8) == 0;
-    if (!h->compressed && memcmp(b, TBK_KMERDB_MAGIC, 8) != 0) return cfail(TBK_ERR_FORMAT, "%s: not a k-mer database (magic)", path);
+    h->floor = (memcmp(b, TBK_KMERDB_MAGIC_FULL, 8) == 0 || memcmp(b, TBK_KMERDB_MAGIC_FULL_HPC, 8) == 0) ? 1 : 2;
+    h->compressed = memcmp(b, h->floor == 1 ? TBK_KMERDB_MAGIC_FULL_HPC : TBK_KMERDB_MAGIC_HPC, 8) == 0;
+    if (h->floor == 2 && !h->compressed && memcmp(b, TBK_KMERDB_MAGIC, 8) != 0) return cfail(TBK_ERR_FORMAT, "%s: not a k-mer database (magic)", path);
     if (get_le<uint32_t>(b + 8) != TBK_KMERDB_HEADER) return cfail(TBK_ERR_FORMAT, "%s: header size %u, expected %zu", path, get_le<uint32_t>(b + 8), TBK_KMERDB_HEADER);
     const uint32_t k = get_le<uint32_t>(b + 12);
     if (k < 1 || k > 32) return cfail(TBK_ERR_FORMAT, "%s: k = %u out of range (1..32)", path, k);
@@ -819,9 +852,16 @@ static int kmerdb_read_header(int fd, const char *path, KmerdbHeader *h) {
     if (body % 9 != 0 || body / 9 != h->n)  // (compared by division: 9 * n is never formed from an unchecked n)
         return cfail(TBK_ERR_FORMAT, "%s: %llu bytes after the header do not hold the %llu k-mers it states (9 bytes each)", path, (unsigned long long)body, (unsigned long long)h->n);
     uint64_t kept = 0;
-    for (int i = 2; i < 256; i++) {
+    for (int i = (int)h->floor; i < 256; i++) {
         if (h->hist[i] > h->n) return cfail(TBK_ERR_FORMAT, "%s: histogram row %d exceeds the number of k-mers", path, i);
         kept += h->hist[i];  // (256 terms of at most n < 2^61: no overflow)
+    }
+    if (h->floor == 1) {  // a full database: every distinct k-mer is an entry
+        if (kept != h->n)
+            return cfail(TBK_ERR_FORMAT, "%s: histogram rows 1..255 sum to %llu, the full database states %llu k-mers", path, (unsigned long long)kept, (unsigned long long)h->n);
+        if (h->hist[0] != h->n)
+            return cfail(TBK_ERR_FORMAT, "%s: histogram row 0 (all distinct k-mers) is %llu, the full database states %llu k-mers", path, (unsigned long long)h->hist[0], (unsigned long long)h->n);
+        return TBK_OK;
     }
     if (kept != h->n) return cfail(TBK_ERR_FORMAT, "%s: histogram rows 2..255 sum to %llu, the file states %llu k-mers", path, (unsigned long long)kept, (unsigned long long)h->n);
     if (h->hist[0] < h->n || h->hist[0] - h->n < h->hist[1])
@@ -857,6 +897,24 @@ extern "C" int tbk_kmerdb_file_compressed(const char *path, int *flag) {
     return TBK_OK;
 }
 
+extern "C" int tbk_kmerdb_file_floor(const char *path, int *floor) {
+    if (!path || !floor) return cfail(TBK_ERR_INVALID, "NULL argument");
+    const int fd = ::open(path, O_RDONLY);
+    if (fd < 0) return cfail(TBK_ERR_IO, "cannot open %s: %s", path, strerror(errno));
+    KmerdbHeader h;
+    const int rc = kmerdb_read_header(fd, path, &h);
+    ::close(fd);
+    if (rc) return rc;
+    *floor = (int)h.floor;
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_floor(const tbk_kmerdb *db, int *floor) {
+    if (!db || !floor) return cfail(TBK_ERR_INVALID, "NULL argument");
+    *floor = (int)db->floor;
+    return TBK_OK;
+}
+
 extern "C" int tbk_kmerdb_compressed(const tbk_kmerdb *db, int *flag) {
     if (!db || !flag) return cfail(TBK_ERR_INVALID, "NULL argument");
     *flag = db->compressed ? 1 : 0;
@@ -873,7 +931,7 @@ extern "C" int tbk_kmerdb_save(const tbk_kmerdb *db, const char *path) {
     }
     uint8_t b[TBK_KMERDB_HEADER];
     memset(b, 0, sizeof b);
-    memcpy(b, db->compressed ? TBK_KMERDB_MAGIC_HPC : TBK_KMERDB_MAGIC, 8);
+    memcpy(b, db->floor == 1 ? (db->compressed ? TBK_KMERDB_MAGIC_FULL_HPC : TBK_KMERDB_MAGIC_FULL) : (db->compressed ? TBK_KMERDB_MAGIC_HPC : TBK_KMERDB_MAGIC), 8);
     put_le<uint32_t>(b + 8, (uint32_t)TBK_KMERDB_HEADER);
     put_le<uint32_t>(b + 12, (uint32_t)db->k);
     put_le<uint64_t>(b + 16, db->n);
@@ -921,6 +979,7 @@ extern "C" int tbk_kmerdb_load(const char *path, int device, tbk_kmerdb **out) {
     db->device = device; db->k = h.k; db->n = h.n;
     db->reads_added = h.reads; db->bases_added = h.bases;
     db->compressed = h.compressed;
+    db->floor = h.floor;
     memcpy(db->hist, h.hist, sizeof h.hist);
     if (h.n) {
         unsigned long long *d_tally = nullptr, tally[3 + 256];
@@ -941,7 +1000,7 @@ extern "C" int tbk_kmerdb_load(const char *path, int device, tbk_kmerdb **out) {
             if (ok) e = hipMemcpy(db->d_counts + at, buf.data(), m, hipMemcpyHostToDevice);
         }
         // the content is only data so far: one pass tells whether it may be searched and tallied by
-        if (ok && e == hipSuccess) e = tbk_launch_kmerdb_check(db->d_keys, db->d_counts, h.n, h.k, d_tally, nullptr);
+        if (ok && e == hipSuccess) e = tbk_launch_kmerdb_check(db->d_keys, db->d_counts, h.n, h.k, h.floor, d_tally, nullptr);
         if (ok && e == hipSuccess) e = hipMemcpy(tally, d_tally, sizeof tally, hipMemcpyDeviceToHost);
         if (d_tally) (void)hipFree(d_tally);
         ::close(fd);
@@ -952,13 +1011,13 @@ extern "C" int tbk_kmerdb_load(const char *path, int device, tbk_kmerdb **out) {
             return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "tbk_kmerdb_load (%llu k-mers): %s", (unsigned long long)h.n, hipGetErrorString(e));
         }
         int row = 0;
-        for (int i = 2; i < 256 && !row; i++)
+        for (int i = (int)h.floor; i < 256 && !row; i++)
             if (tally[3 + i] != h.hist[i]) row = i;
         if (tally[0] || tally[1] || tally[2] || row) {
             tbk_kmerdb_destroy(db);
             if (tally[0]) return cfail(TBK_ERR_FORMAT, "%s: the k-mers are not in strictly ascending order (%llu places)", path, tally[0]);
             if (tally[1]) return cfail(TBK_ERR_FORMAT, "%s: %llu k-mers have bits above 2k = %d", path, tally[1], 2 * h.k);
-            if (tally[2]) return cfail(TBK_ERR_FORMAT, "%s: %llu counters are below 2", path, tally[2]);
+            if (tally[2]) return cfail(TBK_ERR_FORMAT, "%s: %llu counters are below %u", path, tally[2], h.floor);
             return cfail(TBK_ERR_FORMAT, "%s: %llu counters are %d, the header's histogram states %llu", path, tally[3 + row], row, (unsigned long long)h.hist[row]);
         }
     } else {
@@ -1008,6 +1067,7 @@ extern "C" int tbk_kmerdb_unique(const tbk_kmerdb *a, const tbk_kmerdb *b, uint3
     if (a->k != b->k) return cfail(TBK_ERR_INVALID, "the databases have different k (%d and %d)", a->k, b->k);
     if (a->device != b->device) return cfail(TBK_ERR_INVALID, "the databases live on different devices");
     if (kmerdb_same_space(a, b, "the second")) return TBK_ERR_INVALID;
+    if (kmerdb_not_full(a, "the first", "tbk_kmerdb_unique") || kmerdb_not_full(b, "the second", "tbk_kmerdb_unique")) return TBK_ERR_INVALID;
     *n_written = 0;
     // upper bound of what can come out: k-mers of A with a counter in range
     uint64_t cap = 0;
@@ -1067,6 +1127,7 @@ extern "C" int tbk_kmerdb_unique_table(const tbk_kmerdb *a, const tbk_kmerdb *b,
     if (a->k != b->k) return cfail(TBK_ERR_INVALID, "the databases have different k (%d and %d)", a->k, b->k);
     if (a->device != b->device) return cfail(TBK_ERR_INVALID, "the databases live on different devices");
     if (kmerdb_same_space(a, b, "the second")) return TBK_ERR_INVALID;
+    if (kmerdb_not_full(a, "the first", "tbk_kmerdb_unique_table") || kmerdb_not_full(b, "the second", "tbk_kmerdb_unique_table")) return TBK_ERR_INVALID;
     // upper bound of what can come out, as in tbk_kmerdb_unique: none in range means nothing to launch
     uint64_t cap = 0;
     for (uint32_t cnt = std::max<uint32_t>(2, min_count); cnt <= std::min<uint32_t>(255, max_count); cnt++) cap += a->hist[cnt];
@@ -1116,6 +1177,9 @@ static int inherited_check(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_k
         return cfail(TBK_ERR_INVALID, "the databases have different k (%d, %d and the child's %d)", a->k, b->k, child->k);
     if (a->device != b->device || a->device != child->device) return cfail(TBK_ERR_INVALID, "the databases live on different devices");
     if (kmerdb_same_space(a, b, "the second") || kmerdb_same_space(a, child, "the child's")) return TBK_ERR_INVALID;
+    if (kmerdb_not_full(a, "the first", "tbk_kmerdb_inherited") || kmerdb_not_full(b, "the second", "tbk_kmerdb_inherited") ||
+        kmerdb_not_full(child, "the child's", "tbk_kmerdb_inherited"))
+        return TBK_ERR_INVALID;
     return TBK_OK;
 }
 
@@ -1209,6 +1273,158 @@ extern "C" int tbk_kmerdb_inherited_table(const tbk_kmerdb *a, const tbk_kmerdb 
         *out = nullptr;
     }
     return made;
+}
+
+// ---- full databases: the union of two, and the way back to the solid form -------------------------------------------------
+extern "C" hipError_t tbk_launch_kmerdb_union_flag(const uint64_t *, uint64_t, const uint64_t *, uint64_t, uint64_t *, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_kmerdb_union_scatter(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, const uint8_t *, uint64_t,
+                                                      const uint64_t *, const unsigned long long *, uint64_t *, uint8_t *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_kmerdb_tally(const uint8_t *, uint64_t, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_kmerdb_scatter_pairs(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, const unsigned long long *, uint64_t *,
+                                                      uint8_t *, uint64_t, hipStream_t);
+
+// db(X) united with db(Y) is db(X ++ Y) when both are full: min(255, min(255, x) + min(255, y)) == min(255, x + y).  A's
+// entries are flagged where B holds the same key (one bit per entry of A, one count per tile of A), the tile counts are
+// scanned, the output is allocated at n_a + n_b - duplicates and both inputs are scattered to their places (the kernels'
+// comment has the rule); the histogram is tallied from the merged counters.  Beside the output: n_a / 8 + n_a / 64 bytes and
+// 2 KiB, freed before the call returns.
+extern "C" int tbk_kmerdb_union(const tbk_kmerdb *a, const tbk_kmerdb *b, tbk_kmerdb **out) {
+    if (out) *out = nullptr;
+    if (!a || !b || !out) return cfail(TBK_ERR_INVALID, "NULL argument");
+    for (const tbk_kmerdb *d : {a, b})
+        if (d->floor != 1)
+            return cfail(TBK_ERR_INVALID, "tbk_kmerdb_union: the %s database was kept without the once-seen k-mers and cannot be united exactly "
+                                          "(a k-mer seen once in each half is in neither); count with keep_singletons", d == a ? "first" : "second");
+    if (a->k != b->k) return cfail(TBK_ERR_INVALID, "the databases have different k (%d and %d)", a->k, b->k);
+    if (a->device != b->device) return cfail(TBK_ERR_INVALID, "the databases live on different devices");
+    if (kmerdb_same_space(a, b, "the second")) return TBK_ERR_INVALID;
+    if (a->n > (UINT64_MAX >> 4) || b->n > (UINT64_MAX >> 4)) return cfail(TBK_ERR_INVALID, "tbk_kmerdb_union: too many k-mers");
+    const int rc = kmerdb_device(a->device);
+    if (rc) return rc;
+    tbk_kmerdb *db = new tbk_kmerdb();
+    db->device = a->device; db->k = a->k; db->floor = 1; db->compressed = a->compressed;
+    db->reads_added = a->reads_added + b->reads_added;
+    db->bases_added = a->bases_added + b->bases_added;
+    const uint64_t tiles = tbk_kmerdb_table_tiles(a->n), words = tbk_kmerdb_table_flag_words(a->n);
+    uint64_t *d_flags = nullptr;
+    unsigned long long *d_tiles = nullptr, *d_hist = nullptr, dups = 0, hist[256];  // d_tiles: tiles + 1 counts (the last one 0), then their tiles + 1 offsets (the last one the total)
+    memset(hist, 0, sizeof hist);
+    hipError_t e = hipMalloc((void **)&d_flags, (words ? words : 1) * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_tiles, 2 * (tiles + 1) * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_hist, sizeof hist);
+    if (e == hipSuccess) e = hipMemset(d_tiles + tiles, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(d_hist, 0, sizeof hist);
+    if (e == hipSuccess) e = tbk_launch_kmerdb_union_flag(a->d_keys, a->n, b->d_keys, b->n, d_flags, d_tiles, nullptr);
+    if (e == hipSuccess) e = tbk_launch_kmerdb_scan(d_tiles, d_tiles + tiles + 1, tiles + 1, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(&dups, d_tiles + 2 * tiles + 1, sizeof dups, hipMemcpyDeviceToHost);
+    const bool sane = dups <= a->n && dups <= b->n;  // (nothing is allocated or written by a count that cannot be)
+    const uint64_t n = sane ? a->n + b->n - dups : 0;
+    if (e == hipSuccess && sane && n) e = hipMalloc((void **)&db->d_keys, n * sizeof(uint64_t));
+    if (e == hipSuccess && sane && n) e = hipMalloc((void **)&db->d_counts, n);
+    if (e == hipSuccess && sane && n)
+        e = tbk_launch_kmerdb_union_scatter(a->d_keys, a->d_counts, a->n, b->d_keys, b->d_counts, b->n, d_flags, d_tiles + tiles + 1, db->d_keys,
+                                            db->d_counts, n, nullptr);
+    if (e == hipSuccess && sane && n) e = tbk_launch_kmerdb_tally(db->d_counts, n, d_hist, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(hist, d_hist, sizeof hist, hipMemcpyDeviceToHost);
+    for (void *p : {(void *)d_flags, (void *)d_tiles, (void *)d_hist})
+        if (p) (void)hipFree(p);
+    if (e != hipSuccess || !sane) {
+        tbk_kmerdb_destroy(db);
+        (void)hipGetLastError();
+        if (e != hipSuccess)
+            return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "tbk_kmerdb_union (%llu and %llu k-mers): %s", (unsigned long long)a->n, (unsigned long long)b->n, hipGetErrorString(e));
+        return cfail(TBK_ERR_HIP, "tbk_kmerdb_union: %llu k-mers in both of %llu and %llu", dups, (unsigned long long)a->n, (unsigned long long)b->n);
+    }
+    db->n = n;
+    uint64_t tallied = 0;
+    for (int i = 1; i < 256; i++) { db->hist[i] = hist[i]; tallied += hist[i]; }
+    db->hist[0] = n;
+    if (hist[0] || tallied != n) {
+        tbk_kmerdb_destroy(db);
+        return cfail(TBK_ERR_HIP, "tbk_kmerdb_union: %llu of %llu merged counters tallied, %llu of them 0", (unsigned long long)tallied, (unsigned long long)n, hist[0]);
+    }
+    *out = db;
+    return TBK_OK;
+}
+
+// (measurement hook, not in tbk.h: tools/measure_union.py makes databases of 1e8 entries where they lie.  Takes over d_keys and
+// d_counts - device memory of hipMalloc, freed with the database - once the pass that checks a loaded file has found them in
+// order, within 2k bits and at or above the floor; the histogram is that pass's tally, row 0 = n.)
+extern "C" int tbk_kmerdb_adopt_device_(uint64_t *d_keys, uint8_t *d_counts, uint64_t n, int k, int device, int floor, tbk_kmerdb **out) {
+    if (out) *out = nullptr;
+    if (!out || (n && (!d_keys || !d_counts))) return cfail(TBK_ERR_INVALID, "NULL argument");
+    if (k < 1 || k > 32 || floor < 1 || floor > 2) return cfail(TBK_ERR_INVALID, "k = %d, floor = %d", k, floor);
+    const int rc = kmerdb_device(device);
+    if (rc) return rc;
+    unsigned long long *d_tally = nullptr, tally[3 + 256];
+    memset(tally, 0, sizeof tally);
+    hipError_t e = hipMalloc((void **)&d_tally, sizeof tally);
+    if (e == hipSuccess) e = hipMemset(d_tally, 0, sizeof tally);
+    if (e == hipSuccess) e = tbk_launch_kmerdb_check(d_keys, d_counts, n, k, (uint32_t)floor, d_tally, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(tally, d_tally, sizeof tally, hipMemcpyDeviceToHost);
+    if (d_tally) (void)hipFree(d_tally);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return cfail(TBK_ERR_HIP, "tbk_kmerdb_adopt_device_: %s", hipGetErrorString(e));
+    }
+    if (tally[0] || tally[1] || tally[2])
+        return cfail(TBK_ERR_FORMAT, "tbk_kmerdb_adopt_device_: %llu places out of order, %llu keys above 2k bits, %llu counters below %d", tally[0], tally[1], tally[2], floor);
+    tbk_kmerdb *db = new tbk_kmerdb();
+    db->device = device; db->k = k; db->n = n; db->floor = (uint32_t)floor;
+    db->d_keys = d_keys; db->d_counts = d_counts;
+    for (int i = 1; i < 256; i++) db->hist[i] = tally[3 + i];
+    db->hist[0] = n;
+    *out = db;
+    return TBK_OK;
+}
+
+// The database the same counter would have left without keep_singletons: the entries with a counter of 2 or more, in their
+// places; the header's numbers as they are.  Flag (tbk_kmerdb_flag_kernel with no B and the range 2..255), scan, scatter
+// of keys and counters; n / 8 + n / 64 bytes beside the output.
+extern "C" int tbk_kmerdb_solid(const tbk_kmerdb *src, tbk_kmerdb **out) {
+    if (out) *out = nullptr;
+    if (!src || !out) return cfail(TBK_ERR_INVALID, "NULL argument");
+    if (src->floor != 1) return cfail(TBK_ERR_INVALID, "tbk_kmerdb_solid: the database is not a full one: it is solid already");
+    const int rc = kmerdb_device(src->device);
+    if (rc) return rc;
+    uint64_t want = 0;
+    for (int i = 2; i < 256; i++) want += src->hist[i];
+    tbk_kmerdb *db = new tbk_kmerdb();
+    db->device = src->device; db->k = src->k; db->floor = 2; db->compressed = src->compressed;
+    db->reads_added = src->reads_added; db->bases_added = src->bases_added;
+    memcpy(db->hist, src->hist, sizeof src->hist);
+    unsigned long long total = 0;
+    if (src->n) {
+        const uint64_t tiles = tbk_kmerdb_table_tiles(src->n), words = tbk_kmerdb_table_flag_words(src->n);
+        uint64_t *d_flags = nullptr;
+        unsigned long long *d_tiles = nullptr;
+        hipError_t e = hipMalloc((void **)&d_flags, words * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&d_tiles, 2 * (tiles + 1) * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMemset(d_tiles + tiles, 0, sizeof(unsigned long long));
+        if (e == hipSuccess) e = tbk_launch_kmerdb_flag(src->d_keys, src->d_counts, src->n, nullptr, 0, 2, 255, d_flags, d_tiles, nullptr);
+        if (e == hipSuccess) e = tbk_launch_kmerdb_scan(d_tiles, d_tiles + tiles + 1, tiles + 1, nullptr);
+        if (e == hipSuccess) e = hipMemcpy(&total, d_tiles + 2 * tiles + 1, sizeof total, hipMemcpyDeviceToHost);
+        const bool agree = total == want;
+        if (e == hipSuccess && agree && want) e = hipMalloc((void **)&db->d_keys, want * sizeof(uint64_t));
+        if (e == hipSuccess && agree && want) e = hipMalloc((void **)&db->d_counts, want);
+        if (e == hipSuccess && agree && want)
+            e = tbk_launch_kmerdb_scatter_pairs(src->d_keys, src->d_counts, src->n, d_flags, d_tiles + tiles + 1, db->d_keys, db->d_counts, want, nullptr);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (d_flags) (void)hipFree(d_flags);
+        if (d_tiles) (void)hipFree(d_tiles);
+        if (e != hipSuccess) {
+            tbk_kmerdb_destroy(db);
+            (void)hipGetLastError();
+            return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "tbk_kmerdb_solid (%llu k-mers): %s", (unsigned long long)src->n, hipGetErrorString(e));
+        }
+    }
+    if (total != want) {
+        tbk_kmerdb_destroy(db);
+        return cfail(TBK_ERR_HIP, "tbk_kmerdb_solid: %llu counters of 2 or more, the histogram states %llu", total, (unsigned long long)want);
+    }
+    db->n = want;
+    *out = db;
+    return TBK_OK;
 }
 
 // =====================================================================================================================
@@ -1367,7 +1583,7 @@ extern "C" int tbk_kmerdb_query_add(tbk_kmerdb_query *q, const uint8_t *bases, c
     CHIP(tbk_launch_separate(q->bases.as<uint8_t>(), q->offsets.as<uint64_t>(), n_reads, q->sep.as<uint8_t>(), nullptr));
     const tbk_kmerdb *db = q->db;
     CHIP(tbk_launch_query_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, db->n ? db->d_keys : (const uint64_t *)q->d_pad,
-                                 db->n ? db->d_counts : (const uint8_t *)q->d_pad, q->d_dir, db->n, q->prefix_bits, std::max<uint32_t>(2, min_count),
+                                 db->n ? db->d_counts : (const uint8_t *)q->d_pad, q->d_dir, db->n, q->prefix_bits, std::max<uint32_t>(db->floor, min_count),
                                  q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(), counts ? q->bytes.as<uint8_t>() : nullptr, q->d_sums, q->d_seen,
                                  q->with_copies ? q->d_copies : nullptr, q->wave_slots, nullptr));
     q->windows += windows;  // (the launch is in the stream: what follows can only fail to bring the answers home)
@@ -1392,7 +1608,7 @@ extern "C" int tbk_kmerdb_query_histogram(tbk_kmerdb_query *q, uint64_t hist[256
 extern "C" int tbk_kmerdb_query_completeness(tbk_kmerdb_query *q, uint32_t min_count, uint32_t max_count, uint64_t *seen, uint64_t *solid) {
     if (!q || !seen || !solid) return cfail(TBK_ERR_INVALID, "NULL argument");
     *seen = *solid = 0;
-    const uint32_t ci = std::max<uint32_t>(2, min_count), cx = std::min<uint32_t>(255, max_count);
+    const uint32_t ci = std::max<uint32_t>(q->db->floor, min_count), cx = std::min<uint32_t>(255, max_count);
     if (!q->db->n || ci > cx) return TBK_OK;
     const int rc = kmerdb_device(q->device);
     if (rc) return rc;

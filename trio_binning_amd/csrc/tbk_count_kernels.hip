@@ -355,9 +355,10 @@ tbk_count_unique_kernel(TbkCountView a, TbkCountView b, int k, uint32_t ci, uint
 // After a class has been counted, its table is distilled: every k-mer seen at least twice (kmc's -ci2) is
 // appended to the class's database as (key, counter capped at 255) - 9 bytes - and every slot goes back to
 // free, ready for the next class.  The k-mers seen once are dropped here; the histogram (taken just before,
-// tbk_count_histogram_kernel) has counted them.  Appends are per wave, as in tbk_count_unique_kernel.
+// tbk_count_histogram_kernel) has counted them.  floor = 1 (tbk_counter_options.keep_singletons) keeps them too.
+// Appends are per wave, as in tbk_count_unique_kernel.
 __global__ void __launch_bounds__(256)
-tbk_count_distil_kernel(TbkCountView t, uint64_t *__restrict__ db_keys, uint8_t *__restrict__ db_counts, uint64_t capacity,
+tbk_count_distil_kernel(TbkCountView t, uint32_t floor, uint64_t *__restrict__ db_keys, uint8_t *__restrict__ db_counts, uint64_t capacity,
                         unsigned long long *__restrict__ n_out) {
     const uint64_t n_slots = (uint64_t)t.n_buckets * TBK_SLOTS_PER_BUCKET;
     const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
@@ -373,7 +374,7 @@ tbk_count_distil_kernel(TbkCountView t, uint64_t *__restrict__ db_keys, uint8_t 
             if (key != TBK_EMPTY) {
                 uint32_t *cp = &t.counts((uint32_t)(i >> 3))[i & 7];
                 raw = *cp;
-                emit = raw >= 2u;
+                emit = raw >= floor;
                 *kp = TBK_EMPTY;
                 *cp = 0;
             }
@@ -447,7 +448,7 @@ tbk_db_unique_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restr
 // A live one-pass table to (rank, capped counter) pairs: tbk_count_distil_kernel without its stores to the
 // table, which is only read.  Appends are per wave; the order is the sort's business.
 __global__ void __launch_bounds__(256)
-tbk_count_export_kernel(TbkCountView t, int k, uint64_t *__restrict__ out_keys, uint8_t *__restrict__ out_counts, uint64_t capacity,
+tbk_count_export_kernel(TbkCountView t, int k, uint32_t floor, uint64_t *__restrict__ out_keys, uint8_t *__restrict__ out_counts, uint64_t capacity,
                         unsigned long long *__restrict__ n_out) {
     const uint64_t n_slots = (uint64_t)t.n_buckets * TBK_SLOTS_PER_BUCKET;
     const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
@@ -461,7 +462,7 @@ tbk_count_export_kernel(TbkCountView t, int k, uint64_t *__restrict__ out_keys, 
             key = t.keys((uint32_t)(i >> 3))[i & 7];
             if (key != TBK_EMPTY) {
                 raw = t.counts((uint32_t)(i >> 3))[i & 7];
-                emit = raw >= 2u;
+                emit = raw >= floor;  // (2, or 1: a full database keeps the k-mers seen once)
             }
         }
         const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
@@ -494,9 +495,9 @@ tbk_db_rank_kernel(const uint64_t *__restrict__ keys, const uint8_t *__restrict_
 // One pass over a database that came from a file, before anything indexes by its content.  tally[0]: places where
 // key[i] >= key[i + 1] (every element reads its right neighbour from memory, so the pairs that straddle a wave, a
 // block or a grid stride are compared like any other); tally[1]: keys with a bit of high_mask (the bits above
-// 2k; 0 for k = 32); tally[2]: counters below 2; tally[3 + c]: counters equal to c.
+// 2k; 0 for k = 32); tally[2]: counters below the database's floor (2, or 1 for a full one); tally[3 + c]: counters equal to c.
 __global__ void __launch_bounds__(256)
-tbk_kmerdb_check_kernel(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ counts, uint64_t n, uint64_t high_mask,
+tbk_kmerdb_check_kernel(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ counts, uint64_t n, uint64_t high_mask, uint32_t floor,
                         unsigned long long *__restrict__ tally) {
     __shared__ unsigned int h[256];
     __shared__ unsigned int bad[3];
@@ -509,7 +510,7 @@ tbk_kmerdb_check_kernel(const uint64_t *__restrict__ keys, const uint8_t *__rest
         const uint32_t c = counts[i];
         if (i + 1 < n && key >= keys[i + 1]) disorder++;
         if (key & high_mask) high++;
-        if (c < 2u) low++;
+        if (c < floor) low++;
         atomicAdd(&h[c], 1u);
     }
     if (disorder) atomicAdd(&bad[0], disorder);
@@ -735,6 +736,212 @@ tbk_kmerdb_scatter_ranks_kernel(const uint64_t *__restrict__ a_keys, uint64_t n_
     }
 }
 
+// ---- a class database without its once-seen k-mers: B's side of tbk_counter_unique for a counter that keeps them --------
+// tbk_db_unique_kernel tests membership in B by key alone; a class database made with floor 1 also holds the k-mers
+// seen once, which B "does not hold" in kmc's sense.  Their keys are left out here, before the sort.
+__global__ void __launch_bounds__(256)
+tbk_db_solid_keys_kernel(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ counts, uint64_t n, uint64_t *__restrict__ out,
+                         uint64_t capacity, unsigned long long *__restrict__ n_out) {
+    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; i0 < n; i0 += step) {
+        const uint64_t i = i0 + lane;
+        const bool emit = i < n && counts[i] >= 2u;
+        const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
+        if (mask) {
+            unsigned long long base = 0;
+            const int leader = __builtin_ctzll(mask);
+            if ((int)lane == leader) base = atomicAdd(n_out, (unsigned long long)__popcll(mask));
+            base = __shfl(base, leader);
+            if (emit) {
+                const uint64_t at = base + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+                if (at < capacity) out[at] = keys[i];
+            }
+        }
+    }
+}
+
+// ---- tbk_kmerdb_solid: a full database without its once-seen k-mers ------------------------------------------------------
+// The flags are tbk_kmerdb_flag_kernel's with an empty B and the range 2..255; this is tbk_kmerdb_scatter_ranks_kernel
+// taking the counter along.
+__global__ void __launch_bounds__(256)
+tbk_kmerdb_scatter_pairs_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restrict__ a_counts, uint64_t n_a,
+                                const uint64_t *__restrict__ flags, const unsigned long long *__restrict__ tile_offsets,
+                                uint64_t *__restrict__ out_keys, uint8_t *__restrict__ out_counts, uint64_t n_out) {
+    __shared__ uint64_t word_mask[TBK_DBT_WORDS];
+    __shared__ uint32_t word_before[TBK_DBT_WORDS];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t tile = blockIdx.x;
+    if (threadIdx.x < TBK_DBT_WORDS) word_mask[threadIdx.x] = flags[tile * TBK_DBT_WORDS + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (uint32_t w = 0; w < TBK_DBT_WORDS; w++) {
+            word_before[w] = sum;
+            sum += (uint32_t)__popcll(word_mask[w]);
+        }
+    }
+    __syncthreads();
+    const uint64_t base = tile_offsets[tile];
+    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
+        const uint32_t word = r * 4 + wave;
+        const uint64_t mask = word_mask[word];
+        const uint64_t i = tile * TBK_DBT_TILE + (uint64_t)word * 64 + lane;
+        if (((mask >> lane) & 1ull) && i < n_a) {
+            const uint64_t at = base + word_before[word] + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+            if (at < n_out) {
+                out_keys[at] = a_keys[i];
+                out_counts[at] = a_counts[i];
+            }
+        }
+    }
+}
+
+// ---- tbk_kmerdb_union: two full databases to the database of both read sets -----------------------------------------------
+// The RANK-BASED shape.  Both inputs ascend and hold no key twice, so the place of an entry in the union is its own
+// index plus its lower bound in the other database, less the keys both hold (the duplicates) that stand before it; no
+// sort, no concatenation.  Three steps, separate launches, no block waiting for another:
+//   1. flag: one block per tile of TBK_DBT_TILE entries of A.  Every entry finds its lower bound in B, between the
+//      bounds of its tile's first and last entry as in tbk_kmerdb_inherited_flag_kernel; a duplicate is an entry whose
+//      key B holds at that place - B's key is read from memory wherever it lies, whatever tile of B that is.  One bit
+//      per entry of A and a count per tile of A;
+//   2. the exclusive scan of the tile counts (tbk_launch_kmerdb_scan);
+//   3. scatter, one launch per input.  A's entry i goes to i + lower bound in B - duplicates of A before i, and a
+//      duplicate carries min(255, ca + cb), added in 32 bits.  B's entry j asks A in the same way: held by A (again
+//      read from A's memory at its lower bound there), it writes nothing - A's copy has written both; otherwise it
+//      goes to j + lower bound in A - duplicates of A before that lower bound, which the flag words and tile offsets
+//      of A give (the 16 flag words of a tile are one 128-byte line).
+// Keys are compared as unsigned 64-bit numbers: at k = 32 a rank uses the top bit.  The bisection is repeated in step
+// 3 and not kept: 8 bytes per entry would be more than the bit per entry the call may hold beside its output.
+// 256 threads and no LDS to speak of (two bounds, a word table): occupancy is bounded by registers alone; a tile of
+// 1024 keeps the per-tile state at 16 bytes per 9 KiB of input and the tile's span in B small enough that the
+// bisection's lines are shared by the block.
+__global__ void __launch_bounds__(256)
+tbk_kmerdb_union_flag_kernel(const uint64_t *__restrict__ a_keys, uint64_t n_a, const uint64_t *__restrict__ b_keys, uint64_t n_b,
+                             uint64_t *__restrict__ flags, unsigned long long *__restrict__ tile_counts) {
+    __shared__ uint64_t bound[2];
+    __shared__ uint32_t tile_sum;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t tile = blockIdx.x;
+    const uint64_t first = tile * TBK_DBT_TILE;  // (< n_a: one block per tile of A)
+    if (threadIdx.x < 2) {
+        const uint64_t last = (n_a - first < TBK_DBT_TILE ? n_a : first + TBK_DBT_TILE) - 1;
+        bound[threadIdx.x] = db_lower_bound(b_keys, 0, n_b, a_keys[threadIdx.x ? last : first]);
+    }
+    if (threadIdx.x == 0) tile_sum = 0;
+    __syncthreads();
+    const uint64_t b_lo = bound[0], b_hi = bound[1];
+    uint32_t mine = 0;  // (the same in every lane of a wave)
+    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
+        const uint32_t word = r * 4 + wave;
+        const uint64_t i = first + (uint64_t)word * 64 + lane;
+        bool dup = false;
+        if (i < n_a) {
+            const uint64_t key = a_keys[i];
+            const uint64_t at = db_lower_bound(b_keys, b_lo, b_hi, key);  // (at <= b_hi <= n_b)
+            dup = at < n_b && b_keys[at] == key;
+        }
+        const uint64_t mask = __builtin_amdgcn_ballot_w64(dup);
+        if (lane == 0) flags[tile * TBK_DBT_WORDS + word] = mask;
+        mine += (uint32_t)__popcll(mask);
+    }
+    if (lane == 0 && mine) atomicAdd(&tile_sum, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) tile_counts[tile] = tile_sum;
+}
+
+__global__ void __launch_bounds__(256)
+tbk_kmerdb_union_scatter_a_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restrict__ a_counts, uint64_t n_a,
+                                  const uint64_t *__restrict__ b_keys, const uint8_t *__restrict__ b_counts, uint64_t n_b,
+                                  const uint64_t *__restrict__ flags, const unsigned long long *__restrict__ tile_offsets,
+                                  uint64_t *__restrict__ out_keys, uint8_t *__restrict__ out_counts, uint64_t n_out) {
+    __shared__ uint64_t bound[2];
+    __shared__ uint64_t word_mask[TBK_DBT_WORDS];
+    __shared__ uint32_t word_before[TBK_DBT_WORDS];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t tile = blockIdx.x;
+    const uint64_t first = tile * TBK_DBT_TILE;
+    if (threadIdx.x < 2) {
+        const uint64_t last = (n_a - first < TBK_DBT_TILE ? n_a : first + TBK_DBT_TILE) - 1;
+        bound[threadIdx.x] = db_lower_bound(b_keys, 0, n_b, a_keys[threadIdx.x ? last : first]);
+    }
+    if (threadIdx.x >= 64 && threadIdx.x < 64 + TBK_DBT_WORDS) word_mask[threadIdx.x - 64] = flags[tile * TBK_DBT_WORDS + threadIdx.x - 64];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (uint32_t w = 0; w < TBK_DBT_WORDS; w++) {
+            word_before[w] = sum;
+            sum += (uint32_t)__popcll(word_mask[w]);
+        }
+    }
+    __syncthreads();
+    const uint64_t b_lo = bound[0], b_hi = bound[1];
+    const uint64_t dups_before_tile = tile_offsets[tile];
+    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
+        const uint32_t word = r * 4 + wave;
+        const uint64_t mask = word_mask[word];
+        const uint64_t i = first + (uint64_t)word * 64 + lane;
+        if (i < n_a) {
+            const uint64_t key = a_keys[i];
+            const uint64_t rank = db_lower_bound(b_keys, b_lo, b_hi, key);
+            const uint64_t dups = dups_before_tile + word_before[word] + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+            uint32_t c = a_counts[i];
+            if (((mask >> lane) & 1ull) && rank < n_b) c += b_counts[rank];  // (32-bit sum of two bytes)
+            const uint64_t at = i + rank - dups;
+            if (at < n_out) {
+                out_keys[at] = key;
+                out_counts[at] = (uint8_t)(c < 255u ? c : 255u);
+            }
+        }
+    }
+}
+
+// One block per tile of B; flags and tile_offsets are A's.
+__global__ void __launch_bounds__(256)
+tbk_kmerdb_union_scatter_b_kernel(const uint64_t *__restrict__ b_keys, const uint8_t *__restrict__ b_counts, uint64_t n_b,
+                                  const uint64_t *__restrict__ a_keys, uint64_t n_a, const uint64_t *__restrict__ flags,
+                                  const unsigned long long *__restrict__ tile_offsets, uint64_t *__restrict__ out_keys,
+                                  uint8_t *__restrict__ out_counts, uint64_t n_out) {
+    __shared__ uint64_t bound[2];
+    const uint64_t first = (uint64_t)blockIdx.x * TBK_DBT_TILE;  // (< n_b)
+    if (threadIdx.x < 2) {
+        const uint64_t last = (n_b - first < TBK_DBT_TILE ? n_b : first + TBK_DBT_TILE) - 1;
+        bound[threadIdx.x] = db_lower_bound(a_keys, 0, n_a, b_keys[threadIdx.x ? last : first]);
+    }
+    __syncthreads();
+    const uint64_t a_lo = bound[0], a_hi = bound[1];
+    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
+        const uint64_t j = first + (uint64_t)r * 256 + threadIdx.x;
+        if (j >= n_b) continue;
+        const uint64_t key = b_keys[j];
+        const uint64_t rank = db_lower_bound(a_keys, a_lo, a_hi, key);  // (<= a_hi <= n_a)
+        if (rank < n_a && a_keys[rank] == key) continue;  // A's copy carries both counters
+        // duplicates of A before entry `rank` of A: its tile's offset and the flag bits of the tile below it.  rank == n_a
+        // on a tile edge reads offset [tiles] (the total) and no flag word.
+        const uint64_t a_tile = rank / TBK_DBT_TILE;
+        const uint32_t in_tile = (uint32_t)(rank % TBK_DBT_TILE), whole = in_tile >> 6, bits = in_tile & 63u;
+        uint64_t dups = tile_offsets[a_tile];
+        for (uint32_t w = 0; w < whole; w++) dups += (uint64_t)__popcll(flags[a_tile * TBK_DBT_WORDS + w]);
+        if (bits) dups += (uint64_t)__popcll(flags[a_tile * TBK_DBT_WORDS + whole] & ((1ull << bits) - 1ull));
+        const uint64_t at = j + rank - dups;
+        if (at < n_out) {
+            out_keys[at] = key;
+            out_counts[at] = b_counts[j];
+        }
+    }
+}
+
+// hist[c] += counters equal to c (hist: 256 words, zeroed by the caller): the histogram of a database made on the device
+__global__ void __launch_bounds__(256)
+tbk_kmerdb_tally_kernel(const uint8_t *__restrict__ counts, uint64_t n, unsigned long long *__restrict__ hist) {
+    __shared__ unsigned int h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) atomicAdd(&h[counts[i]], 1u);
+    __syncthreads();
+    if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], (unsigned long long)h[threadIdx.x]);
+}
+
 // =======================================================================================
 // launchers (called from tbk_count.cpp)
 // =======================================================================================
@@ -822,9 +1029,10 @@ extern "C" hipError_t tbk_launch_count_class(const uint64_t *d_store, uint64_t n
     return hipGetLastError();
 }
 
-extern "C" hipError_t tbk_launch_count_distil(uint64_t *d_lines, uint32_t n_buckets, TbkMz mz, uint64_t *d_keys, uint8_t *d_counts,
+extern "C" hipError_t tbk_launch_count_distil(uint64_t *d_lines, uint32_t n_buckets, TbkMz mz, uint32_t floor, uint64_t *d_keys, uint8_t *d_counts,
                                               uint64_t capacity, unsigned long long *d_n, hipStream_t stream) {
-    hipLaunchKernelGGL(tbk_count_distil_kernel, dim3(4096), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz}, d_keys, d_counts, capacity, d_n);
+    if (floor < 1 || floor > 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tbk_count_distil_kernel, dim3(4096), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz}, floor, d_keys, d_counts, capacity, d_n);
     return hipGetLastError();
 }
 
@@ -839,9 +1047,10 @@ extern "C" hipError_t tbk_launch_db_unique(const uint64_t *a_keys, const uint8_t
 }
 
 // ---- count databases ------------------------------------------------------------------------------------
-extern "C" hipError_t tbk_launch_count_export(uint64_t *d_lines, uint32_t n_buckets, TbkMz mz, int k, uint64_t *d_keys, uint8_t *d_counts,
+extern "C" hipError_t tbk_launch_count_export(uint64_t *d_lines, uint32_t n_buckets, TbkMz mz, int k, uint32_t floor, uint64_t *d_keys, uint8_t *d_counts,
                                               uint64_t capacity, unsigned long long *d_n, hipStream_t stream) {
-    hipLaunchKernelGGL(tbk_count_export_kernel, dim3(4096), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz}, k, d_keys, d_counts, capacity, d_n);
+    if (floor < 1 || floor > 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tbk_count_export_kernel, dim3(4096), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz}, k, floor, d_keys, d_counts, capacity, d_n);
     return hipGetLastError();
 }
 
@@ -854,12 +1063,13 @@ extern "C" hipError_t tbk_launch_db_rank(const uint64_t *d_keys, const uint8_t *
 }
 
 // d_tally: 3 + 256 words, zeroed by the caller
-extern "C" hipError_t tbk_launch_kmerdb_check(const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, int k, unsigned long long *d_tally,
-                                              hipStream_t stream) {
+extern "C" hipError_t tbk_launch_kmerdb_check(const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, int k, uint32_t floor,
+                                              unsigned long long *d_tally, hipStream_t stream) {
     if (!n) return hipSuccess;
+    if (floor < 1 || floor > 2) return hipErrorInvalidValue;
     const uint64_t high_mask = k >= 32 ? 0ull : ~0ull << (2 * k);
     const uint64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(tbk_kmerdb_check_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, d_keys, d_counts, n, high_mask, d_tally);
+    hipLaunchKernelGGL(tbk_kmerdb_check_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, d_keys, d_counts, n, high_mask, floor, d_tally);
     return hipGetLastError();
 }
 
@@ -932,5 +1142,64 @@ extern "C" hipError_t tbk_launch_kmerdb_scatter_ranks(const uint64_t *a_keys, ui
     if (!tiles || !n_out) return hipSuccess;
     if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(tbk_kmerdb_scatter_ranks_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, n_a, d_flags, d_tile_offsets, d_out, n_out);
+    return hipGetLastError();
+}
+
+// ---- keep_singletons: B's class keys without the once-seen ones ------------------------------------------------------
+extern "C" hipError_t tbk_launch_db_solid_keys(const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, uint64_t *d_out, uint64_t capacity,
+                                               unsigned long long *d_n, hipStream_t stream) {
+    if (!n) return hipSuccess;
+    const uint64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(tbk_db_solid_keys_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, d_keys, d_counts, n, d_out, capacity, d_n);
+    return hipGetLastError();
+}
+
+// ---- tbk_kmerdb_solid: tbk_launch_kmerdb_flag (no B, 2..255), the scan, then this ------------------------------------------
+extern "C" hipError_t tbk_launch_kmerdb_scatter_pairs(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *d_flags,
+                                                      const unsigned long long *d_tile_offsets, uint64_t *d_out_keys, uint8_t *d_out_counts,
+                                                      uint64_t n_out, hipStream_t stream) {
+    const uint64_t tiles = tbk_kmerdb_table_tiles(n_a);
+    if (!tiles || !n_out) return hipSuccess;
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tbk_kmerdb_scatter_pairs_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, a_counts, n_a, d_flags, d_tile_offsets,
+                       d_out_keys, d_out_counts, n_out);
+    return hipGetLastError();
+}
+
+// ---- tbk_kmerdb_union: flag A against B, the scan above, scatter A, scatter B, tally --------------------------------------
+// d_flags: tbk_kmerdb_table_flag_words(n_a) words; d_tile_counts: one per tile of A
+extern "C" hipError_t tbk_launch_kmerdb_union_flag(const uint64_t *a_keys, uint64_t n_a, const uint64_t *b_keys, uint64_t n_b, uint64_t *d_flags,
+                                                   unsigned long long *d_tile_counts, hipStream_t stream) {
+    const uint64_t tiles = tbk_kmerdb_table_tiles(n_a);
+    if (!tiles) return hipSuccess;
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tbk_kmerdb_union_flag_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, n_a, b_keys, n_b, d_flags, d_tile_counts);
+    return hipGetLastError();
+}
+
+// d_tile_offsets: tiles of A + 1 (the last one the number of duplicates); the output holds n_out = n_a + n_b - duplicates
+extern "C" hipError_t tbk_launch_kmerdb_union_scatter(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *b_keys,
+                                                      const uint8_t *b_counts, uint64_t n_b, const uint64_t *d_flags,
+                                                      const unsigned long long *d_tile_offsets, uint64_t *d_out_keys, uint8_t *d_out_counts,
+                                                      uint64_t n_out, hipStream_t stream) {
+    const uint64_t tiles_a = tbk_kmerdb_table_tiles(n_a), tiles_b = tbk_kmerdb_table_tiles(n_b);
+    if (!n_out) return hipSuccess;
+    if (tiles_a > 0x7FFFFFFFull || tiles_b > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (tiles_a)
+        hipLaunchKernelGGL(tbk_kmerdb_union_scatter_a_kernel, dim3((unsigned)tiles_a), dim3(256), 0, stream, a_keys, a_counts, n_a, b_keys, b_counts, n_b,
+                           d_flags, d_tile_offsets, d_out_keys, d_out_counts, n_out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (tiles_b)
+        hipLaunchKernelGGL(tbk_kmerdb_union_scatter_b_kernel, dim3((unsigned)tiles_b), dim3(256), 0, stream, b_keys, b_counts, n_b, a_keys, n_a, d_flags,
+                           d_tile_offsets, d_out_keys, d_out_counts, n_out);
+    return hipGetLastError();
+}
+
+// d_hist: 256 words, zeroed by the caller
+extern "C" hipError_t tbk_launch_kmerdb_tally(const uint8_t *d_counts, uint64_t n, unsigned long long *d_hist, hipStream_t stream) {
+    if (!n) return hipSuccess;
+    const uint64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(tbk_kmerdb_tally_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, d_counts, n, d_hist);
     return hipGetLastError();
 }

@@ -88,10 +88,19 @@ def parse_args(argv=None):
              "k-mers: give them to classify-by-kmers --compress. A database given in place of reads must agree with the run",
     )
     parser.add_argument(
+        "--keep-singletons", action="store_true",
+        help="the databases this run keeps are FULL ones: they hold the k-mers seen once too, so a later run can unite them "
+             "exactly with more reads of the same library (mother.tbkdb,new_lane.fq.gz) or with another database "
+             "(python -m trio_binning_amd.merge_databases). Needs a run that goes through databases (--keep-databases, "
+             "--child, or a database among the arguments); the run itself works on their solid form, so lists and "
+             "histograms are those of a run without the flag. A full database takes 9 bytes for every distinct k-mer",
+    )
+    parser.add_argument(
         "read_files", nargs=2,
         help="one comma-separated list of file paths for both libraries being compared. Files can "
              "be in fasta or fastq format, and uncompressed or gzipped. A single path ending in .tbkdb is a count "
-             "database kept by --keep-databases: it is loaded instead of counted.",
+             "database kept by --keep-databases: it is loaded instead of counted. A list may also mix full databases "
+             "(kept with --keep-singletons) and read files: the reads are counted and united with the databases.",
     )
     args = parser.parse_args(argv)
     for hap in "ab":
@@ -104,12 +113,47 @@ def parse_args(argv=None):
         parser.error("--min-count-child chooses from the child's counts: give --child too")
     if args.min_count_child is not None and args.min_count_child < 1:
         parser.error("--min-count-child {}: need 1 <= min".format(args.min_count_child))
+    arguments = list(args.read_files) + ([args.child] if args.child is not None else [])
+    if args.keep_singletons and not (args.keep_databases or args.child is not None
+                                     or any(is_database_path(s) or is_mixed_argument(s) for s in arguments)):
+        parser.error("--keep-singletons keeps full databases: give --keep-databases (or --child, or a database among the arguments)")
+    for files_string in arguments:
+        if not is_mixed_argument(files_string):
+            continue
+        # every database of a mixed list is united with freshly counted reads: its header must allow that, before anything is counted
+        for path in split_mixed_argument(files_string)[0]:
+            try:
+                info = kmers.database_file_info(path)
+            except (IOError, ValueError) as exc:
+                parser.error("{}: {}".format(path, exc))
+            if info["floor"] != 1:
+                parser.error("{} was kept without the k-mers seen once and cannot be united exactly with more reads or another "
+                             "database: count that library again with --keep-databases --keep-singletons".format(path))
+            if info["k"] != args.kmer_size:
+                parser.error("{} holds {}-mers, but -k {} was given".format(path, info["k"], args.kmer_size))
+            if info["compressed"] != args.compress:
+                parser.error("{} holds {} k-mers, but this run {}".format(
+                    path, "homopolymer-compressed" if info["compressed"] else "plain (uncompressed)",
+                    "was not given --compress" if info["compressed"] else "was given --compress"))
     return args
 
 
 def is_database_path(files_string: str) -> bool:
     """A parent argument that names one count database (*.tbkdb) and no read files."""
     return "," not in files_string and files_string.endswith(DATABASE_SUFFIX)
+
+
+def split_mixed_argument(files_string: str) -> Tuple[List[str], List[str]]:
+    """(databases, read files) of a comma-separated library argument, each in the order given."""
+    parts = [p for p in files_string.split(",") if p]
+    return [p for p in parts if p.endswith(DATABASE_SUFFIX)], [p for p in parts if not p.endswith(DATABASE_SUFFIX)]
+
+
+def is_mixed_argument(files_string: str) -> bool:
+    """A library argument that names at least one count database among several comma-separated entries, read files or
+    further databases (mother.tbkdb,new_lane.fq.gz): the reads are counted and everything is united.  One database alone is
+    `is_database_path`'s case, read files alone are neither."""
+    return "," in files_string and bool(split_mixed_argument(files_string)[0])
 
 
 def analyze_histogram(rows: Sequence[Tuple[int, int]], histogram_path: str = "") -> Tuple[int, int]:
@@ -144,14 +188,15 @@ def analyze_histogram(rows: Sequence[Tuple[int, int]], histogram_path: str = "")
     return min_coverage, max_coverage
 
 
-def count_library(paths: List[str], k: int, capacity: int, passes: int = 1, compress: bool = False) -> "kmers.KmerCounter":
+def count_library(paths: List[str], k: int, capacity: int, passes: int = 1, compress: bool = False,
+                  keep_singletons: bool = False) -> "kmers.KmerCounter":
     """Count the canonical k-mers of all files of one library (what `kmc -k<k> @files` does).
     The files are read side by side, one reader thread each (a gzip stream inflates on one core, but
     a library usually comes as many files); this thread feeds their batches to the GPU."""
     import queue
     import threading
 
-    counter = kmers.KmerCounter(k, capacity, passes=passes, compress=compress)
+    counter = kmers.KmerCounter(k, capacity, passes=passes, compress=compress, keep_singletons=keep_singletons)
     n_readers = max(1, min(len(paths), kmers.host_threads()))
     todo: "queue.Queue" = queue.Queue()
     for p in paths:
@@ -234,7 +279,7 @@ DATABASE_SHARE = 8         # 1 / this of a parent's distinct k-mers is planned t
 DATABASE_BYTES = 9         # ... and costs a key and a one-byte counter
 
 
-def choose_passes(capacity: int, bases_estimate: int, free_bytes: int, databases: int = 2) -> int:
+def choose_passes(capacity: int, bases_estimate: int, free_bytes: int, databases: int = 2, database_share: int = DATABASE_SHARE) -> int:
     """The fewest passes in which one parent of `capacity` distinct k-mers and `bases_estimate` bases can be
     counted within `free_bytes` of HBM.  A pure function of its arguments; all arithmetic in integers.
 
@@ -247,12 +292,13 @@ def choose_passes(capacity: int, bases_estimate: int, free_bytes: int, databases
       reads of the parent being counted, 0.5 bytes per base), 3 * table(P) is one class's table beside its
       doubling twin, and databases = `databases` * 9 * (capacity // 8) is what the libraries leave behind (two
       parents; three with a child): a ninth byte on every key seen at least twice, planned as an eighth of the
-      distinct k-mers (the others are the k-mers seen once that -ci2 drops).
+      distinct k-mers (the others are the k-mers seen once that -ci2 drops).  `database_share` is that 8; a run that keeps
+      the once-seen k-mers (--keep-singletons) passes 1: every distinct k-mer is kept.
 
     Returns the smallest such P; ValueError when the store and the databases alone pass the budget, or when
     more than 1024 passes would be needed."""
-    if capacity < 1 or bases_estimate < 0 or free_bytes < 0 or databases < 0:
-        raise ValueError("choose_passes: capacity must be positive, bases, free bytes and databases not negative")
+    if capacity < 1 or bases_estimate < 0 or free_bytes < 0 or databases < 0 or database_share < 1:
+        raise ValueError("choose_passes: capacity and database_share must be positive, bases, free bytes and databases not negative")
     budget = free_bytes * PLAN_FRACTION[0] // PLAN_FRACTION[1]
 
     def table(p: int) -> int:
@@ -261,7 +307,7 @@ def choose_passes(capacity: int, bases_estimate: int, free_bytes: int, databases
     if 4 * table(1) <= budget:
         return 1
     store = -(-bases_estimate * STORE_BYTES[0] // STORE_BYTES[1])
-    fixed = store + databases * DATABASE_BYTES * (capacity // DATABASE_SHARE)
+    fixed = store + databases * DATABASE_BYTES * (capacity // database_share)
     if store > budget:
         raise ValueError(
             "the reads alone ({} bases, {} bytes packed) do not fit the {} bytes planned of {} free on the GPU: "
@@ -302,9 +348,10 @@ def main(argv=None):
         raise ValueError("--passes must be between 0 and {}".format(MAX_PASSES))
     hap_ids = ["A", "B"]
     from_file = [is_database_path(s) for s in args.read_files]
+    mixed = [is_mixed_argument(s) for s in args.read_files]
     # with none of the database options both counters stay live until the dumps are written, as ever; a child is a third
     # library, and three are only ever held as databases
-    by_database = args.keep_databases or any(from_file) or args.child is not None
+    by_database = args.keep_databases or any(from_file) or any(mixed) or args.child is not None
     given = {"A": (args.min_count_a, args.max_count_a), "B": (args.min_count_b, args.max_count_b)}
     counted = list(zip(args.read_files, from_file))  # every library: (its argument, whether that is a database)
     if args.child is not None:
@@ -325,9 +372,10 @@ def main(argv=None):
         for files_string, is_db in counted:
             if is_db:
                 continue
-            paths = [p for p in files_string.split(",") if os.path.isfile(p)]  # (a missing file is reported below, in its turn)
+            paths = [p for p in split_mixed_argument(files_string)[1] if os.path.isfile(p)]  # (a missing file is reported below, in its turn)
             bases = estimate_bases(paths)
-            passes = max(passes, choose_passes(args.capacity or max(1 << 16, bases), bases, free, databases=len(counted)))
+            share = 1 if args.keep_singletons or is_mixed_argument(files_string) else DATABASE_SHARE  # (full databases keep every distinct k-mer)
+            passes = max(passes, choose_passes(args.capacity or max(1 << 16, bases), bases, free, databases=len(counted), database_share=share))
     kept = {}      # haplotype (or "child") -> the database file it can be dumped from again
     held = None    # the first HistogramError of a --keep-databases run: raised once every database is on disk
     child = [None, args.min_count_child]  # the child's database and its lower cut-off
@@ -335,8 +383,13 @@ def main(argv=None):
         for hap_id, files_string, is_db in zip(hap_ids, args.read_files, from_file):
             if is_db:
                 print("\033[92mLoading the k-mer database of haplotype {}...\033[0m".format(hap_id), file=sys.stderr)
-                libraries.append([kmers.KmerDatabase.load(files_string), None, None])
+                libraries.append([kmers.load_solid_database(files_string), None, None])
                 kept[hap_id] = files_string
+            elif by_database:
+                keep_as = os.path.join(args.outpath, "haplotype{}{}".format(hap_id, DATABASE_SUFFIX)) if args.keep_databases else None
+                libraries.append([library_database(files_string, "haplotype " + hap_id, args, passes, keep_as), None, None])
+                if keep_as:
+                    kept[hap_id] = keep_as
             else:
                 print("\033[92mCounting k-mers in haplotype {}...\033[0m".format(hap_id), file=sys.stderr)
                 paths = files_string.split(",")
@@ -345,18 +398,7 @@ def main(argv=None):
                         raise IOError("no such file: {}".format(p))
                 # (in passes the table holds one class and is not bound by what two resident tables may take)
                 capacity = args.capacity or (estimate_capacity(paths) if passes == 1 else max(1 << 16, estimate_bases(paths)))
-                counter = count_library(paths, k, capacity, passes, args.compress)
-                if by_database:
-                    # the database takes the counter's place: its table leaves the HBM before the other parent is counted
-                    try:
-                        libraries.append([counter.database(), None, None])
-                    finally:
-                        counter.close()
-                    if args.keep_databases:
-                        kept[hap_id] = os.path.join(args.outpath, "haplotype{}{}".format(hap_id, DATABASE_SUFFIX))
-                        libraries[-1][0].save(kept[hap_id])
-                else:
-                    libraries.append([counter, None, None])
+                libraries.append([count_library(paths, k, capacity, passes, args.compress), None, None])
             print("\033[92mComputing and analyzing histogram...\033[0m", file=sys.stderr)
             histogram_path = os.path.join(args.scratch_dir, "haplotype{}.histogram".format(hap_id))
             rows = write_histogram(histogram_path, libraries[-1][0].histogram())
@@ -376,23 +418,13 @@ def main(argv=None):
             # third, when each parent's counter has become its database and is closed
             if counted[2][1]:
                 print("\033[92mLoading the k-mer database of the child...\033[0m", file=sys.stderr)
-                child[0] = kmers.KmerDatabase.load(args.child)
+                child[0] = kmers.load_solid_database(args.child)
                 kept["child"] = args.child
             else:
-                print("\033[92mCounting k-mers in the child...\033[0m", file=sys.stderr)
-                paths = args.child.split(",")
-                for p in paths:
-                    if not os.path.isfile(p):
-                        raise IOError("no such file: {}".format(p))
-                capacity = args.capacity or (estimate_capacity(paths) if passes == 1 else max(1 << 16, estimate_bases(paths)))
-                counter = count_library(paths, k, capacity, passes, args.compress)
-                try:
-                    child[0] = counter.database()
-                finally:
-                    counter.close()
-                if args.keep_databases:
-                    kept["child"] = os.path.join(args.outpath, "child" + DATABASE_SUFFIX)
-                    child[0].save(kept["child"])
+                keep_as = os.path.join(args.outpath, "child" + DATABASE_SUFFIX) if args.keep_databases else None
+                child[0] = library_database(args.child, "the child", args, passes, keep_as)
+                if keep_as:
+                    kept["child"] = keep_as
             print("\033[92mComputing and analyzing histogram...\033[0m", file=sys.stderr)
             histogram_path = os.path.join(args.scratch_dir, "child.histogram")
             rows = write_histogram(histogram_path, child[0].histogram())
@@ -423,6 +455,53 @@ def main(argv=None):
     what = "unique k-mers" if args.child is None else "unique k-mers the child inherited"
     print("\n\n\033[94m# of {} in haplotype A: {}\033[0m".format(what, n_a), file=sys.stderr)
     print("\033[94m# of {} in haplotype B: {}\033[0m".format(what, n_b), file=sys.stderr)
+
+
+def library_database(files_string: str, whose: str, args, passes: int, keep_as=None) -> "kmers.KmerDatabase":
+    """The database a run works on, for a library given as read files or as a mix of full databases and read files
+    (`is_mixed_argument`; parse_args has checked the databases' headers).  The reads are counted - keeping the once-seen
+    k-mers when the result is to be united or kept full - and exported, the counter's table leaves the HBM, and the loaded
+    databases are united with the result one after the other, each input freed as the fold goes.  `keep_as` saves what was
+    made: the united database, full with --keep-singletons or a mixed list.  What comes back is its solid form."""
+    databases, paths = split_mixed_argument(files_string)
+    full = bool(databases) or args.keep_singletons
+    for p in paths:
+        if not os.path.isfile(p):
+            raise IOError("no such file: {}".format(p))
+    db = None
+    try:
+        if paths:
+            print("\033[92mCounting k-mers in {}...\033[0m".format(whose), file=sys.stderr)
+            # (in passes the table holds one class and is not bound by what two resident tables may take)
+            capacity = args.capacity or (estimate_capacity(paths) if passes == 1 else max(1 << 16, estimate_bases(paths)))
+            counter = count_library(paths, args.kmer_size, capacity, passes, args.compress, keep_singletons=full)
+            try:
+                db = counter.database()  # the database takes the counter's place
+            finally:
+                counter.close()
+        for path in databases:
+            print("\033[92mUniting {} with the k-mer database {}...\033[0m".format(whose, path), file=sys.stderr)
+            more = kmers.KmerDatabase.load(path)
+            if db is None:
+                db = more
+                continue
+            try:
+                united = db.union(more)
+            finally:
+                more.close()
+            db.close()
+            db = united
+        if keep_as:
+            db.save(keep_as)
+        if db.floor >= 2:
+            return db
+        solid = db.solid()
+    except BaseException:
+        if db is not None:
+            db.close()
+        raise
+    db.close()
+    return solid
 
 
 def redump_advice(args, kept, libraries, child_min=None) -> str:

@@ -900,20 +900,26 @@ class KmerCounter:
 
     ``compress`` counts in homopolymer-compressed space: every batch goes through ``HomopolymerCompressor`` (case folded)
     before its k-mers are cut, ``bases_added`` counts the bases that are left, and the database says so (``KmerDatabase.compressed``);
-    ``unique`` needs both counters to agree on it."""
+    ``unique`` needs both counters to agree on it.
 
-    def __init__(self, k: int, capacity: int, device: Optional[int] = None, passes: int = 1, store_limit: int = 0, compress: bool = False):
+    ``keep_singletons`` makes ``database()`` a FULL database: the k-mers seen once are entries too (counters 1..255), so two
+    such databases can be united exactly (``KmerDatabase.union``).  Histogram and ``unique`` answer as without it."""
+
+    def __init__(self, k: int, capacity: int, device: Optional[int] = None, passes: int = 1, store_limit: int = 0, compress: bool = False,
+                 keep_singletons: bool = False):
         self._h = C.c_void_p()
         self.k = k
         self.passes = passes
         self.compress = bool(compress)
+        self.keep_singletons = bool(keep_singletons)
         self.device = default_device() if device is None else device
-        if passes == 1 and not store_limit and not compress:
+        if passes == 1 and not store_limit and not compress and not keep_singletons:
             check(lib.tbk_counter_create(k, capacity, self.device, C.byref(self._h)))
         else:
             opts = _lib.CounterOptions()
             lib.tbk_counter_options_init(C.byref(opts))
             opts.passes, opts.store_limit_bytes, opts.compress = passes, store_limit, int(self.compress)
+            opts.keep_singletons = int(self.keep_singletons)
             check(lib.tbk_counter_create_opts(k, capacity, C.byref(opts), self.device, C.byref(self._h)))
 
     def add_reads(self, reads: Sequence[str]) -> None:
@@ -1004,8 +1010,23 @@ def database_file_info(path: str) -> dict:
                                    C.byref(reads), C.byref(bases)))
     flag = C.c_int()
     check(lib.tbk_kmerdb_file_compressed(os.fsencode(path), C.byref(flag)))
+    floor = C.c_int()
+    check(lib.tbk_kmerdb_file_floor(os.fsencode(path), C.byref(floor)))
     return {"k": k.value, "n": n.value, "histogram": hist, "reads_added": reads.value, "bases_added": bases.value,
-            "compressed": bool(flag.value)}
+            "compressed": bool(flag.value), "floor": floor.value}
+
+
+def load_solid_database(path: str, device: Optional[int] = None) -> "KmerDatabase":
+    """A ``*.tbkdb`` file for a consumer that works on k-mers seen at least twice (the list builders, the classifier's lists,
+    the phase blocks): a full file is loaded, turned solid (``KmerDatabase.solid``) and freed, so what comes back is what the
+    solid file of the same reads would have given."""
+    db = KmerDatabase.load(path, device)
+    if db.floor >= 2:
+        return db
+    try:
+        return db.solid()
+    finally:
+        db.close()
 
 
 class KmerDatabase:
@@ -1022,6 +1043,9 @@ class KmerDatabase:
         flag = C.c_int()
         check(lib.tbk_kmerdb_compressed(self._h, C.byref(flag)))
         self.compressed = bool(flag.value)  # counted in homopolymer-compressed space: its file has another magic, and it mixes with no plain one
+        floor = C.c_int()
+        check(lib.tbk_kmerdb_floor(self._h, C.byref(floor)))
+        self.floor = floor.value  # 2, or 1: a full database, which holds the k-mers seen once too (``KmerCounter(keep_singletons=True)``)
 
     @classmethod
     def load(cls, path: str, device: Optional[int] = None) -> "KmerDatabase":
@@ -1079,6 +1103,20 @@ class KmerDatabase:
         else:
             check(lib.tbk_kmerdb_inherited_table(self._h, other._h, child._h, min_count, max_count, child_min, child_max, C.byref(h)))
         return HashSet(h.value)
+
+    def union(self, other: "KmerDatabase") -> "KmerDatabase":
+        """The database of both read sets (``tbk_kmerdb_union``): exactly what one count of both would have left.  Both must
+        be full (``floor == 1``), of one k, one device and one space; ``ValueError`` otherwise."""
+        h = C.c_void_p()
+        check(lib.tbk_kmerdb_union(self._h, other._h, C.byref(h)))
+        return KmerDatabase(h)
+
+    def solid(self) -> "KmerDatabase":
+        """From a full database the one the same counter would have left without ``keep_singletons`` (``tbk_kmerdb_solid``):
+        the entries seen at least twice, the histogram as it is."""
+        h = C.c_void_p()
+        check(lib.tbk_kmerdb_solid(self._h, C.byref(h)))
+        return KmerDatabase(h)
 
     def query(self, copies: bool = False) -> "DatabaseQuery":
         """A session that scores sequences against this database (``DatabaseQuery``); ``copies`` keeps a 32-bit counter
