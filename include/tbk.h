@@ -847,6 +847,23 @@ int tbk_hpc_compress_device(tbk_hpc *h, const void *d_bases, const void *d_offse
 /* The last result to host memory: total_out bytes to `bases` (cap: its room; too little is TBK_ERR_INVALID) and
  * n_reads + 1 offsets to `offsets` (may be NULL). */
 int tbk_hpc_fetch(tbk_hpc *h, uint8_t *bases, uint64_t cap, uint64_t *offsets);
+/* The map read backwards.  The session keeps the keep bits and the scanned tile counts of its last result until its
+ * next compress call.  With total / offsets the batch as given and total_c / coff its compressed form: kept byte j
+ * (0 <= j < total_c) came from input position lift(j), the position of the j-th set keep bit, and lift(total_c) =
+ * total.  Then lift(coff[r]) == offsets[r] for every r in 0 .. n_reads (empty reads included), and window w of k bytes
+ * of compressed read r covers the original bases [lift(coff[r] + w) - offsets[r], lift(coff[r] + w + k) - offsets[r])
+ * of read r: that span compresses to exactly the window's bytes, and a window that reaches the compressed end of
+ * the read ends at the read's length - its trailing run belongs to it.
+ * tbk_hpc_lift: out[i] = lift(positions[i]) for n positions in host arrays, in any order, duplicates allowed.  n == 0
+ * is TBK_OK; a position above total_c is TBK_ERR_INVALID (nothing is written); a session without a result is
+ * TBK_ERR_INVALID; the session and its result stay usable after either refusal.  One lane bisects the tile offsets for
+ * the last tile that starts at or before its position (a homopolymer longer than a tile leaves tiles without a kept bit,
+ * which share their successor's offset); the wave then finds the keep word among the tile's 64 by popcounts and the lane
+ * selects the bit.
+ * tbk_hpc_expand: one value per kept byte in (total_c bytes), one per base of the batch as given out (total bytes):
+ * out[lift(j)] = values[j], every other byte 0.  An empty batch writes nothing. */
+int tbk_hpc_lift(tbk_hpc *h, const uint64_t *positions, uint64_t n, uint64_t *out);
+int tbk_hpc_expand(tbk_hpc *h, const uint8_t *values, uint8_t *out);
 
 /* ---- hit tracker: WHERE along a sequence the haplotype k-mers lie ------------------------ */
 /* The classifier answers with two numbers per read; the tracker keeps the positions.  A window start is a MARKER of
@@ -875,6 +892,21 @@ int tbk_hit_tracker_runs(tbk_hit_tracker *t, const uint8_t *bases, const uint64_
  * for window start w of read r; the last k - 1 bytes of a read are 0. */
 int tbk_hit_tracker_marks(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
                           uint8_t *marks);
+/* The same in homopolymer-compressed space, for lists made of compressed k-mers, reported in the coordinates of the
+ * batch as given.  The tracker owns one tbk_hpc session, made on first use; the batch goes through tbk_hpc_compress
+ * with fold_case = ignore_case, and separation, marking, compaction and run extraction run on the compressed batch as
+ * they do on a plain one.  Markers, runs and counts are those of the compressed batch (counts: what the classifier
+ * counts in compressed mode); only the coordinates are lifted (tbk_hpc_lift above), on the device.  Of a lifted run,
+ * first and last are the original positions of the first kept byte of its first and last marker's windows and end is
+ * the original end of the last marker's window, all relative to the read as given: the run covers [first, end), and
+ * end is the read's length when the window reaches the compressed end of the read.
+ * tbk_hit_tracker_marks_compressed: one byte per base of the batch as given; a window's mark sits on the first base
+ * of the window's first run, every other base is 0. */
+typedef struct tbk_hit_run_lifted { uint64_t read, first, last, end; uint32_t markers, hap; } tbk_hit_run_lifted;
+int tbk_hit_tracker_runs_compressed(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
+                                    tbk_hit_run_lifted **runs, uint64_t *n_runs, int32_t *counts);
+int tbk_hit_tracker_marks_compressed(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
+                                     uint8_t *marks);
 
 /* ---- database query: how often did the reads see the k-mers of a sequence? --------------- */
 /* A query session scores sequences (an assembly's contigs) against ONE count database.  A window start of a sequence

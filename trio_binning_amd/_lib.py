@@ -224,6 +224,8 @@ if HAS_HPC:
     _sig("tbk_hpc_compress", C.c_int, _vp, _vp, _vp, _u64, C.c_int, C.POINTER(_vp), C.POINTER(_vp), _u64p)
     _sig("tbk_hpc_compress_device", C.c_int, _vp, _vp, _vp, _u64, _u64, C.c_int, C.POINTER(_vp), C.POINTER(_vp), _u64p)
     _sig("tbk_hpc_fetch", C.c_int, _vp, _vp, _u64, _vp)
+    _sig("tbk_hpc_lift", C.c_int, _vp, _vp, _u64, _vp)
+    _sig("tbk_hpc_expand", C.c_int, _vp, _vp, _vp)
     _sig("tbk_kmerdb_compressed", C.c_int, _vp, C.POINTER(C.c_int))
     _sig("tbk_kmerdb_file_compressed", C.c_int, C.c_char_p, C.POINTER(C.c_int))
 HAS_HIT_TRACKER = hasattr(lib, "tbk_hit_tracker_create")  # (variant builds of tools/build_variant.sh may predate the hit tracker)
@@ -232,6 +234,8 @@ if HAS_HIT_TRACKER:
     _sig("tbk_hit_tracker_destroy", None, _vp)
     _sig("tbk_hit_tracker_runs", C.c_int, _vp, _vp, _vp, _u64, C.c_int, C.POINTER(_vp), _u64p, _vp)
     _sig("tbk_hit_tracker_marks", C.c_int, _vp, _vp, _vp, _u64, C.c_int, _vp)
+    _sig("tbk_hit_tracker_runs_compressed", C.c_int, _vp, _vp, _vp, _u64, C.c_int, C.POINTER(_vp), _u64p, _vp)
+    _sig("tbk_hit_tracker_marks_compressed", C.c_int, _vp, _vp, _vp, _u64, C.c_int, _vp)
 HAS_KMERDB_FULL = hasattr(lib, "tbk_kmerdb_union")  # (variant builds of tools/build_variant.sh may predate full databases)
 if HAS_KMERDB_FULL:
     _sig("tbk_kmerdb_floor", C.c_int, _vp, C.POINTER(C.c_int))

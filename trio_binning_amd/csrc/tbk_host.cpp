@@ -3173,6 +3173,10 @@ extern "C" hipError_t tbk_launch_track_runs(const uint64_t *, uint64_t, const ui
 extern "C" uint64_t tbk_track_tiles(uint64_t n_markers);
 extern "C" uint64_t tbk_track_flag_words(uint64_t n_markers);
 extern "C" hipError_t tbk_launch_kmerdb_scan(const unsigned long long *, unsigned long long *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_track_endpoints(const tbk_hit_run *, uint64_t, const uint64_t *, int, uint64_t *, hipStream_t);
+extern "C" hipError_t tbk_launch_track_lifted(const tbk_hit_run *, uint64_t, const uint64_t *, const uint64_t *, tbk_hit_run_lifted *, hipStream_t);
+extern "C" int tbk_hpc_lift_device_(tbk_hpc *, const uint64_t *, uint64_t, uint64_t *, hipStream_t);    // tbk_hpc_host.cpp
+extern "C" int tbk_hpc_expand_device_(tbk_hpc *, const uint8_t *, uint8_t *, hipStream_t);
 
 // a device buffer that only ever grows
 struct TrackBuf {
@@ -3186,6 +3190,8 @@ struct tbk_hit_tracker {
     int device = 0, k = 0;
     uint64_t wave_slots = 0;  // waves the device holds at once: the grid of the launches that stride over reads or passes
     TrackBuf bases, offsets, sep, bits_a, bits_b, pass_count, pass_offsets, markers, flags, tile_count, tile_offsets, runs, head_index, counts, marks;
+    tbk_hpc *hpc = nullptr;                            // the compressed calls' session, made on first use
+    TrackBuf endpoints, lifted_at, lifted, marks_given;  // compressed calls: 3 stream positions per run in and out, the lifted runs, the expanded marks
 };
 
 static int track_reserve(TrackBuf &b, size_t need) {
@@ -3222,13 +3228,33 @@ extern "C" void tbk_hit_tracker_destroy(tbk_hit_tracker *t) {
     if (!t) return;
     if (hipSetDevice(t->device) == hipSuccess)
         for (TrackBuf *b : {&t->bases, &t->offsets, &t->sep, &t->bits_a, &t->bits_b, &t->pass_count, &t->pass_offsets, &t->markers, &t->flags,
-                            &t->tile_count, &t->tile_offsets, &t->runs, &t->head_index, &t->counts, &t->marks})
+                            &t->tile_count, &t->tile_offsets, &t->runs, &t->head_index, &t->counts, &t->marks, &t->endpoints, &t->lifted_at,
+                            &t->lifted, &t->marks_given})
             if (b->p) (void)hipFree(b->p);
+    tbk_hpc_destroy(t->hpc);
     delete t;
 }
 
-// Upload, separate, mark: leaves the batch's offsets in t->offsets, the two bitmaps and the markers per pass, one zero
-// behind them for the scan.  *n_passes = 0: the batch has no window (fewer than k bases in all).
+// Separate and mark a batch that lies in HBM (`total` bases, at least k): leaves the two bitmaps and the markers per
+// pass, one zero behind them for the scan.
+static int track_mark_device(tbk_hit_tracker *t, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t total, int ignore_case,
+                             uint64_t *n_passes) {
+    int rc;
+    const uint64_t sep_total = total + n_reads;  // one 'N' behind every read
+    const uint64_t passes = tbk_probe_passes(sep_total);
+    if ((rc = track_reserve(t->sep, sep_total)) || (rc = track_reserve(t->bits_a, passes * 64 * 4)) || (rc = track_reserve(t->bits_b, passes * 64 * 4)) ||
+        (rc = track_reserve(t->pass_count, (passes + 1) * 8)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(t->pass_count.as<unsigned long long>() + passes, 0, 8, nullptr));
+    HIP_TRY(tbk_launch_track_separate(d_bases, d_offsets, n_reads, ignore_case, t->sep.as<uint8_t>(), t->wave_slots, nullptr));
+    HIP_TRY(tbk_launch_track_mark(t->sep.as<uint8_t>(), sep_total, passes, t->k, t->a->d_slots, t->a->n_buckets, t->b->d_slots, t->b->n_buckets,
+                                  t->bits_a.as<uint32_t>(), t->bits_b.as<uint32_t>(), t->pass_count.as<unsigned long long>(), t->wave_slots, nullptr));
+    *n_passes = passes;
+    return TBK_OK;
+}
+
+// Upload, separate, mark: leaves the batch's offsets in t->offsets beside what track_mark_device leaves.
+// *n_passes = 0: the batch has no window (fewer than k bases in all).
 static int track_mark(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case, uint64_t *n_passes) {
     *n_passes = 0;
     int rc = tbk_check_offsets_(offsets, n_reads);
@@ -3237,20 +3263,25 @@ static int track_mark(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *
     if (total && !bases) return fail(TBK_ERR_INVALID, "bases is NULL");
     if (total < (uint64_t)t->k) return TBK_OK;
     if ((rc = use_device(t->device))) return rc;
-    const uint64_t sep_total = total + n_reads;  // one 'N' behind every read
-    const uint64_t passes = tbk_probe_passes(sep_total);
-    if ((rc = track_reserve(t->bases, total)) || (rc = track_reserve(t->offsets, (n_reads + 1) * 8)) || (rc = track_reserve(t->sep, sep_total)) ||
-        (rc = track_reserve(t->bits_a, passes * 64 * 4)) || (rc = track_reserve(t->bits_b, passes * 64 * 4)) ||
-        (rc = track_reserve(t->pass_count, (passes + 1) * 8)))
-        return rc;
+    if ((rc = track_reserve(t->bases, total)) || (rc = track_reserve(t->offsets, (n_reads + 1) * 8))) return rc;
     HIP_TRY(hipMemcpyAsync(t->bases.p, bases, total, hipMemcpyHostToDevice, nullptr));
     HIP_TRY(hipMemcpyAsync(t->offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(hipMemsetAsync(t->pass_count.as<unsigned long long>() + passes, 0, 8, nullptr));
-    HIP_TRY(tbk_launch_track_separate(t->bases.as<uint8_t>(), t->offsets.as<uint64_t>(), n_reads, ignore_case, t->sep.as<uint8_t>(), t->wave_slots, nullptr));
-    HIP_TRY(tbk_launch_track_mark(t->sep.as<uint8_t>(), sep_total, passes, t->k, t->a->d_slots, t->a->n_buckets, t->b->d_slots, t->b->n_buckets,
-                                  t->bits_a.as<uint32_t>(), t->bits_b.as<uint32_t>(), t->pass_count.as<unsigned long long>(), t->wave_slots, nullptr));
-    *n_passes = passes;
-    return TBK_OK;
+    return track_mark_device(t, t->bases.as<uint8_t>(), t->offsets.as<uint64_t>(), n_reads, total, ignore_case, n_passes);
+}
+
+// The compressed calls' first half: the batch through the tracker's own compression session (fold_case = ignore_case;
+// the host form returns when the result is complete, so the null-stream work that follows may read it), then
+// separated and marked where it lies.  *n_passes = 0: the compressed batch has no window.
+static int track_mark_compressed(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
+                                 const uint64_t **d_coff, uint64_t *total_c, uint64_t *n_passes) {
+    *n_passes = 0;
+    int rc = use_device(t->device);
+    if (rc || (!t->hpc && (rc = tbk_hpc_create(t->device, &t->hpc)))) return rc;
+    void *d_bases = nullptr, *d_offsets = nullptr;
+    if ((rc = tbk_hpc_compress(t->hpc, bases, offsets, n_reads, ignore_case != 0, &d_bases, &d_offsets, total_c))) return rc;
+    *d_coff = static_cast<const uint64_t *>(d_offsets);
+    if (*total_c < (uint64_t)t->k) return TBK_OK;
+    return track_mark_device(t, static_cast<const uint8_t *>(d_bases), *d_coff, n_reads, *total_c, ignore_case, n_passes);
 }
 
 extern "C" int tbk_hit_tracker_marks(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
@@ -3270,24 +3301,20 @@ extern "C" int tbk_hit_tracker_marks(tbk_hit_tracker *t, const uint8_t *bases, c
     return TBK_OK;
 }
 
-extern "C" int tbk_hit_tracker_runs(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
-                                    tbk_hit_run **runs, uint64_t *n_runs, int32_t *counts) {
-    if (!t || !runs || !n_runs) return fail(TBK_ERR_INVALID, "NULL argument");
-    *runs = nullptr;
+// Markers and runs of the batch track_mark_device marked, left on the device: the runs in t->runs, ordered by (read,
+// first) in the coordinates of d_offsets, and - when wanted - the markers per read and list in t->counts.
+// *n_runs = 0: no marker.
+static int track_extract(tbk_hit_tracker *t, const uint64_t *d_offsets, uint64_t n_reads, uint64_t total, uint64_t passes, bool want_counts,
+                         uint64_t *n_runs) {
     *n_runs = 0;
-    if (!n_reads) return TBK_OK;
-    uint64_t passes = 0;
-    int rc = track_mark(t, bases, offsets, n_reads, ignore_case, &passes);
-    if (rc) return rc;
-    if (counts) memset(counts, 0, n_reads * 2 * sizeof(int32_t));
-    if (!passes) return TBK_OK;
+    int rc;
     // the markers: pass counts -> pass offsets, the total behind them
     unsigned long long n_markers = 0, n_heads = 0;
     if ((rc = track_reserve(t->pass_offsets, (passes + 1) * 8))) return rc;
     HIP_TRY(tbk_launch_kmerdb_scan(t->pass_count.as<unsigned long long>(), t->pass_offsets.as<unsigned long long>(), passes + 1, nullptr));
     HIP_TRY(hipMemcpy(&n_markers, t->pass_offsets.as<unsigned long long>() + passes, 8, hipMemcpyDeviceToHost));
     if (!n_markers) return TBK_OK;
-    if (n_markers > offsets[n_reads]) return fail(TBK_ERR_HIP, "hit tracker: %llu markers in %llu bases", n_markers, (unsigned long long)offsets[n_reads]);
+    if (n_markers > total) return fail(TBK_ERR_HIP, "hit tracker: %llu markers in %llu bases", n_markers, (unsigned long long)total);
     if ((rc = track_reserve(t->markers, n_markers * 8))) return rc;
     HIP_TRY(tbk_launch_track_markers(t->bits_a.as<uint32_t>(), t->bits_b.as<uint32_t>(), passes, t->pass_offsets.as<unsigned long long>(),
                                      t->markers.as<uint64_t>(), n_markers, nullptr));
@@ -3297,25 +3324,96 @@ extern "C" int tbk_hit_tracker_runs(tbk_hit_tracker *t, const uint8_t *bases, co
         (rc = track_reserve(t->tile_offsets, (tiles + 1) * 8)))
         return rc;
     HIP_TRY(hipMemsetAsync(t->tile_count.as<unsigned long long>() + tiles, 0, 8, nullptr));
-    HIP_TRY(tbk_launch_track_heads(t->markers.as<uint64_t>(), n_markers, t->offsets.as<uint64_t>(), n_reads, t->flags.as<uint64_t>(),
+    HIP_TRY(tbk_launch_track_heads(t->markers.as<uint64_t>(), n_markers, d_offsets, n_reads, t->flags.as<uint64_t>(),
                                    t->tile_count.as<unsigned long long>(), nullptr));
     HIP_TRY(tbk_launch_kmerdb_scan(t->tile_count.as<unsigned long long>(), t->tile_offsets.as<unsigned long long>(), tiles + 1, nullptr));
     HIP_TRY(hipMemcpy(&n_heads, t->tile_offsets.as<unsigned long long>() + tiles, 8, hipMemcpyDeviceToHost));
     if (!n_heads || n_heads > n_markers) return fail(TBK_ERR_HIP, "hit tracker: %llu runs of %llu markers", n_heads, n_markers);
     if ((rc = track_reserve(t->runs, n_heads * sizeof(tbk_hit_run))) || (rc = track_reserve(t->head_index, n_heads * 8))) return rc;
-    if (counts) {
+    if (want_counts) {
         if ((rc = track_reserve(t->counts, n_reads * 2 * sizeof(int32_t)))) return rc;
         HIP_TRY(hipMemsetAsync(t->counts.p, 0, n_reads * 2 * sizeof(int32_t), nullptr));
     }
-    HIP_TRY(tbk_launch_track_runs(t->markers.as<uint64_t>(), n_markers, t->offsets.as<uint64_t>(), n_reads, t->flags.as<uint64_t>(),
+    HIP_TRY(tbk_launch_track_runs(t->markers.as<uint64_t>(), n_markers, d_offsets, n_reads, t->flags.as<uint64_t>(),
                                   t->tile_offsets.as<unsigned long long>(), t->runs.as<tbk_hit_run>(), t->head_index.as<uint64_t>(), n_heads,
-                                  counts ? t->counts.as<int32_t>() : nullptr, nullptr));
-    tbk_hit_run *home = static_cast<tbk_hit_run *>(tbk_host_alloc(n_heads * sizeof(tbk_hit_run)));
+                                  want_counts ? t->counts.as<int32_t>() : nullptr, nullptr));
+    *n_runs = n_heads;
+    return TBK_OK;
+}
+
+// `n` runs of `size` bytes each from d_runs, and the counts beside them, into memory of tbk_host_alloc
+static int track_home(tbk_hit_tracker *t, const void *d_runs, uint64_t n, size_t size, uint64_t n_reads, int32_t *counts, void **home_out) {
+    void *home = tbk_host_alloc(n * size);
     if (!home) return TBK_ERR_NOMEM;
-    hipError_t e = hipMemcpy(home, t->runs.p, n_heads * sizeof(tbk_hit_run), hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(home, d_runs, n * size, hipMemcpyDeviceToHost);
     if (e == hipSuccess && counts) e = hipMemcpy(counts, t->counts.p, n_reads * 2 * sizeof(int32_t), hipMemcpyDeviceToHost);
     if (e != hipSuccess) { tbk_host_free(home); return fail(TBK_ERR_HIP, "hit tracker: %s", hipGetErrorString(e)); }
-    *runs = home;
+    *home_out = home;
+    return TBK_OK;
+}
+
+extern "C" int tbk_hit_tracker_runs(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
+                                    tbk_hit_run **runs, uint64_t *n_runs, int32_t *counts) {
+    if (!t || !runs || !n_runs) return fail(TBK_ERR_INVALID, "NULL argument");
+    *runs = nullptr;
+    *n_runs = 0;
+    if (!n_reads) return TBK_OK;
+    uint64_t passes = 0, n_heads = 0;
+    int rc = track_mark(t, bases, offsets, n_reads, ignore_case, &passes);
+    if (rc) return rc;
+    if (counts) memset(counts, 0, n_reads * 2 * sizeof(int32_t));
+    if (!passes) return TBK_OK;
+    if ((rc = track_extract(t, t->offsets.as<uint64_t>(), n_reads, offsets[n_reads], passes, counts != nullptr, &n_heads)) || !n_heads) return rc;
+    void *home = nullptr;
+    if ((rc = track_home(t, t->runs.p, n_heads, sizeof(tbk_hit_run), n_reads, counts, &home))) return rc;
+    *runs = static_cast<tbk_hit_run *>(home);
     *n_runs = n_heads;
+    return TBK_OK;
+}
+
+extern "C" int tbk_hit_tracker_runs_compressed(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
+                                               tbk_hit_run_lifted **runs, uint64_t *n_runs, int32_t *counts) {
+    if (!t || !runs || !n_runs) return fail(TBK_ERR_INVALID, "NULL argument");
+    *runs = nullptr;
+    *n_runs = 0;
+    if (!n_reads) return TBK_OK;
+    const uint64_t *d_coff = nullptr;
+    uint64_t total_c = 0, passes = 0, n_heads = 0;
+    int rc = track_mark_compressed(t, bases, offsets, n_reads, ignore_case, &d_coff, &total_c, &passes);
+    if (rc) return rc;
+    if (counts) memset(counts, 0, n_reads * 2 * sizeof(int32_t));
+    if (!passes) return TBK_OK;
+    if ((rc = track_extract(t, d_coff, n_reads, total_c, passes, counts != nullptr, &n_heads)) || !n_heads) return rc;
+    // three stream positions per run - its first and last window's first byte, the last window's end - lifted in one launch
+    if ((rc = track_reserve(t->offsets, (n_reads + 1) * 8)) || (rc = track_reserve(t->endpoints, n_heads * 3 * 8)) ||
+        (rc = track_reserve(t->lifted_at, n_heads * 3 * 8)) || (rc = track_reserve(t->lifted, n_heads * sizeof(tbk_hit_run_lifted))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(t->offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(tbk_launch_track_endpoints(t->runs.as<tbk_hit_run>(), n_heads, d_coff, t->k, t->endpoints.as<uint64_t>(), nullptr));
+    if ((rc = tbk_hpc_lift_device_(t->hpc, t->endpoints.as<uint64_t>(), n_heads * 3, t->lifted_at.as<uint64_t>(), nullptr))) return rc;
+    HIP_TRY(tbk_launch_track_lifted(t->runs.as<tbk_hit_run>(), n_heads, t->offsets.as<uint64_t>(), t->lifted_at.as<uint64_t>(),
+                                    t->lifted.as<tbk_hit_run_lifted>(), nullptr));
+    void *home = nullptr;
+    if ((rc = track_home(t, t->lifted.p, n_heads, sizeof(tbk_hit_run_lifted), n_reads, counts, &home))) return rc;
+    *runs = static_cast<tbk_hit_run_lifted *>(home);
+    *n_runs = n_heads;
+    return TBK_OK;
+}
+
+extern "C" int tbk_hit_tracker_marks_compressed(tbk_hit_tracker *t, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int ignore_case,
+                                                uint8_t *marks) {
+    if (!t) return fail(TBK_ERR_INVALID, "tracker is NULL");
+    if (!n_reads) return TBK_OK;
+    const uint64_t *d_coff = nullptr;
+    uint64_t total_c = 0, passes = 0;
+    int rc = track_mark_compressed(t, bases, offsets, n_reads, ignore_case, &d_coff, &total_c, &passes);
+    if (rc) return rc;
+    const uint64_t total = offsets[n_reads];
+    if (total && !marks) return fail(TBK_ERR_INVALID, "marks is NULL");
+    if (!passes) { if (total) memset(marks, 0, total); return TBK_OK; }
+    if ((rc = track_reserve(t->marks, total_c)) || (rc = track_reserve(t->marks_given, (total + 15) & ~(uint64_t)15))) return rc;
+    HIP_TRY(tbk_launch_track_marks(t->bits_a.as<uint32_t>(), t->bits_b.as<uint32_t>(), d_coff, n_reads, t->marks.as<uint8_t>(), t->wave_slots, nullptr));
+    if ((rc = tbk_hpc_expand_device_(t->hpc, t->marks.as<uint8_t>(), t->marks_given.as<uint8_t>(), nullptr))) return rc;
+    HIP_TRY(hipMemcpy(marks, t->marks_given.p, total, hipMemcpyDeviceToHost));
     return TBK_OK;
 }

@@ -195,6 +195,109 @@ tbk_hpc_offsets_kernel(const uint64_t *__restrict__ offsets, uint64_t n_reads, u
     out_offsets[r] = rank;
 }
 
+// ---- the map read backwards: compressed position -> input position (lift), compressed bytes -> input bytes (expand) ----
+
+// The position of set bit number r (from 0) of w, r < popcount(w): the half that holds it, five times over.
+__device__ __forceinline__ uint32_t hpc_select64(uint64_t w, uint32_t r) {
+    uint32_t x = (uint32_t)w, at = 0;
+    uint32_t c = (uint32_t)__popc(x);
+    if (r >= c) { r -= c; at = 32; x = (uint32_t)(w >> 32); }
+#pragma unroll
+    for (uint32_t half = 16; half > 0; half >>= 1) {
+        c = (uint32_t)__popc(x & ((1u << half) - 1u));
+        if (r >= c) { r -= c; at += half; x >>= half; }
+    }
+    return at;
+}
+
+// out[i] = the input position of kept byte positions[i]: the position of set keep bit number positions[i].  A position at
+// (or past: the host refuses those) the compressed total gives `total`.  A lane bisects the tiles + 1 tile offsets for the
+// LAST tile whose offset is not above its position - an empty tile has its successor's offset, and a homopolymer longer
+// than a tile leaves such tiles - which is then a tile that holds the bit.  The wave serves its lanes' positions in
+// turn: the 64 lanes load the tile's 64 keep words as one 512-byte read, popcount, scan the counts across the wave and
+// ballot for the word; the owner selects the bit.  No atomics; nothing waits for another wave.
+__global__ void __launch_bounds__(256)
+tbk_hpc_lift_kernel(const uint64_t *__restrict__ positions, uint64_t n, const uint64_t *__restrict__ keep64,
+                    const unsigned long long *__restrict__ tile_offsets, uint64_t tiles, uint64_t total, uint64_t *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long tile = 0;
+    uint32_t rank = 0;  // of the bit among its tile's
+    bool inside = false;
+    if (i < n) {
+        const uint64_t j = positions[i];
+        if (j >= tile_offsets[tiles]) {
+            out[i] = total;
+        } else {
+            uint64_t lo = 0, hi = tiles;  // tile_offsets[lo] <= j < tile_offsets[hi]
+            while (hi - lo > 1) {
+                const uint64_t mid = lo + (hi - lo) / 2;
+                if (tile_offsets[mid] <= j) lo = mid; else hi = mid;
+            }
+            tile = lo;
+            rank = (uint32_t)(j - tile_offsets[lo]);
+            inside = true;
+        }
+    }
+    uint64_t todo = __builtin_amdgcn_ballot_w64(inside);
+    while (todo) {  // (the same in every lane)
+        const uint32_t owner = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
+        todo &= todo - 1ull;
+        const unsigned long long t = __shfl(tile, (int)owner);
+        const uint32_t r = __shfl(rank, (int)owner);
+        const unsigned long long word = keep64[t * TBK_HPC_WORDS + lane];
+        const uint32_t mine = (uint32_t)__popcll(word);
+        uint32_t upto = mine;  // inclusive prefix sum over the words of the tile
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t below = __shfl_up(upto, d);
+            if (lane >= (uint32_t)d) upto += below;
+        }
+        const uint64_t reached = __builtin_amdgcn_ballot_w64(upto > r);
+        if (!reached) continue;  // (never: the rank is below the tile's count)
+        const uint32_t w = (uint32_t)__ffsll((unsigned long long)reached) - 1u;
+        const unsigned long long the_word = __shfl(word, (int)w);
+        const uint32_t before = __shfl(upto - mine, (int)w);
+        if (lane == owner) out[i] = t * TBK_HPC_TILE + (uint64_t)w * 64 + hpc_select64(the_word, r - before);
+    }
+}
+
+// tbk_hpc_scatter_kernel run backwards, for one value per kept byte: input position p gets values[its rank among the
+// kept bits] if its keep bit is set and 0 if not.  One block per tile of the input, a lane per 16-byte vector; the
+// lane's first rank is the tile's offset plus the prefix sum of the keep popcounts below it.  One aligned 16-byte
+// store per lane, byte by byte where `total` cuts the vector.
+__global__ void __launch_bounds__(256)
+tbk_hpc_expand_kernel(const uint8_t *__restrict__ values, uint64_t total_c, const uint16_t *__restrict__ keep16,
+                      const unsigned long long *__restrict__ tile_offsets, uint64_t total, uint8_t *__restrict__ out) {
+    __shared__ uint32_t wave_sum[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t pos = (uint64_t)blockIdx.x * TBK_HPC_TILE + (uint64_t)threadIdx.x * 16;
+    const uint32_t keep = keep16[pos >> 4];
+    const uint32_t mine = (uint32_t)__popc(keep);
+    uint32_t upto = mine;  // inclusive prefix sum over the lanes of the wave
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t below = __shfl_up(upto, d);
+        if (lane >= (uint32_t)d) upto += below;
+    }
+    if (lane == 63) wave_sum[wave] = upto;
+    __syncthreads();
+    uint64_t at = tile_offsets[blockIdx.x] + (upto - mine);
+    for (uint32_t w = 0; w < wave; w++) at += wave_sum[w];
+    uint32_t word[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t j = 0; j < 16; j++)
+        if ((keep >> j) & 1u) {
+            if (at < total_c) word[j >> 2] |= (uint32_t)values[at] << (8 * (j & 3));
+            at++;
+        }
+    if (pos + 16 <= total) {
+        *reinterpret_cast<uint4 *>(out + pos) = make_uint4(word[0], word[1], word[2], word[3]);
+    } else {
+#pragma unroll
+        for (uint32_t i = 0; i < 16; i++)
+            if (pos + i < total) out[pos + i] = (uint8_t)(word[i >> 2] >> (8 * (i & 3)));
+    }
+}
+
 // =======================================================================================
 // launchers (called from tbk_hpc_host.cpp)
 // =======================================================================================
@@ -234,5 +337,25 @@ extern "C" hipError_t tbk_launch_hpc_move(const uint8_t *d_bases, const uint64_t
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(tbk_hpc_offsets_kernel, dim3((unsigned)read_blocks), dim3(256), 0, stream, d_offsets, n_reads, total, d_keep, d_tile_offsets,
                        d_out_offsets);
+    return hipGetLastError();
+}
+
+// d_keep, d_tile_offsets: what tbk_launch_hpc_mark left for an input of `total` bases.  n positions in, n out.
+extern "C" hipError_t tbk_launch_hpc_lift(const uint64_t *d_positions, uint64_t n, const uint64_t *d_keep, const unsigned long long *d_tile_offsets,
+                                          uint64_t total, uint64_t *d_out, hipStream_t stream) {
+    const uint64_t tiles = tbk_hpc_tiles(total), blocks = (n + 255) / 256;
+    if (!n) return hipSuccess;
+    if (!tiles || tiles > 0x7FFFFFFFull || blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tbk_hpc_lift_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_positions, n, d_keep, d_tile_offsets, tiles, total, d_out);
+    return hipGetLastError();
+}
+
+// d_values: total_c bytes; d_out: 16-byte aligned, `total` bytes rounded up to 16
+extern "C" hipError_t tbk_launch_hpc_expand(const uint8_t *d_values, uint64_t total_c, const uint64_t *d_keep, const unsigned long long *d_tile_offsets,
+                                            uint64_t total, uint8_t *d_out, hipStream_t stream) {
+    const uint64_t tiles = tbk_hpc_tiles(total);
+    if (!tiles || tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tbk_hpc_expand_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, d_values, total_c, reinterpret_cast<const uint16_t *>(d_keep),
+                       d_tile_offsets, total, d_out);
     return hipGetLastError();
 }

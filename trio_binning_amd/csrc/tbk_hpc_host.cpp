@@ -1,6 +1,7 @@
 // tbk_hpc_host.cpp — host side of homopolymer compression (kernels: tbk_hpc.hip; the contract: include/tbk.h).
 // A session owns a stream and its device buffers, which grow to the largest batch seen; a batch is five launches
-// queued back to back and one 16-byte copy home (the compressed total and the verdict on the offsets).
+// queued back to back and one 16-byte copy home (the compressed total and the verdict on the offsets).  The keep bits
+// and the tile offsets stay until the next compress call: lift and expand read the map backwards from them.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -18,6 +19,8 @@ extern "C" hipError_t tbk_launch_hpc_mark(const uint8_t *, const uint64_t *, uin
                                           unsigned long long *, unsigned long long *, hipStream_t);
 extern "C" hipError_t tbk_launch_hpc_move(const uint8_t *, const uint64_t *, uint64_t, uint64_t, const uint64_t *, const unsigned long long *, uint8_t *,
                                           uint64_t, uint64_t *, hipStream_t);
+extern "C" hipError_t tbk_launch_hpc_lift(const uint64_t *, uint64_t, const uint64_t *, const unsigned long long *, uint64_t, uint64_t *, hipStream_t);
+extern "C" hipError_t tbk_launch_hpc_expand(const uint8_t *, uint64_t, const uint64_t *, const unsigned long long *, uint64_t, uint8_t *, hipStream_t);
 
 static int hfail(int code, const char *fmt, ...) {
     char buf[512];
@@ -50,8 +53,10 @@ struct tbk_hpc {
     HpcBuf in_bases, in_offsets;        // a host batch on its way in
     HpcBuf out_bases, out_offsets;      // the result
     HpcBuf starts, keep, tiles;         // one bit per base each; tiles + 1 counts, tiles + 1 offsets, the verdict word
+    HpcBuf back_in, back_out;           // a host array on its way through lift or expand
     bool valid = false;                 // a result is there to fetch
     uint64_t n_reads = 0, total = 0;    // of the result
+    uint64_t in_total = 0;              // bases of the batch it was made of: what `keep` and the tile offsets describe
 };
 
 static int hpc_device(const tbk_hpc *h) {
@@ -101,7 +106,7 @@ extern "C" void tbk_hpc_destroy(tbk_hpc *h) {
             (void)hipStreamSynchronize(h->stream);
             (void)hipStreamDestroy(h->stream);
         }
-        for (HpcBuf *b : {&h->in_bases, &h->in_offsets, &h->out_bases, &h->out_offsets, &h->starts, &h->keep, &h->tiles})
+        for (HpcBuf *b : {&h->in_bases, &h->in_offsets, &h->out_bases, &h->out_offsets, &h->starts, &h->keep, &h->tiles, &h->back_in, &h->back_out})
             if (b->p) (void)hipFree(b->p);
     }
     delete h;
@@ -117,7 +122,7 @@ static int hpc_run(tbk_hpc *h, const uint8_t *d_bases, const uint64_t *d_offsets
         HHIP(hipMemsetAsync(h->out_offsets.p, 0, (size_t)(n_reads + 1) * 8, h->stream));
         HHIP(hipMemsetAsync(h->out_bases.p, 0, 64, h->stream));
         HHIP(hipStreamSynchronize(h->stream));
-        h->valid = true; h->n_reads = n_reads; h->total = 0;
+        h->valid = true; h->n_reads = n_reads; h->total = 0; h->in_total = 0;
         return TBK_OK;
     }
     if (((uintptr_t)d_bases & 15u) != 0) return hfail(TBK_ERR_INVALID, "the bases of a device batch must be 16-byte aligned");
@@ -137,7 +142,7 @@ static int hpc_run(tbk_hpc *h, const uint8_t *d_bases, const uint64_t *d_offsets
     // what lies behind the result reads as not-ACGT, whatever a consumer's vector loads take with them
     HHIP(hipMemsetAsync(h->out_bases.as<uint8_t>() + home[0], 0, 64, h->stream));
     HHIP(hipStreamSynchronize(h->stream));
-    h->valid = true; h->n_reads = n_reads; h->total = home[0];
+    h->valid = true; h->n_reads = n_reads; h->total = home[0]; h->in_total = total;
     return TBK_OK;
 }
 
@@ -191,4 +196,60 @@ extern "C" int tbk_hpc_fetch(tbk_hpc *h, uint8_t *bases, uint64_t cap, uint64_t 
     if (offsets) HHIP(hipMemcpyAsync(offsets, h->out_offsets.p, (size_t)(h->n_reads + 1) * 8, hipMemcpyDeviceToHost, h->stream));
     HHIP(hipStreamSynchronize(h->stream));
     return TBK_OK;
+}
+
+// ---- the map read backwards ----------------------------------------------------------------------------------------
+static unsigned long long *hpc_tile_offsets(const tbk_hpc *h) { return h->tiles.as<unsigned long long>() + tbk_hpc_tiles(h->in_total) + 1; }
+
+// For the hit tracker: n positions of the last result's compressed stream, in HBM, to positions of the batch it was made
+// of.  Queued on `stream`, which must be ordered behind the compress call's return; nothing is waited for.
+extern "C" int tbk_hpc_lift_device_(tbk_hpc *h, const uint64_t *d_positions, uint64_t n, uint64_t *d_out, hipStream_t stream) {
+    if (!h || !h->valid) return hfail(TBK_ERR_INVALID, "the session holds no result");
+    if (!n) return TBK_OK;
+    if (!h->in_total) {  // an empty batch: the one position there is, 0, is its end
+        HHIP(hipMemsetAsync(d_out, 0, (size_t)n * 8, stream));
+        return TBK_OK;
+    }
+    HHIP(tbk_launch_hpc_lift(d_positions, n, h->keep.as<uint64_t>(), hpc_tile_offsets(h), h->in_total, d_out, stream));
+    return TBK_OK;
+}
+
+// One byte per kept byte in, one byte per base of the batch out (d_out 16-byte aligned, room rounded up to 16).
+extern "C" int tbk_hpc_expand_device_(tbk_hpc *h, const uint8_t *d_values, uint8_t *d_out, hipStream_t stream) {
+    if (!h || !h->valid) return hfail(TBK_ERR_INVALID, "the session holds no result");
+    if (!h->in_total) return TBK_OK;
+    HHIP(tbk_launch_hpc_expand(d_values, h->total, h->keep.as<uint64_t>(), hpc_tile_offsets(h), h->in_total, d_out, stream));
+    return TBK_OK;
+}
+
+extern "C" int tbk_hpc_lift(tbk_hpc *h, const uint64_t *positions, uint64_t n, uint64_t *out) {
+    if (!h) return hfail(TBK_ERR_INVALID, "session is NULL");
+    if (!h->valid) return hfail(TBK_ERR_INVALID, "the session holds no result");
+    if (!n) return TBK_OK;
+    if (!positions || !out) return hfail(TBK_ERR_INVALID, "NULL argument");
+    for (uint64_t i = 0; i < n; i++)
+        if (positions[i] > h->total)
+            return hfail(TBK_ERR_INVALID, "position %llu (number %llu) lies behind the %llu compressed bases", (unsigned long long)positions[i],
+                         (unsigned long long)i, (unsigned long long)h->total);
+    int rc = hpc_device(h);
+    if (rc || (rc = hpc_reserve(h->back_in, (size_t)n * 8)) || (rc = hpc_reserve(h->back_out, (size_t)n * 8))) return rc;
+    HHIP(hipMemcpyAsync(h->back_in.p, positions, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    rc = tbk_hpc_lift_device_(h, h->back_in.as<uint64_t>(), n, h->back_out.as<uint64_t>(), h->stream);
+    if (!rc) HHIP(hipMemcpyAsync(out, h->back_out.p, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    HHIP(hipStreamSynchronize(h->stream));
+    return rc;
+}
+
+extern "C" int tbk_hpc_expand(tbk_hpc *h, const uint8_t *values, uint8_t *out) {
+    if (!h) return hfail(TBK_ERR_INVALID, "session is NULL");
+    if (!h->valid) return hfail(TBK_ERR_INVALID, "the session holds no result");
+    if (!h->in_total) return TBK_OK;
+    if (!values || !out) return hfail(TBK_ERR_INVALID, "NULL argument");
+    int rc = hpc_device(h);
+    if (rc || (rc = hpc_reserve(h->back_in, (size_t)h->total)) || (rc = hpc_reserve(h->back_out, (((size_t)h->in_total + 15) & ~(size_t)15)))) return rc;
+    HHIP(hipMemcpyAsync(h->back_in.p, values, (size_t)h->total, hipMemcpyHostToDevice, h->stream));
+    rc = tbk_hpc_expand_device_(h, h->back_in.as<uint8_t>(), h->back_out.as<uint8_t>(), h->stream);
+    if (!rc) HHIP(hipMemcpyAsync(out, h->back_out.p, (size_t)h->in_total, hipMemcpyDeviceToHost, h->stream));
+    HHIP(hipStreamSynchronize(h->stream));
+    return rc;
 }

@@ -256,6 +256,40 @@ tbk_track_close_kernel(const uint64_t *__restrict__ markers, uint64_t n_markers,
     if (counts) atomicAdd(&counts[2 * read + runs[j].hap], (int32_t)n);
 }
 
+// ---- runs found in homopolymer-compressed space, in the coordinates of the batch as given ----------------------------
+// The runs above are those of the compressed batch (offsets coff).  The three endpoints of run j as positions of the
+// compressed stream - the first byte of its first and of its last marker's window, and the end of that last window -
+// go to positions[3 j ..]; tbk_hpc_lift_kernel (tbk_hpc.hip) turns them into positions of the batch as given.  The
+// window's end is at most coff[read + 1], which lifts to the next read's start: the read's length.
+__global__ void __launch_bounds__(256)
+tbk_track_endpoints_kernel(const tbk_hit_run *__restrict__ runs, uint64_t n_runs, const uint64_t *__restrict__ coff, int k,
+                           uint64_t *__restrict__ positions) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_runs) return;
+    const uint64_t base = coff[runs[j].read];
+    positions[3 * j] = base + runs[j].first;
+    positions[3 * j + 1] = base + runs[j].last;
+    positions[3 * j + 2] = base + runs[j].last + (uint64_t)k;
+}
+
+// Run j with its lifted endpoints, relative to its read as given (offsets: the batch's own).
+__global__ void __launch_bounds__(256)
+tbk_track_lifted_kernel(const tbk_hit_run *__restrict__ runs, uint64_t n_runs, const uint64_t *__restrict__ offsets,
+                        const uint64_t *__restrict__ lifted_at, tbk_hit_run_lifted *__restrict__ out) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_runs) return;
+    const tbk_hit_run run = runs[j];
+    const uint64_t start = offsets[run.read];
+    tbk_hit_run_lifted up;
+    up.read = run.read;
+    up.first = lifted_at[3 * j] - start;
+    up.last = lifted_at[3 * j + 1] - start;
+    up.end = lifted_at[3 * j + 2] - start;
+    up.markers = run.markers;
+    up.hap = run.hap;
+    out[j] = up;
+}
+
 // =======================================================================================
 // launchers (called from tbk_host.cpp)
 // =======================================================================================
@@ -326,5 +360,25 @@ extern "C" hipError_t tbk_launch_track_runs(const uint64_t *d_markers, uint64_t 
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(tbk_track_close_kernel, dim3((unsigned)close_blocks), dim3(256), 0, stream, d_markers, n_markers, d_offsets, d_head_index,
                        d_runs, n_runs, d_counts);
+    return hipGetLastError();
+}
+
+// d_positions: 3 * n_runs stream positions of the compressed batch (offsets d_coff)
+extern "C" hipError_t tbk_launch_track_endpoints(const tbk_hit_run *d_runs, uint64_t n_runs, const uint64_t *d_coff, int k, uint64_t *d_positions,
+                                                 hipStream_t stream) {
+    const uint64_t blocks = (n_runs + 255) / 256;
+    if (!n_runs) return hipSuccess;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tbk_track_endpoints_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_runs, n_runs, d_coff, k, d_positions);
+    return hipGetLastError();
+}
+
+// d_offsets: of the batch as given; d_lifted_at: the 3 * n_runs positions after the lift
+extern "C" hipError_t tbk_launch_track_lifted(const tbk_hit_run *d_runs, uint64_t n_runs, const uint64_t *d_offsets, const uint64_t *d_lifted_at,
+                                              tbk_hit_run_lifted *d_out, hipStream_t stream) {
+    const uint64_t blocks = (n_runs + 255) / 256;
+    if (!n_runs) return hipSuccess;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tbk_track_lifted_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_runs, n_runs, d_offsets, d_lifted_at, d_out);
     return hipGetLastError();
 }

@@ -561,6 +561,8 @@ class Classifier:
 
 # one raw run or phase block: tbk_hit_run (include/tbk.h), 32 bytes
 HIT_RUN_DTYPE = [("read", "<u8"), ("first", "<u8"), ("last", "<u8"), ("markers", "<u4"), ("hap", "<u4")]
+# the same found in homopolymer-compressed space, in the coordinates of the read as given: tbk_hit_run_lifted, 40 bytes
+HIT_RUN_LIFTED_DTYPE = [("read", "<u8"), ("first", "<u8"), ("last", "<u8"), ("end", "<u8"), ("markers", "<u4"), ("hap", "<u4")]
 
 
 class HitTracker:
@@ -568,7 +570,11 @@ class HitTracker:
 
     A window start is a marker of hapA or hapB by the rule of ``count_kmers_in_read`` (hapA first); a raw run is a
     maximal sequence of one read's markers, in position order, of one haplotype.  The lists are borrowed, as a
-    ``Classifier`` borrows them; the tracker owns its device buffers."""
+    ``Classifier`` borrows them; the tracker owns its device buffers.
+
+    With ``compress=True`` (lists of homopolymer-compressed k-mers) the batch is compressed on the device first, with
+    ``fold_case = ignore_case``; markers, runs and counts are those of the compressed batch, and only the coordinates are
+    lifted back to the batch as given: a run covers the bases ``[first, end)`` of its read."""
 
     def __init__(self, kmers_hap_a: HashSet, kmers_hap_b: HashSet):
         h = C.c_void_p()
@@ -577,30 +583,35 @@ class HitTracker:
         self._a, self._b = kmers_hap_a, kmers_hap_b  # keep the tables alive
         self.k = kmers_hap_a.k
 
-    def runs(self, bases: np.ndarray, offsets: np.ndarray, ignore_case: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    def runs(self, bases: np.ndarray, offsets: np.ndarray, ignore_case: bool = False, compress: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """(runs, counts): the batch's raw runs ordered by (read, first) - a structured array with the fields read, first,
         last (window starts of the first and last marker within the read), markers and hap (0 = A, 1 = B) - and the
-        markers per read and list, ``Classifier.classify_batch``'s (n_reads, 2) array."""
+        markers per read and list, ``Classifier.classify_batch``'s (n_reads, 2) array.  With ``compress`` the runs have
+        ``HIT_RUN_LIFTED_DTYPE``: first and last are the original positions of the first kept byte of the first and last
+        marker's windows, ``end`` the original end of the last marker's window; counts are those of the compressed batch."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.size - 1
         counts = np.zeros((n, 2), dtype=np.int32)
         ptr, n_runs = C.c_void_p(), C.c_uint64()
-        check(lib.tbk_hit_tracker_runs(self._h, bases.ctypes.data, offsets.ctypes.data, n, int(bool(ignore_case)), C.byref(ptr), C.byref(n_runs),
-                                       counts.ctypes.data))
-        runs = np.zeros(n_runs.value, dtype=HIT_RUN_DTYPE)
+        fn = lib.tbk_hit_tracker_runs_compressed if compress else lib.tbk_hit_tracker_runs
+        check(fn(self._h, bases.ctypes.data, offsets.ctypes.data, n, int(bool(ignore_case)), C.byref(ptr), C.byref(n_runs), counts.ctypes.data))
+        runs = np.zeros(n_runs.value, dtype=HIT_RUN_LIFTED_DTYPE if compress else HIT_RUN_DTYPE)
         if n_runs.value:
             C.memmove(runs.ctypes.data, ptr.value, runs.nbytes)
         lib.tbk_host_free(ptr)
         return runs, counts
 
-    def marks(self, bases: np.ndarray, offsets: np.ndarray, ignore_case: bool = False) -> np.ndarray:
-        """One byte per base of the batch: 0 none, 1 A, 2 B for the window that starts there (a read's last k - 1 bytes are 0)."""
+    def marks(self, bases: np.ndarray, offsets: np.ndarray, ignore_case: bool = False, compress: bool = False) -> np.ndarray:
+        """One byte per base of the batch: 0 none, 1 A, 2 B for the window that starts there (a read's last k - 1 bytes are 0).
+        With ``compress`` the window is one of the compressed read and its mark sits on the first base of the window's
+        first run, in the batch as given; every other base is 0."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = offsets.size - 1
         marks = np.zeros(int(offsets[-1]) if offsets.size else 0, dtype=np.uint8)
-        check(lib.tbk_hit_tracker_marks(self._h, bases.ctypes.data, offsets.ctypes.data, n, int(bool(ignore_case)), marks.ctypes.data))
+        fn = lib.tbk_hit_tracker_marks_compressed if compress else lib.tbk_hit_tracker_marks
+        check(fn(self._h, bases.ctypes.data, offsets.ctypes.data, n, int(bool(ignore_case)), marks.ctypes.data))
         return marks
 
     def close(self) -> None:
@@ -625,10 +636,12 @@ def phase_blocks(runs: np.ndarray, min_run: int = 1) -> np.ndarray:
     """Raw runs -> phase blocks, on the host.  Every raw run with fewer than ``min_run`` markers is dropped, in one pass
     that is not repeated; surviving runs that are now neighbours in the same read and of the same haplotype merge into
     one block: ``first`` of the first, ``last`` of the last, the markers added up.  (This project's rule - an isolated
-    hit of an error k-mer is one window, a real variant up to k neighbouring ones - not Merqury's short-range-switch rule.)"""
+    hit of an error k-mer is one window, a real variant up to k neighbouring ones - not Merqury's short-range-switch rule.)
+    Lifted runs (``HIT_RUN_LIFTED_DTYPE``: an ``end`` field) give lifted blocks, a block's ``end`` that of its last run."""
     if min_run < 1:
         raise ValueError("min_run must be at least 1")
-    runs = np.asarray(runs, dtype=HIT_RUN_DTYPE)
+    lifted = isinstance(runs, np.ndarray) and runs.dtype.names is not None and "end" in runs.dtype.names
+    runs = np.asarray(runs, dtype=HIT_RUN_LIFTED_DTYPE if lifted else HIT_RUN_DTYPE)
     kept = runs[runs["markers"] >= min_run]
     if kept.size == 0:
         return kept.copy()
@@ -638,6 +651,8 @@ def phase_blocks(runs: np.ndarray, min_run: int = 1) -> np.ndarray:
     ends = np.append(starts[1:], kept.size) - 1
     blocks = kept[starts].copy()
     blocks["last"] = kept["last"][ends]
+    if lifted:
+        blocks["end"] = kept["end"][ends]
     total = np.add.reduceat(kept["markers"].astype(np.uint64), starts)
     blocks["markers"] = np.minimum(total, 0xFFFFFFFF).astype(np.uint32)
     return blocks
@@ -1153,11 +1168,12 @@ class HomopolymerCompressor:
         self.device = default_device() if device is None else device
         check(lib.tbk_hpc_create(self.device, C.byref(self._h)))
         self._n_reads = 0
+        self._total_given = self._total = 0  # bases of the batch the last result was made of, and of the result (``expand``: out, in)
 
-    def _call(self, fn, n_reads, *args):
+    def _call(self, fn, n_reads, total_given, *args):
         d_bases, d_offsets, total = C.c_void_p(), C.c_void_p(), C.c_uint64()
         check(fn(self._h, *args, C.byref(d_bases), C.byref(d_offsets), C.byref(total)))
-        self._n_reads = n_reads
+        self._n_reads, self._total_given, self._total = n_reads, int(total_given), total.value
         return d_bases.value or 0, d_offsets.value or 0, total.value
 
     def compress_host(self, bases: np.ndarray, offsets: np.ndarray, fold_case: bool = False) -> Tuple[int, int, int]:
@@ -1166,22 +1182,43 @@ class HomopolymerCompressor:
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         n = max(offsets.size - 1, 0)
-        return self._call(lib.tbk_hpc_compress, n, bases.ctypes.data, offsets.ctypes.data, n, int(bool(fold_case)))
+        return self._call(lib.tbk_hpc_compress, n, offsets[-1] if n else 0, bases.ctypes.data, offsets.ctypes.data, n, int(bool(fold_case)))
 
     def compress_batch(self, batch, fold_case: bool = False) -> Tuple[int, int, int]:
         """``compress_host`` for a ``seq.Batch``, straight from its (pinned) buffers."""
         bases_ptr, off_ptr = batch.pointers()
-        return self._call(lib.tbk_hpc_compress, batch.n_reads, C.c_void_p(bases_ptr), C.c_void_p(off_ptr), batch.n_reads, int(bool(fold_case)))
+        n = batch.n_reads
+        total_given = C.cast(off_ptr, C.POINTER(C.c_uint64))[n] if n else 0
+        return self._call(lib.tbk_hpc_compress, n, total_given, C.c_void_p(bases_ptr), C.c_void_p(off_ptr), n, int(bool(fold_case)))
 
     def compress_device(self, d_bases: int, d_offsets: int, n_reads: int, total_bases: int, fold_case: bool = False) -> Tuple[int, int, int]:
         """The same for a batch already in HBM (``d_bases`` 16-byte aligned)."""
-        return self._call(lib.tbk_hpc_compress_device, n_reads, C.c_void_p(d_bases), C.c_void_p(d_offsets), n_reads, total_bases, int(bool(fold_case)))
+        return self._call(lib.tbk_hpc_compress_device, n_reads, total_bases if n_reads else 0, C.c_void_p(d_bases), C.c_void_p(d_offsets), n_reads, total_bases, int(bool(fold_case)))
 
     def fetch(self, total: int) -> Tuple[np.ndarray, np.ndarray]:
         """The last result as numpy arrays (``total``: what the compress call returned)."""
         bases, offsets = np.zeros(total, dtype=np.uint8), np.zeros(self._n_reads + 1, dtype=np.uint64)
         check(lib.tbk_hpc_fetch(self._h, bases.ctypes.data, total, offsets.ctypes.data))
         return bases, offsets
+
+    def lift(self, positions: np.ndarray) -> np.ndarray:
+        """Positions of the last result's compressed bases -> positions of the batch it was made of: kept byte j came from
+        input position lift(j), and the compressed total lifts to the input's total.  Any order, duplicates allowed; a
+        position above the compressed total is refused."""
+        positions = np.ascontiguousarray(positions, dtype=np.uint64)
+        out = np.zeros(positions.shape, dtype=np.uint64)
+        check(lib.tbk_hpc_lift(self._h, positions.ctypes.data, positions.size, out.ctypes.data))
+        return out
+
+    def expand(self, values: np.ndarray) -> np.ndarray:
+        """One byte per compressed base of the last result in, one per base of the batch as given out: a kept position
+        gets the byte of its compressed position, every other position 0."""
+        values = np.ascontiguousarray(values, dtype=np.uint8)
+        if values.size != self._total:
+            raise ValueError("expand: {} values for {} compressed bases".format(values.size, self._total))
+        out = np.zeros(self._total_given, dtype=np.uint8)
+        check(lib.tbk_hpc_expand(self._h, values.ctypes.data, out.ctypes.data))
+        return out
 
     def compress(self, bases: np.ndarray, offsets: np.ndarray, fold_case: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """(bases, offsets) of the compressed batch, as numpy."""

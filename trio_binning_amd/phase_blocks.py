@@ -8,6 +8,9 @@ block in a file.  A block is a stretch of the sequence whose markers are all of 
 # text lists or two count databases, settled by its own code and refused in its own words - and a sequence's marker
 # columns are the counts classify-by-kmers scores it by.  The positions come from the hit tracker (kmers.HitTracker:
 # marking and run extraction on the device); the block rule (kmers.phase_blocks) and the tables run on the host.
+# With --compress the markers are looked for in homopolymer-compressed space (lists or databases made with
+# find-unique-kmers --compress) and every coordinate is lifted back on the device: the outputs speak the coordinates of
+# the sequence as given, and a block covers [first, end) - its last window's end, which takes the trailing run with it.
 
 import argparse
 import os
@@ -49,6 +52,13 @@ def _parser() -> argparse.ArgumentParser:
     )
     parser.add_argument("--ignore-case", action="store_true", default=False,
                         help="read lower-case acgt (soft-masked sequence) as upper-case; by default they are not ACGT, as for classify-by-kmers")
+    parser.add_argument(
+        "--compress", action="store_true", default=False,
+        help="k-mer lists or count databases made by find-unique-kmers --compress: markers are looked for in the sequence with every "
+             "run of equal bases written once, and reported at the coordinates of the sequence as given. A block then runs from the "
+             "first base of its first marker's window to the end of its last marker's window, homopolymer runs included; the marker "
+             "columns are what classify-by-kmers counts in compressed mode",
+    )
     cbk._add_database_options(parser)
     return parser
 
@@ -65,17 +75,36 @@ def parse_args(argv=None):
         if what is not None and not isfile(what):
             sys.exit("{}: {} does not exist or is not a file".format(PROG, what))
     args.databases = cbk._settle_databases(args, PROG) if is_db else None
-    cbk.refuse_compressed(args.databases, PROG)
+    if args.databases is None:
+        if args.compress:
+            for list_path in (args.haplotype_a_kmers, args.haplotype_b_kmers):
+                cbk.check_compressed_list(list_path, PROG)
+    elif args.databases.compressed and not args.compress:
+        # (the outputs change meaning with compression, so the switch is explicit here and does not follow the headers)
+        sys.exit(PROG + ": {} and {} hold homopolymer-compressed k-mers (find-unique-kmers --compress): their markers lie in compressed "
+                 "space. Give --compress to look for them there and report the positions along the sequence as given, or give plain "
+                 "databases.".format(args.haplotype_a_kmers, args.haplotype_b_kmers))
+    elif args.compress and not args.databases.compressed:
+        sys.exit(PROG + ": --compress was given, but {} and {} hold plain (uncompressed) k-mers: count the parents with "
+                 "find-unique-kmers --compress".format(args.haplotype_a_kmers, args.haplotype_b_kmers))
     return args
+
+
+def block_ends(blocks, k: int):
+    """One past the last base of every block: last + k, or - of lifted blocks (--compress) - the end of the last window."""
+    import numpy as np
+
+    return blocks["end"] if "end" in blocks.dtype.names else blocks["last"] + np.uint64(k)
 
 
 def sequence_rows(n_reads: int, lengths, counts, blocks, k: int):
     """The TSV columns behind the name for every sequence of a batch, as integer arrays: length, markers_a, markers_b,
-    blocks, switches, bases_in_a_blocks, bases_in_b_blocks, longest_block.  A block's extent in bases is last + k - first."""
+    blocks, switches, bases_in_a_blocks, bases_in_b_blocks, longest_block.  A block's extent in bases is last + k - first;
+    a lifted block's (--compress) is end - first."""
     import numpy as np
 
     read = blocks["read"].astype(np.int64)
-    extent = (blocks["last"] + np.uint64(k) - blocks["first"]).astype(np.int64)
+    extent = (block_ends(blocks, k) - blocks["first"]).astype(np.int64)
     n_blocks = np.bincount(read, minlength=n_reads).astype(np.int64)
     in_hap = np.zeros((2, n_reads), dtype=np.int64)
     np.add.at(in_hap, (blocks["hap"].astype(np.int64), read), extent)
@@ -104,14 +133,14 @@ def main(argv=None):
                 while reader.next_batch(batch, _BATCH_BASES, _BATCH_READS):
                     bases, base_off, names, name_off = batch.arrays()[:4]
                     n = batch.n_reads
-                    runs, counts = tracker.runs(bases, base_off, args.ignore_case)
+                    runs, counts = tracker.runs(bases, base_off, args.ignore_case, compress=args.compress)
                     blocks = kmers.phase_blocks(runs, args.min_run)
                     text = bytes(names)
                     label = [text[int(name_off[i]):int(name_off[i + 1])].decode() for i in range(n)]
                     columns = sequence_rows(n, np.diff(base_off.astype(np.int64)), counts, blocks, k)
                     out.write("".join("\t".join([label[i]] + [str(int(c[i])) for c in columns]) + "\n" for i in range(n)))
-                    bed.write("".join("{}\t{}\t{}\t{}\t{}\n".format(label[int(b["read"])], int(b["first"]), int(b["last"]) + k, "AB"[int(b["hap"])],
-                                                                    int(b["markers"])) for b in blocks))
+                    bed.write("".join("{}\t{}\t{}\t{}\t{}\n".format(label[int(b["read"])], int(b["first"]), int(end), "AB"[int(b["hap"])],
+                                                                    int(b["markers"])) for b, end in zip(blocks, block_ends(blocks, k))))
             finally:
                 batch.close()
         out.flush()
