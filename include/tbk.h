@@ -817,6 +817,53 @@ int tbk_kmerdb_inherited(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kme
 int tbk_kmerdb_inherited_table(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kmerdb *child, uint32_t min_count, uint32_t max_count,
                                uint32_t child_min, uint32_t child_max, tbk_table **out);
 
+/* ---- counted k-mer dumps: a database from the text other counters print, and back ----------------------------
+ * `kmc_dump`, `meryl print` (tab) and `jellyfish dump -c` (space) print one line per k-mer, KMER<sep>COUNT.
+ * tbk_kmerdb_import_text makes a database of such text on one device; tbk_kmerdb_dump_text writes a database as such text.
+ * THE LINE RULE.  A line is K S D and then '\n': K exactly k bytes, each one of ACGT (lower case, N and anything else are
+ * refused); S one tab or one space; D 1 to 32 decimal digits and nothing else (no sign, no '\r').  The last line of a file
+ * may lack its '\n'.  An empty line is refused; an empty file is fine.  A line longer than k + 35 bytes is refused ("line too
+ * long").  The value of D saturates at 255; 0 is refused.  Several files are read as one text, each under its own line rule.
+ * THE KEY is the canonical k-mer - the smaller, as strings, of the k-mer and its reverse complement - as the database's
+ * lexicographic rank.  REPEATED KEYS (both strands listed, several lanes' dumps, one file given twice) fold to min(255, sum):
+ * exact on saturated counters for the reason tbk_kmerdb_union is.
+ * floor = 1 makes a full database: every entry kept, rows 1..255 summing to n, row 0 = n.  floor = 2 makes the solid form:
+ * entries whose folded counter is 1 are left out but tallied in row 1, row 0 is the number of distinct keys.  floor = 0 means
+ * 1 when any folded counter is 1, else 2.  compressed = 1: a k-mer with two equal adjacent bases is refused, and the database
+ * says that it lives in homopolymer-compressed space.  The file magic follows floor and space as for any database.
+ * REFUSALS are TBK_ERR_FORMAT, "<file>: line <1-based number>: <reason>" - the FIRST offending line in file order, whichever
+ * window it lies in; *out is NULL and the device stays usable.  A missing file is TBK_ERR_IO, no memory TBK_ERR_NOMEM.
+ * On the device (csrc/tbk_dump.hip): the files are mapped and cut into windows of window_bytes at a newline, staged through
+ * two pinned buffers on a stream of the call's own; per window one bit per byte for newlines and a count per tile of 4096
+ * bytes, the scan of the counts, and the parse - the lane that holds a line start takes the line's number from the scanned
+ * count and the popcounts below it and writes its pair there.  Then one checking pass: keys that ascend strictly (kmc_dump,
+ * meryl print of canonical counts) are neither sorted nor folded; otherwise the pairs are sorted (rocPRIM, 2k bits), the heads
+ * of runs of equal keys flagged, scanned, and scattered with their runs' saturating sums.  No block waits for another.
+ * MEMORY: 9 bytes per pair while appending, reserved for the most lines the text can hold (its bytes / (k + 3)); a second 9 n
+ * plus rocPRIM's temporary storage only when the sort runs; one window of text, n/8 + n/64 bytes during a compaction. */
+typedef struct tbk_dump_options {
+    size_t size;            /* sizeof(tbk_dump_options) of the caller (tbk_dump_options_init sets it) */
+    int k;                  /* 0: taken from the first line of the first file that has one */
+    int floor;              /* 0 auto, 1, 2 (above) */
+    int compressed;         /* 1: the k-mers are homopolymer-compressed; checked on every line, and the database says so */
+    uint64_t reads, bases;  /* stamped into the header (a dump does not know them); default 0 */
+    uint64_t window_bytes;  /* text per device window; 0 = default (64 MiB); at least 4096 */
+} tbk_dump_options;
+void tbk_dump_options_init(tbk_dump_options *o);
+int tbk_kmerdb_import_text(const char *const *paths, int n_paths, const tbk_dump_options *o, int device, tbk_kmerdb **out);
+/* Host only, no device: the bytes before the first tab or space of line 1.  An empty file, a line 1 without a separator and a
+ * k outside 1..32 are TBK_ERR_FORMAT. */
+int tbk_dump_file_k(const char *path, int *k);
+/* What `kmc_dump -ciMIN -cxMAX` writes: KMER<tab>COUNT<newline> in lexicographic order for the entries whose counter lies in
+ * [max(floor, min_count), min(255, max_count)], of any database - solid or full, plain or compressed.  An empty selection is an
+ * empty file and TBK_OK.  The selection runs on the device (flag, scan, scatter of keys and counters; skipped when every entry
+ * is selected); the 9-byte entries come home in pieces and the host's threads format them - text is (k + 4) / 9 of the entries'
+ * bytes and the link bounds a dump, so nothing is gained by formatting on the device.  Written to out_path + ".tmp" and renamed. */
+int tbk_kmerdb_dump_text(const tbk_kmerdb *db, uint32_t min_count, uint32_t max_count, const char *out_path, uint64_t *n_written);
+/* Running totals of this process's imports: calls that reached a device, those of them that had to sort, windows launched,
+ * lines parsed, and the HIP-event time of the newline and parse kernels.  Any pointer may be NULL. */
+int tbk_dump_import_stats(uint64_t *imports, uint64_t *sorts, uint64_t *windows, uint64_t *lines, double *parse_ms);
+
 /* ---- homopolymer compression: every run of equal bases written once, before k-mers are cut --------------------
  * The dominant error of ONT and HiFi reads is the length of a homopolymer run; pipelines beside this one bin in
  * homopolymer-compressed space for that reason (meryl `count compress`, Canu's and Verkko's trio modes): parental

@@ -252,6 +252,22 @@ if HAS_DB_QUERY:
     _sig("tbk_kmerdb_query_copy_spectrum", C.c_int, _vp, _vp)
     _sig("tbk_kmerdb_query_reset", C.c_int, _vp)
     _sig("tbk_kmerdb_query_set_windows_", C.c_int, _vp, _u64)  # (test hook: the running total of window starts)
+
+class DumpOptions(C.Structure):
+    """tbk_dump_options (include/tbk.h)."""
+    _fields_ = [("size", C.c_size_t), ("k", C.c_int), ("floor", C.c_int), ("compressed", C.c_int), ("reads", C.c_uint64),
+                ("bases", C.c_uint64), ("window_bytes", C.c_uint64)]
+
+
+HAS_DUMP = hasattr(lib, "tbk_kmerdb_import_text")  # (variant builds of tools/build_variant.sh may predate counted dumps)
+if HAS_DUMP:
+    _sig("tbk_dump_options_init", None, C.POINTER(DumpOptions))
+    _sig("tbk_kmerdb_import_text", C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(DumpOptions), C.c_int, C.POINTER(_vp))
+    _sig("tbk_dump_file_k", C.c_int, C.c_char_p, C.POINTER(C.c_int))
+    _sig("tbk_kmerdb_dump_text", C.c_int, _vp, C.c_uint32, C.c_uint32, C.c_char_p, _u64p)
+    _sig("tbk_dump_import_stats", C.c_int, _u64p, _u64p, _u64p, _u64p, _dp)
+    _sig("tbk_dump_set_alloc_limit_", None, _u64)  # (test hook: device bytes one import may take)
+    _sig("tbk_dump_export_timing_", C.c_int, _dp)  # (measurement hook: selection, copy home, format + write of the last export)
 _sig("tbk_calib_gather", C.c_int, C.c_int, _u64, C.c_int, C.c_int, C.c_int, _u64, C.c_int, _dp, _dp)
 _sig("tbk_calib_atomics", C.c_int, C.c_int, _u64, C.c_int, C.c_int, _dp)
 if hasattr(lib, "tbk_calib_atomics64"):

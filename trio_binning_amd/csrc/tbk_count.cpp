@@ -1378,6 +1378,31 @@ extern "C" int tbk_kmerdb_adopt_device_(uint64_t *d_keys, uint8_t *d_counts, uin
     return TBK_OK;
 }
 
+// (for tbk_dump_host.cpp, not in tbk.h: the importer of counted dumps has checked, ordered, folded and tallied its pairs on the
+// device itself and states the header; this only makes the object.  Takes over d_keys and d_counts, both NULL when n is 0.)
+extern "C" int tbk_kmerdb_make_(uint64_t *d_keys, uint8_t *d_counts, uint64_t n, int k, int device, int floor, int compressed, const uint64_t hist[256],
+                                uint64_t reads, uint64_t bases, tbk_kmerdb **out) {
+    if (out) *out = nullptr;
+    if (!out || !hist || (n && (!d_keys || !d_counts))) return cfail(TBK_ERR_INVALID, "NULL argument");
+    if (k < 1 || k > 32 || floor < 1 || floor > 2) return cfail(TBK_ERR_INVALID, "k = %d, floor = %d", k, floor);
+    tbk_kmerdb *db = new tbk_kmerdb();
+    db->device = device; db->k = k; db->n = n; db->floor = (uint32_t)floor;
+    db->compressed = compressed != 0;
+    db->d_keys = d_keys; db->d_counts = d_counts;
+    db->reads_added = reads; db->bases_added = bases;
+    memcpy(db->hist, hist, sizeof db->hist);
+    *out = db;
+    return TBK_OK;
+}
+
+// (for tbk_dump_host.cpp: the arrays a dump selects from, where they lie)
+extern "C" int tbk_kmerdb_arrays_(const tbk_kmerdb *db, const uint64_t **d_keys, const uint8_t **d_counts) {
+    if (!db || !d_keys || !d_counts) return cfail(TBK_ERR_INVALID, "NULL argument");
+    *d_keys = db->d_keys;
+    *d_counts = db->d_counts;
+    return TBK_OK;
+}
+
 // The database the same counter would have left without keep_singletons: the entries with a counter of 2 or more, in their
 // places; the header's numbers as they are.  Flag (tbk_kmerdb_flag_kernel with no B and the range 2..255), scan, scatter
 // of keys and counters; n / 8 + n / 64 bytes beside the output.

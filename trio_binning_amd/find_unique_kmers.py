@@ -6,7 +6,10 @@ cut-offs; the KMC subprocesses (`kmc`, `kmc_tools transform ... histogram`, `kmc
 kmers_subtract`, `kmc_dump`; find_unique_kmers.py:62-233) are replaced by a counting table in HBM
 behind the C-ABI (`tbk_counter_*`).  What KMC does at those call sites is restated from its
 documentation (canonical counting, -ci2, -cs255, lexicographic dump); KMC is not part of the
-reference checkout, so equality with its output is not pinned by any fixture.
+reference checkout, so equality with its output is not pinned by any fixture.  Whoever has KMC can check it now (nobody
+has yet): `kmc -k<k> -ci1 -cs255 @files db tmp` and `kmc_dump db db.txt`, then `python -m trio_binning_amd.import_database
+-o kmc.tbkdb --floor 2 --reads N --bases N db.txt`, and compare kmc.tbkdb byte for byte with the haplotypeA.tbkdb that this
+command leaves with --keep-databases on the same files.
 """
 import argparse
 import os

@@ -1031,6 +1031,22 @@ def database_file_info(path: str) -> dict:
             "compressed": bool(flag.value), "floor": floor.value}
 
 
+def dump_file_k(path: str) -> int:
+    """k of a counted k-mer dump (``KMER<tab or space>COUNT`` lines): the bytes before the first separator of line 1
+    (``tbk_dump_file_k``); touches no device.  ``IOError`` for a file that cannot be read, ``ValueError`` for an empty one,
+    a first line without a separator or a k outside 1..32."""
+    k = C.c_int()
+    check(lib.tbk_dump_file_k(os.fsencode(path), C.byref(k)))
+    return k.value
+
+
+def dump_import_stats() -> dict:
+    """Running totals of this process's dump imports (``tbk_dump_import_stats``)."""
+    imports, sorts, windows, lines, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+    check(lib.tbk_dump_import_stats(C.byref(imports), C.byref(sorts), C.byref(windows), C.byref(lines), C.byref(ms)))
+    return {"imports": imports.value, "sorts": sorts.value, "windows": windows.value, "lines": lines.value, "parse_ms": ms.value}
+
+
 def load_solid_database(path: str, device: Optional[int] = None) -> "KmerDatabase":
     """A ``*.tbkdb`` file for a consumer that works on k-mers seen at least twice (the list builders, the classifier's lists,
     the phase blocks): a full file is loaded, turned solid (``KmerDatabase.solid``) and freed, so what comes back is what the
@@ -1067,6 +1083,38 @@ class KmerDatabase:
         h = C.c_void_p()
         check(lib.tbk_kmerdb_load(os.fsencode(path), default_device() if device is None else device, C.byref(h)))
         return cls(h)
+
+    @classmethod
+    def from_dump(cls, paths, k: Optional[int] = None, floor="auto", compressed: bool = False, reads: int = 0, bases: int = 0,
+                  device: Optional[int] = None, window_bytes: int = 0) -> "KmerDatabase":
+        """The database of one or several counted dumps - ``kmc_dump``, ``meryl print``, ``jellyfish dump -c``: one
+        ``KMER<tab or space>COUNT`` line per k-mer - parsed, made canonical, ordered and folded on the device
+        (``tbk_kmerdb_import_text``; include/tbk.h has the line rule).  ``k`` None: taken from the first line.  ``floor``:
+        1 keeps the k-mers seen once (a full database), 2 leaves them out, "auto" is 1 when the dump holds any.  ``ValueError``
+        names the file and the first offending line."""
+        if isinstance(paths, (str, bytes, os.PathLike)):
+            paths = [paths]
+        paths = [os.fsencode(p) for p in paths]
+        if floor not in ("auto", 0, 1, 2):
+            raise ValueError("floor = {!r}: one of 'auto', 1, 2".format(floor))
+        o = _lib.DumpOptions()
+        lib.tbk_dump_options_init(C.byref(o))
+        o.k = 0 if k is None else int(k)
+        o.floor = 0 if floor == "auto" else int(floor)
+        o.compressed = 1 if compressed else 0
+        o.reads, o.bases, o.window_bytes = int(reads), int(bases), int(window_bytes)
+        arr = (C.c_char_p * len(paths))(*paths)
+        h = C.c_void_p()
+        check(lib.tbk_kmerdb_import_text(arr, len(paths), C.byref(o), default_device() if device is None else device, C.byref(h)))
+        return cls(h)
+
+    def dump(self, path: str, min_count: int = 1, max_count: int = 255) -> int:
+        """What ``kmc_dump -ciMIN -cxMAX`` writes: ``KMER<tab>COUNT`` lines in lexicographic order for the entries whose
+        counter lies in [max(floor, min_count), min(255, max_count)] (``tbk_kmerdb_dump_text``).  Returns the lines written."""
+        n = C.c_uint64()
+        check(lib.tbk_kmerdb_dump_text(self._h, max(0, min(int(min_count), 0xFFFFFFFF)), max(0, min(int(max_count), 0xFFFFFFFF)),
+                                       os.fsencode(path), C.byref(n)))
+        return n.value
 
     def __len__(self) -> int:
         return self._n
