@@ -194,6 +194,40 @@ def test_counters_accepted_and_folded(gpu, tmp_path):
             assert _saved(db, tmp_path) == ref.database_bytes([text], k, floor=1), name
 
 
+# runs of equal keys as (first, last) entry of the sorted pairs: across a flag word's edge, across a tile's edge (1024
+# entries), 300 ones up to a tile's last entry, from a tile's first entry on, the last two entries (of a partial tile)
+FOLD_RUNS = [(62, 65), (1022, 1025), (1748, 2047), (2048, 2050), (2506, 2507)]
+FOLD_COUNTERS = [(1, 2, 3, 4), (200, 100, 1, 1), (1,) * 300, (1, 1, 1), (1, 1)]
+
+
+def test_fold_at_word_and_tile_edges(gpu, tmp_path):
+    """The fold's heads and runs where the compaction's layout has its edges (FOLD_RUNS); every other key stands once."""
+    k = 21
+    rng = np.random.default_rng(41)
+    total = FOLD_RUNS[-1][1] + 1
+    times = []  # how often each distinct key is written, in the keys' order
+    for first, last in FOLD_RUNS:
+        times += [1] * (first - sum(times)) + [last - first + 1]
+    assert sum(times) == total
+    keys = _random_kmers(rng, len(times), k)
+    assert keys.size == 2200
+    counts = []
+    runs = iter(FOLD_COUNTERS)
+    for t in times:
+        counts += list(next(runs)) if t > 1 else [int(rng.integers(1, 300))]
+    order = rng.permutation(total)
+    text = _text(np.repeat(keys, times)[order], np.array(counts)[order], k)
+    # the positions are what this test is about: found again from the text alone
+    parsed = np.sort(ref.parse(text, k)[0])
+    heads = np.flatnonzero(np.concatenate(([True], parsed[1:] != parsed[:-1], [True])))
+    assert [(int(a), int(b) - 1) for a, b in zip(heads[:-1], heads[1:]) if b - a > 1] == FOLD_RUNS and parsed.size == total
+    for floor in (1, 2):
+        want = ref.database_bytes([text], k, floor=floor)
+        assert _imported(gpu, tmp_path, [text], floor=floor) == want, floor
+    folded = ref.fold(*ref.parse(text, k))[1]
+    assert folded[np.array(times) > 1].tolist() == [10, 255, 255, 3, 2], "the test's own expectation"
+
+
 @pytest.mark.parametrize("digits,reason", [("0", ref.ZERO), ("000", ref.ZERO), ("-1", ref.NOT_DIGITS), ("+1", ref.NOT_DIGITS), ("1.0", ref.NOT_DIGITS),
                                            ("1e3", ref.NOT_DIGITS), ("", ref.EMPTY_COUNTER), ("1" * 33, ref.TOO_MANY_DIGITS), ("1" * 34, ref.TOO_MANY_DIGITS),
                                            ("1" * 35, ref.TOO_LONG), ("1" * 5000, ref.TOO_LONG)])

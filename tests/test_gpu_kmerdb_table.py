@@ -4,7 +4,7 @@ line on top of it (classify-by-kmers reads.fq haplotypeA.tbkdb haplotypeB.tbkdb)
 The list must be what tbk_kmerdb_unique would write and create_kmer_hash_set would read back: the same keys, in the same -
 lexicographic - order.  For crafted databases (tests/kmerdb_files.py) the expected keys come from numpy alone: the range
 mask, ~np.isin against the partner's ranks, and rank -> packed key base by base.  Sizes sit on both sides of a wave (64), a
-block round (256) and a tile of the compaction (1024 entries: TBK_DBT_TILE in csrc/tbk_count_kernels.hip); the launches take
+block round (256) and a tile of the compaction (1024 entries: TBK_DBT_TILE in csrc/tbk_compact_host.h); the launches take
 one block per tile, so there is no grid stride to wrap - a database of several hundred tiles stands in for it.  Counted
 libraries are those of tests/test_gpu_kmerdb.py; their lists are checked against the text route and the CPU oracle."""
 import gzip

@@ -1,0 +1,99 @@
+// tbk_compact_host.h — the stable tile compaction of the count databases as the host sees it: "keep the flagged entries of a
+// sorted database, in their order, at their exact number".  Three launches, no block ever waits for another: flag (one bit
+// per entry, one count per tile), an exclusive scan of the tile counts (rocPRIM), scatter.  The tile, the buffers the three
+// steps share (Compaction) and the one declaration of every launcher; included by the .hip files that define the launchers
+// (a signature that drifts is a compile error) and by the .cpp files that call them.  The kernels' side: tbk_compact.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+// Round r of a block's wave w covers the 64 entries from tile * TILE + (r * 4 + w) * 64 on, and their ballot is flag word
+// tile * WORDS + r * 4 + w - so bit j of flag word i belongs to entry 64 i + j.
+constexpr uint32_t TBK_DBT_TILE = 1024;                // entries per tile
+constexpr uint32_t TBK_DBT_WORDS = TBK_DBT_TILE / 64;  // flag words per tile
+static_assert(TBK_DBT_TILE == 4 * 256 && TBK_DBT_TILE % 64 == 0, "a tile is 4 rounds of a 256-thread block and whole 64-bit flag words");
+
+constexpr uint64_t tbk_kmerdb_table_tiles(uint64_t n) { return (n + TBK_DBT_TILE - 1) / TBK_DBT_TILE; }
+
+extern "C" {
+// d_tally: 3 + 256 words, d_hist: 256 words; both zeroed by the caller
+hipError_t tbk_launch_kmerdb_check(const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, int k, uint32_t floor, unsigned long long *d_tally,
+                                   hipStream_t stream);
+hipError_t tbk_launch_kmerdb_tally(const uint8_t *d_counts, uint64_t n, unsigned long long *d_hist, hipStream_t stream);
+
+// The flag kernels: d_flags holds TBK_DBT_WORDS words per tile of the first database, d_tile_counts one count per tile.  One
+// block per tile, no grid stride.  The arrays of a partner with no entry may be NULL.
+hipError_t tbk_launch_kmerdb_flag(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *b_keys, uint64_t n_b, uint32_t ci,
+                                  uint32_t cx, uint64_t *d_flags, unsigned long long *d_tile_counts, hipStream_t stream);
+hipError_t tbk_launch_kmerdb_inherited_flag(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *b_keys, uint64_t n_b,
+                                            const uint64_t *h_keys, const uint8_t *h_counts, uint64_t n_h, uint32_t ci, uint32_t cx, uint32_t h_ci,
+                                            uint32_t h_cx, uint64_t *d_flags, unsigned long long *d_tile_counts, hipStream_t stream);
+hipError_t tbk_launch_kmerdb_union_flag(const uint64_t *a_keys, uint64_t n_a, const uint64_t *b_keys, uint64_t n_b, uint64_t *d_flags,
+                                        unsigned long long *d_tile_counts, hipStream_t stream);
+hipError_t tbk_launch_dump_heads(const uint64_t *d_keys, uint64_t n, uint64_t *d_flags, unsigned long long *d_tile_counts, hipStream_t stream);
+hipError_t tbk_launch_dump_select(const uint8_t *d_counts, uint64_t n, uint32_t lo, uint32_t hi, uint64_t *d_flags, unsigned long long *d_tile_counts,
+                                  hipStream_t stream);
+
+// d_out[i] = d_in[0] + ... + d_in[i - 1], n elements; the caller passes one element more than it has tiles, so the last is
+// the total.  Returns with the stream idle.
+hipError_t tbk_launch_kmerdb_scan(const unsigned long long *d_in, unsigned long long *d_out, uint64_t n, hipStream_t stream);
+
+// The scatters: the flagged entries to d_tile_offsets[their tile] + the flagged entries before them in the tile, n_out in
+// all - as packed keys, as ranks, as ranks with their counters, as the heads of runs with the runs' saturated sums.
+hipError_t tbk_launch_kmerdb_scatter(const uint64_t *a_keys, uint64_t n_a, const uint64_t *d_flags, const unsigned long long *d_tile_offsets, int k,
+                                     uint64_t *d_out, uint64_t n_out, hipStream_t stream);
+hipError_t tbk_launch_kmerdb_scatter_ranks(const uint64_t *a_keys, uint64_t n_a, const uint64_t *d_flags, const unsigned long long *d_tile_offsets,
+                                           uint64_t *d_out, uint64_t n_out, hipStream_t stream);
+hipError_t tbk_launch_kmerdb_scatter_pairs(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *d_flags,
+                                           const unsigned long long *d_tile_offsets, uint64_t *d_out_keys, uint8_t *d_out_counts, uint64_t n_out,
+                                           hipStream_t stream);
+hipError_t tbk_launch_dump_fold(const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, const uint64_t *d_flags,
+                                const unsigned long long *d_tile_offsets, uint64_t *d_out_keys, uint8_t *d_out_counts, uint64_t n_out,
+                                hipStream_t stream);
+// d_flags and d_tile_offsets are A's (the last offset the number of duplicates); the output holds n_out = n_a + n_b - duplicates
+hipError_t tbk_launch_kmerdb_union_scatter(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *b_keys,
+                                           const uint8_t *b_counts, uint64_t n_b, const uint64_t *d_flags, const unsigned long long *d_tile_offsets,
+                                           uint64_t *d_out_keys, uint8_t *d_out_counts, uint64_t n_out, hipStream_t stream);
+}
+
+// What a compaction over n entries holds on the device between its flag kernel and its scatter: n / 8 + n / 64 bytes.
+struct Compaction {
+    uint64_t *d_flags = nullptr;
+    unsigned long long *d_tiles = nullptr;  // tiles + 1 counts (the last one 0), then their tiles + 1 offsets (the last one the total)
+    uint64_t tiles = 0;
+    hipStream_t stream = nullptr;
+
+    Compaction() = default;
+    Compaction(const Compaction &) = delete;
+    Compaction &operator=(const Compaction &) = delete;
+    ~Compaction() { release(); }
+
+    static size_t flag_bytes(uint64_t n) { return (size_t)(tbk_kmerdb_table_tiles(n) * TBK_DBT_WORDS * sizeof(uint64_t)); }
+    static size_t tile_bytes(uint64_t n) { return (size_t)(2 * (tbk_kmerdb_table_tiles(n) + 1) * sizeof(unsigned long long)); }
+    // device bytes reserve(n) takes (for a caller that accounts for them)
+    static size_t bytes(uint64_t n) { return flag_bytes(n) + tile_bytes(n); }
+    // n == 0 is no tile: a flag buffer all the same, and the one count the scan then takes
+    hipError_t reserve(uint64_t n, hipStream_t s) {
+        tiles = tbk_kmerdb_table_tiles(n);
+        stream = s;
+        hipError_t e = hipMalloc((void **)&d_flags, flag_bytes(n) ? flag_bytes(n) : 16);
+        if (e == hipSuccess) e = hipMalloc((void **)&d_tiles, tile_bytes(n));
+        if (e == hipSuccess) e = hipMemsetAsync(d_tiles + tiles, 0, sizeof(unsigned long long), stream);
+        return e;
+    }
+    unsigned long long *counts() { return d_tiles; }
+    const unsigned long long *offsets() const { return d_tiles + tiles + 1; }
+    // after the flag kernel: scans the counts, brings the last offset home and returns with the stream idle
+    hipError_t total(unsigned long long *out) {
+        hipError_t e = tbk_launch_kmerdb_scan(d_tiles, d_tiles + tiles + 1, tiles + 1, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(out, d_tiles + 2 * tiles + 1, sizeof *out, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        return e;
+    }
+    void release() {
+        if (d_flags) (void)hipFree(d_flags);
+        if (d_tiles) (void)hipFree(d_tiles);
+        d_flags = nullptr;
+        d_tiles = nullptr;
+    }
+};

@@ -28,6 +28,7 @@
 
 #include "../../include/tbk.h"
 #include "tbk_common.h"
+#include "tbk_compact_host.h"
 
 extern "C" void tbk_set_error_(int code, const char *msg);
 extern "C" hipError_t tbk_launch_separate(const uint8_t *, const uint64_t *, uint64_t, uint8_t *, hipStream_t);
@@ -680,7 +681,6 @@ extern "C" int tbk_counter_unique(tbk_counter *a, tbk_counter *b, uint32_t min_c
 // =====================================================================================================================
 extern "C" hipError_t tbk_launch_count_export(uint64_t *, uint32_t, TbkMz, int, uint32_t, uint64_t *, uint8_t *, uint64_t, unsigned long long *, hipStream_t);
 extern "C" hipError_t tbk_launch_db_rank(const uint64_t *, const uint8_t *, uint64_t, int, uint64_t *, uint8_t *, hipStream_t);
-extern "C" hipError_t tbk_launch_kmerdb_check(const uint64_t *, const uint8_t *, uint64_t, int, uint32_t, unsigned long long *, hipStream_t);
 extern "C" hipError_t tbk_launch_kmerdb_unique(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, uint32_t, uint32_t, uint64_t *,
                                                uint64_t, unsigned long long *, hipStream_t);
 extern "C" hipError_t tbk_launch_sort_u64_u8(const uint64_t *, uint64_t *, const uint8_t *, uint8_t *, uint64_t, int, hipStream_t);
@@ -1108,13 +1108,6 @@ extern "C" int tbk_kmerdb_unique(const tbk_kmerdb *a, const tbk_kmerdb *b, uint3
 }
 
 // ---- the same subtraction as a k-mer list in HBM -------------------------------------------------------------------------
-extern "C" uint64_t tbk_kmerdb_table_tiles(uint64_t);
-extern "C" uint64_t tbk_kmerdb_table_flag_words(uint64_t);
-extern "C" hipError_t tbk_launch_kmerdb_flag(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, uint32_t, uint32_t, uint64_t *,
-                                             unsigned long long *, hipStream_t);
-extern "C" hipError_t tbk_launch_kmerdb_scan(const unsigned long long *, unsigned long long *, uint64_t, hipStream_t);
-extern "C" hipError_t tbk_launch_kmerdb_scatter(const uint64_t *, uint64_t, const uint64_t *, const unsigned long long *, int, uint64_t *, uint64_t,
-                                                hipStream_t);
 extern "C" int tbk_table_adopt_device_keys_(uint64_t *, uint64_t, int, int, int, tbk_table **);
 
 // What tbk_kmerdb_unique would write and tbk_table_create_from_file would read back, without the text in between: the
@@ -1135,21 +1128,17 @@ extern "C" int tbk_kmerdb_unique_table(const tbk_kmerdb *a, const tbk_kmerdb *b,
     if (!cap) return cfail(TBK_ERR_FORMAT, "empty k-mer list");
     const int rc = kmerdb_device(a->device);
     if (rc) return rc;
-    const uint64_t tiles = tbk_kmerdb_table_tiles(a->n), words = tbk_kmerdb_table_flag_words(a->n);
-    uint64_t *d_flags = nullptr, *d_keys = nullptr;
-    unsigned long long *d_tiles = nullptr, total = 0;  // tiles + 1 counts (the last one 0), then their tiles + 1 offsets (the last one the total)
-    hipError_t e = hipMalloc((void **)&d_flags, words * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_tiles, 2 * (tiles + 1) * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(d_tiles + tiles, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) e = tbk_launch_kmerdb_flag(a->d_keys, a->d_counts, a->n, b->d_keys, b->n, min_count, max_count, d_flags, d_tiles, nullptr);
-    if (e == hipSuccess) e = tbk_launch_kmerdb_scan(d_tiles, d_tiles + tiles + 1, tiles + 1, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(&total, d_tiles + 2 * tiles + 1, sizeof total, hipMemcpyDeviceToHost);
+    Compaction sel;
+    uint64_t *d_keys = nullptr;
+    unsigned long long total = 0;
+    hipError_t e = sel.reserve(a->n, nullptr);
+    if (e == hipSuccess) e = tbk_launch_kmerdb_flag(a->d_keys, a->d_counts, a->n, b->d_keys, b->n, min_count, max_count, sel.d_flags, sel.counts(), nullptr);
+    if (e == hipSuccess) e = sel.total(&total);
     const uint64_t n = std::min<uint64_t>(total, cap);  // (never more than the histogram allows: a list is not written past)
     if (e == hipSuccess && n) e = hipMalloc((void **)&d_keys, n * sizeof(uint64_t));
-    if (e == hipSuccess && n) e = tbk_launch_kmerdb_scatter(a->d_keys, a->n, d_flags, d_tiles + tiles + 1, a->k, d_keys, n, nullptr);
+    if (e == hipSuccess && n) e = tbk_launch_kmerdb_scatter(a->d_keys, a->n, sel.d_flags, sel.offsets(), a->k, d_keys, n, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (d_flags) (void)hipFree(d_flags);
-    if (d_tiles) (void)hipFree(d_tiles);
+    sel.release();
     if (e != hipSuccess) {
         if (d_keys) (void)hipFree(d_keys);
         (void)hipGetLastError();
@@ -1166,12 +1155,6 @@ extern "C" int tbk_kmerdb_unique_table(const tbk_kmerdb *a, const tbk_kmerdb *b,
 }
 
 // ---- three databases: what the child inherited of A's own k-mers --------------------------------------------------------
-extern "C" hipError_t tbk_launch_kmerdb_inherited_flag(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, const uint64_t *,
-                                                       const uint8_t *, uint64_t, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t *,
-                                                       unsigned long long *, hipStream_t);
-extern "C" hipError_t tbk_launch_kmerdb_scatter_ranks(const uint64_t *, uint64_t, const uint64_t *, const unsigned long long *, uint64_t *, uint64_t,
-                                                      hipStream_t);
-
 static int inherited_check(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kmerdb *child) {
     if (a->k != b->k || a->k != child->k)
         return cfail(TBK_ERR_INVALID, "the databases have different k (%d, %d and the child's %d)", a->k, b->k, child->k);
@@ -1198,25 +1181,21 @@ static int inherited_select(const char *who, const tbk_kmerdb *a, const tbk_kmer
     if (!cap) return TBK_OK;
     const int rc = kmerdb_device(a->device);
     if (rc) return rc;
-    const uint64_t tiles = tbk_kmerdb_table_tiles(a->n), words = tbk_kmerdb_table_flag_words(a->n);
-    uint64_t *d_flags = nullptr, *d_sel = nullptr;
-    unsigned long long *d_tiles = nullptr, total = 0;  // tiles + 1 counts (the last one 0), then their tiles + 1 offsets (the last one the total)
-    hipError_t e = hipMalloc((void **)&d_flags, words * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_tiles, 2 * (tiles + 1) * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(d_tiles + tiles, 0, sizeof(unsigned long long));
+    Compaction sel;
+    uint64_t *d_sel = nullptr;
+    unsigned long long total = 0;
+    hipError_t e = sel.reserve(a->n, nullptr);
     if (e == hipSuccess)
         e = tbk_launch_kmerdb_inherited_flag(a->d_keys, a->d_counts, a->n, b->d_keys, b->n, child->d_keys, child->d_counts, child->n, min_count,
-                                             max_count, child_min, child_max, d_flags, d_tiles, nullptr);
-    if (e == hipSuccess) e = tbk_launch_kmerdb_scan(d_tiles, d_tiles + tiles + 1, tiles + 1, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(&total, d_tiles + 2 * tiles + 1, sizeof total, hipMemcpyDeviceToHost);
+                                             max_count, child_min, child_max, sel.d_flags, sel.counts(), nullptr);
+    if (e == hipSuccess) e = sel.total(&total);
     const uint64_t n = std::min<uint64_t>(total, cap);  // (never more than the histograms allow: nothing is written past)
     if (e == hipSuccess && n) e = hipMalloc((void **)&d_sel, n * sizeof(uint64_t));
     if (e == hipSuccess && n)
-        e = as_keys ? tbk_launch_kmerdb_scatter(a->d_keys, a->n, d_flags, d_tiles + tiles + 1, a->k, d_sel, n, nullptr)
-                    : tbk_launch_kmerdb_scatter_ranks(a->d_keys, a->n, d_flags, d_tiles + tiles + 1, d_sel, n, nullptr);
+        e = as_keys ? tbk_launch_kmerdb_scatter(a->d_keys, a->n, sel.d_flags, sel.offsets(), a->k, d_sel, n, nullptr)
+                    : tbk_launch_kmerdb_scatter_ranks(a->d_keys, a->n, sel.d_flags, sel.offsets(), d_sel, n, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (d_flags) (void)hipFree(d_flags);
-    if (d_tiles) (void)hipFree(d_tiles);
+    sel.release();
     if (e != hipSuccess) {
         if (d_sel) (void)hipFree(d_sel);
         (void)hipGetLastError();
@@ -1276,13 +1255,6 @@ extern "C" int tbk_kmerdb_inherited_table(const tbk_kmerdb *a, const tbk_kmerdb 
 }
 
 // ---- full databases: the union of two, and the way back to the solid form -------------------------------------------------
-extern "C" hipError_t tbk_launch_kmerdb_union_flag(const uint64_t *, uint64_t, const uint64_t *, uint64_t, uint64_t *, unsigned long long *, hipStream_t);
-extern "C" hipError_t tbk_launch_kmerdb_union_scatter(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, const uint8_t *, uint64_t,
-                                                      const uint64_t *, const unsigned long long *, uint64_t *, uint8_t *, uint64_t, hipStream_t);
-extern "C" hipError_t tbk_launch_kmerdb_tally(const uint8_t *, uint64_t, unsigned long long *, hipStream_t);
-extern "C" hipError_t tbk_launch_kmerdb_scatter_pairs(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, const unsigned long long *, uint64_t *,
-                                                      uint8_t *, uint64_t, hipStream_t);
-
 // db(X) united with db(Y) is db(X ++ Y) when both are full: min(255, min(255, x) + min(255, y)) == min(255, x + y).  A's
 // entries are flagged where B holds the same key (one bit per entry of A, one count per tile of A), the tile counts are
 // scanned, the output is allocated at n_a + n_b - duplicates and both inputs are scattered to their places (the kernels'
@@ -1305,29 +1277,25 @@ extern "C" int tbk_kmerdb_union(const tbk_kmerdb *a, const tbk_kmerdb *b, tbk_km
     db->device = a->device; db->k = a->k; db->floor = 1; db->compressed = a->compressed;
     db->reads_added = a->reads_added + b->reads_added;
     db->bases_added = a->bases_added + b->bases_added;
-    const uint64_t tiles = tbk_kmerdb_table_tiles(a->n), words = tbk_kmerdb_table_flag_words(a->n);
-    uint64_t *d_flags = nullptr;
-    unsigned long long *d_tiles = nullptr, *d_hist = nullptr, dups = 0, hist[256];  // d_tiles: tiles + 1 counts (the last one 0), then their tiles + 1 offsets (the last one the total)
+    Compaction both;  // (of A's entries, the ones B holds too)
+    unsigned long long *d_hist = nullptr, dups = 0, hist[256];
     memset(hist, 0, sizeof hist);
-    hipError_t e = hipMalloc((void **)&d_flags, (words ? words : 1) * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_tiles, 2 * (tiles + 1) * sizeof(unsigned long long));
+    hipError_t e = both.reserve(a->n, nullptr);
     if (e == hipSuccess) e = hipMalloc((void **)&d_hist, sizeof hist);
-    if (e == hipSuccess) e = hipMemset(d_tiles + tiles, 0, sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(d_hist, 0, sizeof hist);
-    if (e == hipSuccess) e = tbk_launch_kmerdb_union_flag(a->d_keys, a->n, b->d_keys, b->n, d_flags, d_tiles, nullptr);
-    if (e == hipSuccess) e = tbk_launch_kmerdb_scan(d_tiles, d_tiles + tiles + 1, tiles + 1, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(&dups, d_tiles + 2 * tiles + 1, sizeof dups, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = tbk_launch_kmerdb_union_flag(a->d_keys, a->n, b->d_keys, b->n, both.d_flags, both.counts(), nullptr);
+    if (e == hipSuccess) e = both.total(&dups);
     const bool sane = dups <= a->n && dups <= b->n;  // (nothing is allocated or written by a count that cannot be)
     const uint64_t n = sane ? a->n + b->n - dups : 0;
     if (e == hipSuccess && sane && n) e = hipMalloc((void **)&db->d_keys, n * sizeof(uint64_t));
     if (e == hipSuccess && sane && n) e = hipMalloc((void **)&db->d_counts, n);
     if (e == hipSuccess && sane && n)
-        e = tbk_launch_kmerdb_union_scatter(a->d_keys, a->d_counts, a->n, b->d_keys, b->d_counts, b->n, d_flags, d_tiles + tiles + 1, db->d_keys,
+        e = tbk_launch_kmerdb_union_scatter(a->d_keys, a->d_counts, a->n, b->d_keys, b->d_counts, b->n, both.d_flags, both.offsets(), db->d_keys,
                                             db->d_counts, n, nullptr);
     if (e == hipSuccess && sane && n) e = tbk_launch_kmerdb_tally(db->d_counts, n, d_hist, nullptr);
     if (e == hipSuccess) e = hipMemcpy(hist, d_hist, sizeof hist, hipMemcpyDeviceToHost);
-    for (void *p : {(void *)d_flags, (void *)d_tiles, (void *)d_hist})
-        if (p) (void)hipFree(p);
+    both.release();
+    if (d_hist) (void)hipFree(d_hist);
     if (e != hipSuccess || !sane) {
         tbk_kmerdb_destroy(db);
         (void)hipGetLastError();
@@ -1420,23 +1388,17 @@ extern "C" int tbk_kmerdb_solid(const tbk_kmerdb *src, tbk_kmerdb **out) {
     memcpy(db->hist, src->hist, sizeof src->hist);
     unsigned long long total = 0;
     if (src->n) {
-        const uint64_t tiles = tbk_kmerdb_table_tiles(src->n), words = tbk_kmerdb_table_flag_words(src->n);
-        uint64_t *d_flags = nullptr;
-        unsigned long long *d_tiles = nullptr;
-        hipError_t e = hipMalloc((void **)&d_flags, words * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_tiles, 2 * (tiles + 1) * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMemset(d_tiles + tiles, 0, sizeof(unsigned long long));
-        if (e == hipSuccess) e = tbk_launch_kmerdb_flag(src->d_keys, src->d_counts, src->n, nullptr, 0, 2, 255, d_flags, d_tiles, nullptr);
-        if (e == hipSuccess) e = tbk_launch_kmerdb_scan(d_tiles, d_tiles + tiles + 1, tiles + 1, nullptr);
-        if (e == hipSuccess) e = hipMemcpy(&total, d_tiles + 2 * tiles + 1, sizeof total, hipMemcpyDeviceToHost);
+        Compaction sel;
+        hipError_t e = sel.reserve(src->n, nullptr);
+        if (e == hipSuccess) e = tbk_launch_kmerdb_flag(src->d_keys, src->d_counts, src->n, nullptr, 0, 2, 255, sel.d_flags, sel.counts(), nullptr);
+        if (e == hipSuccess) e = sel.total(&total);
         const bool agree = total == want;
         if (e == hipSuccess && agree && want) e = hipMalloc((void **)&db->d_keys, want * sizeof(uint64_t));
         if (e == hipSuccess && agree && want) e = hipMalloc((void **)&db->d_counts, want);
         if (e == hipSuccess && agree && want)
-            e = tbk_launch_kmerdb_scatter_pairs(src->d_keys, src->d_counts, src->n, d_flags, d_tiles + tiles + 1, db->d_keys, db->d_counts, want, nullptr);
+            e = tbk_launch_kmerdb_scatter_pairs(src->d_keys, src->d_counts, src->n, sel.d_flags, sel.offsets(), db->d_keys, db->d_counts, want, nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (d_flags) (void)hipFree(d_flags);
-        if (d_tiles) (void)hipFree(d_tiles);
+        sel.release();
         if (e != hipSuccess) {
             tbk_kmerdb_destroy(db);
             (void)hipGetLastError();

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "tbk_common.h"
+#include "tbk_compact.h"
 #include "tbk_device.h"
 
 // =======================================================================================
@@ -412,15 +413,7 @@ tbk_db_unique_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restr
         if (i < n_a) {
             key = a_keys[i];
             const uint32_t c = a_counts[i];
-            emit = c >= 2u && c >= ci && c <= cx;
-            if (emit) {
-                uint64_t lo = 0, hi = n_b;  // first element >= key
-                while (lo < hi) {
-                    const uint64_t mid = lo + (hi - lo) / 2;
-                    if (b_sorted[mid] < key) lo = mid + 1; else hi = mid;
-                }
-                emit = !(lo < n_b && b_sorted[lo] == key);
-            }
+            emit = db_counter_selected(c, ci, cx) && db_absent(b_sorted, 0, n_b, n_b, key);
         }
         const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
         if (mask) {
@@ -536,15 +529,7 @@ tbk_kmerdb_unique_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__r
         if (i < n_a) {
             key = a_keys[i];
             const uint32_t c = a_counts[i];
-            emit = c >= 2u && c >= ci && c <= cx;
-            if (emit) {
-                uint64_t lo = 0, hi = n_b;  // first element >= key
-                while (lo < hi) {
-                    const uint64_t mid = lo + (hi - lo) / 2;
-                    if (b_keys[mid] < key) lo = mid + 1; else hi = mid;
-                }
-                emit = !(lo < n_b && b_keys[lo] == key);
-            }
+            emit = db_counter_selected(c, ci, cx) && db_absent(b_keys, 0, n_b, n_b, key);
         }
         const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
         if (mask) {
@@ -562,178 +547,75 @@ tbk_kmerdb_unique_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__r
 
 // ---- the same subtraction, left in HBM as a k-mer list (tbk_kmerdb_unique_table) -------------------------------
 // A's ranks ascend, so the selected ones in their places ARE the dump's order: a stable compaction, no sort and no
-// buffer the size of the upper bound.  Three launches, no block ever waits for another: flag (one bit per entry,
-// one count per tile), an exclusive scan of the tile counts (rocPRIM), scatter.  A tile is TBK_DBT_TILE entries of
-// one block: round r of the block's wave w covers the 64 entries from tile * TILE + (r * 4 + w) * 64 on, and their
-// ballot is flag word tile * 16 + r * 4 + w - so bit j of flag word i belongs to entry 64 i + j.
-constexpr uint32_t TBK_DBT_TILE = 1024;                       // entries per tile: 4 rounds of a 256-thread block
-constexpr uint32_t TBK_DBT_WORDS = TBK_DBT_TILE / 64;         // flag words per tile
+// buffer the size of the upper bound.  Flag, scan, scatter over tiles of TBK_DBT_TILE entries: tbk_compact.h.
 
-// Selection of tbk_kmerdb_unique_kernel, kept as bits.  flags holds n_tiles * 16 words, tile_counts n_tiles.
+// Selection of tbk_kmerdb_unique_kernel, kept as bits.
 __global__ void __launch_bounds__(256)
 tbk_kmerdb_flag_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restrict__ a_counts, uint64_t n_a,
                        const uint64_t *__restrict__ b_keys, uint64_t n_b, uint32_t ci, uint32_t cx,
                        uint64_t *__restrict__ flags, unsigned long long *__restrict__ tile_counts) {
-    __shared__ uint32_t wave_count[TBK_DBT_WORDS];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t tile = blockIdx.x;
-    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
-        const uint32_t word = r * 4 + wave;
-        const uint64_t i = tile * TBK_DBT_TILE + (uint64_t)word * 64 + lane;
-        bool emit = false;
-        if (i < n_a) {
-            const uint64_t key = a_keys[i];
-            const uint32_t c = a_counts[i];
-            emit = c >= 2u && c >= ci && c <= cx;
-            if (emit) {
-                uint64_t lo = 0, hi = n_b;  // first element >= key
-                while (lo < hi) {
-                    const uint64_t mid = lo + (hi - lo) / 2;
-                    if (b_keys[mid] < key) lo = mid + 1; else hi = mid;
-                }
-                emit = !(lo < n_b && b_keys[lo] == key);
-            }
-        }
-        const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
-        if (lane == 0) {
-            flags[tile * TBK_DBT_WORDS + word] = mask;
-            wave_count[word] = (uint32_t)__popcll(mask);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-        for (uint32_t w = 0; w < TBK_DBT_WORDS; w++) sum += wave_count[w];
-        tile_counts[tile] = sum;
-    }
+    compact_flag_tile(n_a, flags, tile_counts, [=](uint64_t i) {
+        return db_counter_selected(a_counts[i], ci, cx) && db_absent(b_keys, 0, n_b, n_b, a_keys[i]);
+    });
 }
 
-// the key in the classifier's form (base i at bits 2i..2i+1, tbk_kmer_to_int) of a lexicographic rank: lex_rank's inverse
-__device__ __forceinline__ uint64_t key_of_rank(uint64_t rank, int k) {
-    const uint64_t lex = rank << (64 - 2 * k);  // (k = 32: a shift by 0)
-    return ((uint64_t)rev_pairs((uint32_t)lex) << 32) | (uint64_t)rev_pairs((uint32_t)(lex >> 32));
-}
-
-// Entry i of A goes to tile_offsets[its tile] + the flagged entries before it in the tile, converted on the way.
+// The flagged entries of A in their places, as `write(i, at)` stores them: the packed key for a table (key_of_rank), the
+// rank as it is for a list that goes to a file (write_list takes ranks), the rank and its counter for a database.
+template <typename Write>
 __global__ void __launch_bounds__(256)
-tbk_kmerdb_scatter_kernel(const uint64_t *__restrict__ a_keys, uint64_t n_a, const uint64_t *__restrict__ flags,
-                          const unsigned long long *__restrict__ tile_offsets, int k, uint64_t *__restrict__ out, uint64_t n_out) {
-    __shared__ uint64_t word_mask[TBK_DBT_WORDS];
-    __shared__ uint32_t word_before[TBK_DBT_WORDS];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t tile = blockIdx.x;
-    if (threadIdx.x < TBK_DBT_WORDS) word_mask[threadIdx.x] = flags[tile * TBK_DBT_WORDS + threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-        for (uint32_t w = 0; w < TBK_DBT_WORDS; w++) {
-            word_before[w] = sum;
-            sum += (uint32_t)__popcll(word_mask[w]);
-        }
-    }
-    __syncthreads();
-    const uint64_t base = tile_offsets[tile];
-    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
-        const uint32_t word = r * 4 + wave;
-        const uint64_t mask = word_mask[word];
-        const uint64_t i = tile * TBK_DBT_TILE + (uint64_t)word * 64 + lane;
-        if (((mask >> lane) & 1ull) && i < n_a) {
-            const uint64_t at = base + word_before[word] + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-            if (at < n_out) out[at] = key_of_rank(a_keys[i], k);
-        }
-    }
+tbk_kmerdb_scatter_kernel(uint64_t n_a, const uint64_t *__restrict__ flags, const unsigned long long *__restrict__ tile_offsets, uint64_t n_out,
+                          Write write) {
+    compact_scatter_tile(n_a, flags, tile_offsets, [=](uint64_t i, uint64_t at) {
+        if (at < n_out) write(i, at);
+    });
 }
+
+struct ScatterKey {
+    const uint64_t *__restrict__ a_keys;
+    int k;
+    uint64_t *__restrict__ out;
+    __device__ void operator()(uint64_t i, uint64_t at) const { out[at] = key_of_rank(a_keys[i], k); }
+};
+struct ScatterRank {
+    const uint64_t *__restrict__ a_keys;
+    uint64_t *__restrict__ out;
+    __device__ void operator()(uint64_t i, uint64_t at) const { out[at] = a_keys[i]; }
+};
+struct ScatterPair {
+    const uint64_t *__restrict__ a_keys;
+    const uint8_t *__restrict__ a_counts;
+    uint64_t *__restrict__ out_keys;
+    uint8_t *__restrict__ out_counts;
+    __device__ void operator()(uint64_t i, uint64_t at) const {
+        out_keys[at] = a_keys[i];
+        out_counts[at] = a_counts[i];
+    }
+};
 
 // ---- three databases: the k-mers of A that B lacks and the child holds (tbk_kmerdb_inherited) -------------------
-// (db_lower_bound, the bisection of a database's ranks: tbk_device.h)
 // The flags and tile counts of tbk_kmerdb_flag_kernel for the three-way selection: counter of A in [ci, cx], not among
-// B's ranks, among the child's with a counter in [hi_ci, hi_cx] there.  A's ranks ascend within the tile, so every
-// entry's lower bound in B lies between those of the tile's first and last entry (i < n_a), and likewise in the child:
-// threads 0..3 find these four by bisection over the whole partner and leave them in LDS; after the one barrier an
-// entry in range bisects between its tile's two bounds only - about log2(tile * n_b / n_a) dependent loads, on lines
-// the block shares.  Equal bounds mean that nothing of the partner lies inside the tile's span: the search is then
-// no load at all, and the one comparison after it settles the entry.  B first; the child only for what B left.
+// B's ranks, among the child's with a counter in [hi_ci, hi_cx] there.  Every entry bisects between the bounds of its tile
+// in B and in the child (compact_tile_bounds; two waves find the two pairs side by side).  B first; the child only for
+// what B left.
 __global__ void __launch_bounds__(256)
 tbk_kmerdb_inherited_flag_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restrict__ a_counts, uint64_t n_a,
                                  const uint64_t *__restrict__ b_keys, uint64_t n_b, const uint64_t *__restrict__ h_keys,
                                  const uint8_t *__restrict__ h_counts, uint64_t n_h, uint32_t ci, uint32_t cx, uint32_t h_ci, uint32_t h_cx,
                                  uint64_t *__restrict__ flags, unsigned long long *__restrict__ tile_counts) {
     __shared__ uint64_t bound[4];  // B: first, last; child: first, last
-    __shared__ uint32_t tile_sum;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t tile = blockIdx.x;
-    const uint64_t first = tile * TBK_DBT_TILE;  // (< n_a: one block per tile of A)
-    if (threadIdx.x < 4) {
 #ifdef TBK_INHERITED_FULL_DEPTH  // (measurement only, tools/build_variant.sh: every entry bisects the whole partner)
-        bound[threadIdx.x] = (threadIdx.x & 1u) ? ((threadIdx.x & 2u) ? n_h : n_b) : 0;
+    if (threadIdx.x < 4) bound[threadIdx.x] = (threadIdx.x & 1u) ? ((threadIdx.x & 2u) ? n_h : n_b) : 0;
 #else
-        const uint64_t last = (n_a - first < TBK_DBT_TILE ? n_a : first + TBK_DBT_TILE) - 1;
-        const uint64_t key = a_keys[(threadIdx.x & 1u) ? last : first];
-        bound[threadIdx.x] = (threadIdx.x & 2u) ? db_lower_bound(h_keys, 0, n_h, key) : db_lower_bound(b_keys, 0, n_b, key);
+    const uint64_t first = (uint64_t)blockIdx.x * TBK_DBT_TILE;  // (< n_a: one block per tile of A)
+    compact_tile_bounds(a_keys, n_a, first, b_keys, n_b, bound, 0);
+    compact_tile_bounds(a_keys, n_a, first, h_keys, n_h, bound + 2, 64);
 #endif
-    }
-    if (threadIdx.x == 0) tile_sum = 0;
-    __syncthreads();
-    const uint64_t b_lo = bound[0], b_hi = bound[1], h_lo = bound[2], h_hi = bound[3];
-    uint32_t mine = 0;  // (the same in every lane of a wave)
-    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
-        const uint32_t word = r * 4 + wave;
-        const uint64_t i = first + (uint64_t)word * 64 + lane;
-        bool emit = false;
-        if (i < n_a) {
-            const uint64_t key = a_keys[i];
-            const uint32_t c = a_counts[i];
-            emit = c >= 2u && c >= ci && c <= cx;
-            if (emit) {
-                const uint64_t at = db_lower_bound(b_keys, b_lo, b_hi, key);  // (at <= b_hi <= n_b)
-                emit = !(at < n_b && b_keys[at] == key);
-            }
-            if (emit) {
-                const uint64_t at = db_lower_bound(h_keys, h_lo, h_hi, key);
-                emit = at < n_h && h_keys[at] == key;
-                if (emit) {
-                    const uint32_t hc = h_counts[at];
-                    emit = hc >= 2u && hc >= h_ci && hc <= h_cx;
-                }
-            }
-        }
-        const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
-        if (lane == 0) flags[tile * TBK_DBT_WORDS + word] = mask;
-        mine += (uint32_t)__popcll(mask);
-    }
-    if (lane == 0 && mine) atomicAdd(&tile_sum, mine);
-    __syncthreads();
-    if (threadIdx.x == 0) tile_counts[tile] = tile_sum;
-}
-
-// tbk_kmerdb_scatter_kernel for a list that goes to a file: the flagged ranks as they are (write_list takes ranks).
-__global__ void __launch_bounds__(256)
-tbk_kmerdb_scatter_ranks_kernel(const uint64_t *__restrict__ a_keys, uint64_t n_a, const uint64_t *__restrict__ flags,
-                                const unsigned long long *__restrict__ tile_offsets, uint64_t *__restrict__ out, uint64_t n_out) {
-    __shared__ uint64_t word_mask[TBK_DBT_WORDS];
-    __shared__ uint32_t word_before[TBK_DBT_WORDS];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t tile = blockIdx.x;
-    if (threadIdx.x < TBK_DBT_WORDS) word_mask[threadIdx.x] = flags[tile * TBK_DBT_WORDS + threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-        for (uint32_t w = 0; w < TBK_DBT_WORDS; w++) {
-            word_before[w] = sum;
-            sum += (uint32_t)__popcll(word_mask[w]);
-        }
-    }
-    __syncthreads();
-    const uint64_t base = tile_offsets[tile];
-    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
-        const uint32_t word = r * 4 + wave;
-        const uint64_t mask = word_mask[word];
-        const uint64_t i = tile * TBK_DBT_TILE + (uint64_t)word * 64 + lane;
-        if (((mask >> lane) & 1ull) && i < n_a) {
-            const uint64_t at = base + word_before[word] + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-            if (at < n_out) out[at] = a_keys[i];
-        }
-    }
+    compact_flag_tile(n_a, flags, tile_counts, [=](uint64_t i) {
+        const uint64_t key = a_keys[i];
+        if (!db_counter_selected(a_counts[i], ci, cx) || !db_absent(b_keys, bound[0], bound[1], n_b, key)) return false;
+        const uint64_t at = db_lower_bound(h_keys, bound[2], bound[3], key);
+        return at < n_h && h_keys[at] == key && db_counter_selected(h_counts[at], h_ci, h_cx);
+    });
 }
 
 // ---- a class database without its once-seen k-mers: B's side of tbk_counter_unique for a counter that keeps them --------
@@ -761,48 +643,12 @@ tbk_db_solid_keys_kernel(const uint64_t *__restrict__ keys, const uint8_t *__res
     }
 }
 
-// ---- tbk_kmerdb_solid: a full database without its once-seen k-mers ------------------------------------------------------
-// The flags are tbk_kmerdb_flag_kernel's with an empty B and the range 2..255; this is tbk_kmerdb_scatter_ranks_kernel
-// taking the counter along.
-__global__ void __launch_bounds__(256)
-tbk_kmerdb_scatter_pairs_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restrict__ a_counts, uint64_t n_a,
-                                const uint64_t *__restrict__ flags, const unsigned long long *__restrict__ tile_offsets,
-                                uint64_t *__restrict__ out_keys, uint8_t *__restrict__ out_counts, uint64_t n_out) {
-    __shared__ uint64_t word_mask[TBK_DBT_WORDS];
-    __shared__ uint32_t word_before[TBK_DBT_WORDS];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t tile = blockIdx.x;
-    if (threadIdx.x < TBK_DBT_WORDS) word_mask[threadIdx.x] = flags[tile * TBK_DBT_WORDS + threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-        for (uint32_t w = 0; w < TBK_DBT_WORDS; w++) {
-            word_before[w] = sum;
-            sum += (uint32_t)__popcll(word_mask[w]);
-        }
-    }
-    __syncthreads();
-    const uint64_t base = tile_offsets[tile];
-    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
-        const uint32_t word = r * 4 + wave;
-        const uint64_t mask = word_mask[word];
-        const uint64_t i = tile * TBK_DBT_TILE + (uint64_t)word * 64 + lane;
-        if (((mask >> lane) & 1ull) && i < n_a) {
-            const uint64_t at = base + word_before[word] + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-            if (at < n_out) {
-                out_keys[at] = a_keys[i];
-                out_counts[at] = a_counts[i];
-            }
-        }
-    }
-}
-
 // ---- tbk_kmerdb_union: two full databases to the database of both read sets -----------------------------------------------
 // The RANK-BASED shape.  Both inputs ascend and hold no key twice, so the place of an entry in the union is its own
 // index plus its lower bound in the other database, less the keys both hold (the duplicates) that stand before it; no
 // sort, no concatenation.  Three steps, separate launches, no block waiting for another:
 //   1. flag: one block per tile of TBK_DBT_TILE entries of A.  Every entry finds its lower bound in B, between the
-//      bounds of its tile's first and last entry as in tbk_kmerdb_inherited_flag_kernel; a duplicate is an entry whose
+//      bounds of its tile's first and last entry (compact_tile_bounds); a duplicate is an entry whose
 //      key B holds at that place - B's key is read from memory wherever it lies, whatever tile of B that is.  One bit
 //      per entry of A and a count per tile of A;
 //   2. the exclusive scan of the tile counts (tbk_launch_kmerdb_scan);
@@ -820,71 +666,33 @@ __global__ void __launch_bounds__(256)
 tbk_kmerdb_union_flag_kernel(const uint64_t *__restrict__ a_keys, uint64_t n_a, const uint64_t *__restrict__ b_keys, uint64_t n_b,
                              uint64_t *__restrict__ flags, unsigned long long *__restrict__ tile_counts) {
     __shared__ uint64_t bound[2];
-    __shared__ uint32_t tile_sum;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t tile = blockIdx.x;
-    const uint64_t first = tile * TBK_DBT_TILE;  // (< n_a: one block per tile of A)
-    if (threadIdx.x < 2) {
-        const uint64_t last = (n_a - first < TBK_DBT_TILE ? n_a : first + TBK_DBT_TILE) - 1;
-        bound[threadIdx.x] = db_lower_bound(b_keys, 0, n_b, a_keys[threadIdx.x ? last : first]);
-    }
-    if (threadIdx.x == 0) tile_sum = 0;
-    __syncthreads();
-    const uint64_t b_lo = bound[0], b_hi = bound[1];
-    uint32_t mine = 0;  // (the same in every lane of a wave)
-    for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
-        const uint32_t word = r * 4 + wave;
-        const uint64_t i = first + (uint64_t)word * 64 + lane;
-        bool dup = false;
-        if (i < n_a) {
-            const uint64_t key = a_keys[i];
-            const uint64_t at = db_lower_bound(b_keys, b_lo, b_hi, key);  // (at <= b_hi <= n_b)
-            dup = at < n_b && b_keys[at] == key;
-        }
-        const uint64_t mask = __builtin_amdgcn_ballot_w64(dup);
-        if (lane == 0) flags[tile * TBK_DBT_WORDS + word] = mask;
-        mine += (uint32_t)__popcll(mask);
-    }
-    if (lane == 0 && mine) atomicAdd(&tile_sum, mine);
-    __syncthreads();
-    if (threadIdx.x == 0) tile_counts[tile] = tile_sum;
+    compact_tile_bounds(a_keys, n_a, (uint64_t)blockIdx.x * TBK_DBT_TILE, b_keys, n_b, bound, 0);
+    compact_flag_tile(n_a, flags, tile_counts, [=](uint64_t i) { return !db_absent(b_keys, bound[0], bound[1], n_b, a_keys[i]); });
 }
 
+// Every entry of A, flagged or not: the prologue of compact_scatter_tile and a loop of its own.
 __global__ void __launch_bounds__(256)
 tbk_kmerdb_union_scatter_a_kernel(const uint64_t *__restrict__ a_keys, const uint8_t *__restrict__ a_counts, uint64_t n_a,
                                   const uint64_t *__restrict__ b_keys, const uint8_t *__restrict__ b_counts, uint64_t n_b,
                                   const uint64_t *__restrict__ flags, const unsigned long long *__restrict__ tile_offsets,
                                   uint64_t *__restrict__ out_keys, uint8_t *__restrict__ out_counts, uint64_t n_out) {
     __shared__ uint64_t bound[2];
-    __shared__ uint64_t word_mask[TBK_DBT_WORDS];
-    __shared__ uint32_t word_before[TBK_DBT_WORDS];
+    __shared__ CompactWords w;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t tile = blockIdx.x;
     const uint64_t first = tile * TBK_DBT_TILE;
-    if (threadIdx.x < 2) {
-        const uint64_t last = (n_a - first < TBK_DBT_TILE ? n_a : first + TBK_DBT_TILE) - 1;
-        bound[threadIdx.x] = db_lower_bound(b_keys, 0, n_b, a_keys[threadIdx.x ? last : first]);
-    }
-    if (threadIdx.x >= 64 && threadIdx.x < 64 + TBK_DBT_WORDS) word_mask[threadIdx.x - 64] = flags[tile * TBK_DBT_WORDS + threadIdx.x - 64];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-        for (uint32_t w = 0; w < TBK_DBT_WORDS; w++) {
-            word_before[w] = sum;
-            sum += (uint32_t)__popcll(word_mask[w]);
-        }
-    }
-    __syncthreads();
+    compact_tile_bounds(a_keys, n_a, first, b_keys, n_b, bound, 0);
+    compact_load_words(w, flags, 64);  // (another wave than the bisections')
     const uint64_t b_lo = bound[0], b_hi = bound[1];
     const uint64_t dups_before_tile = tile_offsets[tile];
     for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
         const uint32_t word = r * 4 + wave;
-        const uint64_t mask = word_mask[word];
+        const uint64_t mask = w.mask[word];
         const uint64_t i = first + (uint64_t)word * 64 + lane;
         if (i < n_a) {
             const uint64_t key = a_keys[i];
             const uint64_t rank = db_lower_bound(b_keys, b_lo, b_hi, key);
-            const uint64_t dups = dups_before_tile + word_before[word] + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+            const uint64_t dups = dups_before_tile + w.before[word] + compact_below(mask, lane);
             uint32_t c = a_counts[i];
             if (((mask >> lane) & 1ull) && rank < n_b) c += b_counts[rank];  // (32-bit sum of two bytes)
             const uint64_t at = i + rank - dups;
@@ -904,10 +712,7 @@ tbk_kmerdb_union_scatter_b_kernel(const uint64_t *__restrict__ b_keys, const uin
                                   uint8_t *__restrict__ out_counts, uint64_t n_out) {
     __shared__ uint64_t bound[2];
     const uint64_t first = (uint64_t)blockIdx.x * TBK_DBT_TILE;  // (< n_b)
-    if (threadIdx.x < 2) {
-        const uint64_t last = (n_b - first < TBK_DBT_TILE ? n_b : first + TBK_DBT_TILE) - 1;
-        bound[threadIdx.x] = db_lower_bound(a_keys, 0, n_a, b_keys[threadIdx.x ? last : first]);
-    }
+    compact_tile_bounds(b_keys, n_b, first, a_keys, n_a, bound, 0);
     __syncthreads();
     const uint64_t a_lo = bound[0], a_hi = bound[1];
     for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
@@ -1083,19 +888,10 @@ extern "C" hipError_t tbk_launch_kmerdb_unique(const uint64_t *a_keys, const uin
     return hipGetLastError();
 }
 
-// ---- tbk_kmerdb_unique_table: flag, scan, scatter ----------------------------------------------------------------
-extern "C" uint64_t tbk_kmerdb_table_tiles(uint64_t n_a) { return (n_a + TBK_DBT_TILE - 1) / TBK_DBT_TILE; }
-extern "C" uint64_t tbk_kmerdb_table_flag_words(uint64_t n_a) { return tbk_kmerdb_table_tiles(n_a) * TBK_DBT_WORDS; }
-
-// d_flags: tbk_kmerdb_table_flag_words(n_a) words; d_tile_counts: one per tile.  One block per tile: no grid stride.
+// ---- tbk_kmerdb_unique_table: flag, scan, scatter (the buffers: tbk_compact_host.h) ----------------------------------
 extern "C" hipError_t tbk_launch_kmerdb_flag(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *b_keys, uint64_t n_b,
                                              uint32_t ci, uint32_t cx, uint64_t *d_flags, unsigned long long *d_tile_counts, hipStream_t stream) {
-    const uint64_t tiles = tbk_kmerdb_table_tiles(n_a);
-    if (!tiles) return hipSuccess;
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tbk_kmerdb_flag_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, a_counts, n_a, b_keys, n_b, ci, cx, d_flags,
-                       d_tile_counts);
-    return hipGetLastError();
+    return compact_launch_tiles(n_a, stream, tbk_kmerdb_flag_kernel, a_keys, a_counts, n_a, b_keys, n_b, ci, cx, d_flags, d_tile_counts);
 }
 
 // d_out[i] = d_in[0] + ... + d_in[i - 1], n elements; the caller passes one element more than it has tiles, so the last is the total
@@ -1113,36 +909,31 @@ extern "C" hipError_t tbk_launch_kmerdb_scan(const unsigned long long *d_in, uns
     return e != hipSuccess ? e : e2;
 }
 
+template <typename Write>
+static hipError_t launch_scatter(uint64_t n_a, const uint64_t *d_flags, const unsigned long long *d_tile_offsets, uint64_t n_out, hipStream_t stream,
+                                 Write write) {
+    if (!n_out) return hipSuccess;
+    return compact_launch_tiles(n_a, stream, tbk_kmerdb_scatter_kernel<Write>, n_a, d_flags, d_tile_offsets, n_out, write);
+}
+
 extern "C" hipError_t tbk_launch_kmerdb_scatter(const uint64_t *a_keys, uint64_t n_a, const uint64_t *d_flags, const unsigned long long *d_tile_offsets,
                                                 int k, uint64_t *d_out, uint64_t n_out, hipStream_t stream) {
-    const uint64_t tiles = tbk_kmerdb_table_tiles(n_a);
-    if (!tiles || !n_out) return hipSuccess;
-    if (tiles > 0x7FFFFFFFull || k < 1 || k > 32) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tbk_kmerdb_scatter_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, n_a, d_flags, d_tile_offsets, k, d_out, n_out);
-    return hipGetLastError();
+    if (n_a && n_out && (k < 1 || k > 32)) return hipErrorInvalidValue;
+    return launch_scatter(n_a, d_flags, d_tile_offsets, n_out, stream, ScatterKey{a_keys, k, d_out});
 }
 
 // ---- tbk_kmerdb_inherited: its own flag kernel, then the scan above and one of the two scatters ------------------
-// d_flags and d_tile_counts as for tbk_launch_kmerdb_flag; the child's arrays may be NULL when n_h is 0 (as B's when n_b is)
 extern "C" hipError_t tbk_launch_kmerdb_inherited_flag(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *b_keys,
                                                        uint64_t n_b, const uint64_t *h_keys, const uint8_t *h_counts, uint64_t n_h, uint32_t ci,
                                                        uint32_t cx, uint32_t h_ci, uint32_t h_cx, uint64_t *d_flags,
                                                        unsigned long long *d_tile_counts, hipStream_t stream) {
-    const uint64_t tiles = tbk_kmerdb_table_tiles(n_a);
-    if (!tiles) return hipSuccess;
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tbk_kmerdb_inherited_flag_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, a_counts, n_a, b_keys, n_b, h_keys,
-                       h_counts, n_h, ci, cx, h_ci, h_cx, d_flags, d_tile_counts);
-    return hipGetLastError();
+    return compact_launch_tiles(n_a, stream, tbk_kmerdb_inherited_flag_kernel, a_keys, a_counts, n_a, b_keys, n_b, h_keys, h_counts, n_h, ci, cx, h_ci, h_cx,
+                        d_flags, d_tile_counts);
 }
 
 extern "C" hipError_t tbk_launch_kmerdb_scatter_ranks(const uint64_t *a_keys, uint64_t n_a, const uint64_t *d_flags,
                                                       const unsigned long long *d_tile_offsets, uint64_t *d_out, uint64_t n_out, hipStream_t stream) {
-    const uint64_t tiles = tbk_kmerdb_table_tiles(n_a);
-    if (!tiles || !n_out) return hipSuccess;
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tbk_kmerdb_scatter_ranks_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, n_a, d_flags, d_tile_offsets, d_out, n_out);
-    return hipGetLastError();
+    return launch_scatter(n_a, d_flags, d_tile_offsets, n_out, stream, ScatterRank{a_keys, d_out});
 }
 
 // ---- keep_singletons: B's class keys without the once-seen ones ------------------------------------------------------
@@ -1158,42 +949,26 @@ extern "C" hipError_t tbk_launch_db_solid_keys(const uint64_t *d_keys, const uin
 extern "C" hipError_t tbk_launch_kmerdb_scatter_pairs(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *d_flags,
                                                       const unsigned long long *d_tile_offsets, uint64_t *d_out_keys, uint8_t *d_out_counts,
                                                       uint64_t n_out, hipStream_t stream) {
-    const uint64_t tiles = tbk_kmerdb_table_tiles(n_a);
-    if (!tiles || !n_out) return hipSuccess;
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tbk_kmerdb_scatter_pairs_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, a_counts, n_a, d_flags, d_tile_offsets,
-                       d_out_keys, d_out_counts, n_out);
-    return hipGetLastError();
+    return launch_scatter(n_a, d_flags, d_tile_offsets, n_out, stream, ScatterPair{a_keys, a_counts, d_out_keys, d_out_counts});
 }
 
 // ---- tbk_kmerdb_union: flag A against B, the scan above, scatter A, scatter B, tally --------------------------------------
-// d_flags: tbk_kmerdb_table_flag_words(n_a) words; d_tile_counts: one per tile of A
 extern "C" hipError_t tbk_launch_kmerdb_union_flag(const uint64_t *a_keys, uint64_t n_a, const uint64_t *b_keys, uint64_t n_b, uint64_t *d_flags,
                                                    unsigned long long *d_tile_counts, hipStream_t stream) {
-    const uint64_t tiles = tbk_kmerdb_table_tiles(n_a);
-    if (!tiles) return hipSuccess;
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tbk_kmerdb_union_flag_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, a_keys, n_a, b_keys, n_b, d_flags, d_tile_counts);
-    return hipGetLastError();
+    return compact_launch_tiles(n_a, stream, tbk_kmerdb_union_flag_kernel, a_keys, n_a, b_keys, n_b, d_flags, d_tile_counts);
 }
 
-// d_tile_offsets: tiles of A + 1 (the last one the number of duplicates); the output holds n_out = n_a + n_b - duplicates
 extern "C" hipError_t tbk_launch_kmerdb_union_scatter(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *b_keys,
                                                       const uint8_t *b_counts, uint64_t n_b, const uint64_t *d_flags,
                                                       const unsigned long long *d_tile_offsets, uint64_t *d_out_keys, uint8_t *d_out_counts,
                                                       uint64_t n_out, hipStream_t stream) {
-    const uint64_t tiles_a = tbk_kmerdb_table_tiles(n_a), tiles_b = tbk_kmerdb_table_tiles(n_b);
     if (!n_out) return hipSuccess;
-    if (tiles_a > 0x7FFFFFFFull || tiles_b > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (tiles_a)
-        hipLaunchKernelGGL(tbk_kmerdb_union_scatter_a_kernel, dim3((unsigned)tiles_a), dim3(256), 0, stream, a_keys, a_counts, n_a, b_keys, b_counts, n_b,
-                           d_flags, d_tile_offsets, d_out_keys, d_out_counts, n_out);
-    hipError_t e = hipGetLastError();
+    if (tbk_kmerdb_table_tiles(n_a) > 0x7FFFFFFFull || tbk_kmerdb_table_tiles(n_b) > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const hipError_t e = compact_launch_tiles(n_a, stream, tbk_kmerdb_union_scatter_a_kernel, a_keys, a_counts, n_a, b_keys, b_counts, n_b, d_flags,
+                                      d_tile_offsets, d_out_keys, d_out_counts, n_out);
     if (e != hipSuccess) return e;
-    if (tiles_b)
-        hipLaunchKernelGGL(tbk_kmerdb_union_scatter_b_kernel, dim3((unsigned)tiles_b), dim3(256), 0, stream, b_keys, b_counts, n_b, a_keys, n_a, d_flags,
-                           d_tile_offsets, d_out_keys, d_out_counts, n_out);
-    return hipGetLastError();
+    return compact_launch_tiles(n_b, stream, tbk_kmerdb_union_scatter_b_kernel, b_keys, b_counts, n_b, a_keys, n_a, d_flags, d_tile_offsets, d_out_keys,
+                        d_out_counts, n_out);
 }
 
 // d_hist: 256 words, zeroed by the caller

@@ -67,6 +67,12 @@ __device__ __forceinline__ uint64_t lex_rank(uint64_t key, int k) {
     return lex >> (64 - 2 * k);
 }
 
+// the key in the classifier's form (base i at bits 2i..2i+1, tbk_kmer_to_int) of a lexicographic rank: lex_rank's inverse
+__device__ __forceinline__ uint64_t key_of_rank(uint64_t rank, int k) {
+    const uint64_t lex = rank << (64 - 2 * k);  // (k = 32: a shift by 0)
+    return ((uint64_t)rev_pairs((uint32_t)lex) << 32) | (uint64_t)rev_pairs((uint32_t)(lex >> 32));
+}
+
 // first element >= key among keys[lo .. hi), which ascend: hi when there is none
 __device__ __forceinline__ uint64_t db_lower_bound(const uint64_t *__restrict__ keys, uint64_t lo, uint64_t hi, uint64_t key) {
     while (lo < hi) {

@@ -13,12 +13,14 @@
 // A line that breaks the rule (include/tbk.h has it) writes nothing and lowers one 64-bit word to (its global line index
 // << 8 | reason) with a vector atomicMin: the smallest index wins, whichever window or tile it lies in.
 // After the last window the pairs are checked by tbk_kmerdb_check_kernel; only when they do not ascend strictly are they
-// sorted (tbk_launch_sort_u64_u8) and folded here: tbk_dump_heads_kernel flags the first entry of every run of equal keys
-// in the layout of tbk_kmerdb_flag_kernel (bit j of word i is entry 64 i + j, a count per tile of 1024), the scan gives
+// sorted (tbk_launch_sort_u64_u8) and folded here: tbk_dump_flag_kernel<0> flags the first entry of every run of equal keys
+// in the layout of tbk_compact.h (bit j of word i is entry 64 i + j, a count per tile of TBK_DBT_TILE), the scan gives
 // every tile its place and tbk_dump_fold_kernel writes each head with the saturating sum of its run.
 // No block waits for another; the only atomics are the bad-line minimum and block-local counts in LDS.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "tbk_compact.h"
 
 constexpr uint32_t TBK_DUMP_TILE = 4096;                  // bytes per tile: 256 lanes x 16
 constexpr uint32_t TBK_DUMP_WORDS = TBK_DUMP_TILE / 64;   // newline words per tile
@@ -159,80 +161,34 @@ tbk_dump_parse_kernel(const uint8_t *__restrict__ text, uint64_t len, const uint
     }
 }
 
-// ---- flags over entries, in the layout tbk_launch_kmerdb_scan and tbk_kmerdb_scatter_pairs_kernel take ---------------------
-constexpr uint32_t TBK_DUMP_ENTRY_TILE = 1024;  // (= TBK_DBT_TILE of tbk_count_kernels.hip: 4 rounds of a 256-thread block)
-constexpr uint32_t TBK_DUMP_ENTRY_WORDS = TBK_DUMP_ENTRY_TILE / 64;
-
+// ---- flags over entries: the tile compaction of tbk_compact.h ---------------------------------------------------------------
 // MODE 0: entry i is the head of a run of equal keys.  MODE 1: its counter lies in [lo, hi].
 template <int MODE>
 __global__ void __launch_bounds__(256)
 tbk_dump_flag_kernel(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ counts, uint64_t n, uint32_t lo, uint32_t hi,
                      uint64_t *__restrict__ flags, unsigned long long *__restrict__ tile_counts) {
-    __shared__ uint32_t wave_count[TBK_DUMP_ENTRY_WORDS];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t tile = blockIdx.x;
-    for (uint32_t r = 0; r < TBK_DUMP_ENTRY_TILE / 256; r++) {
-        const uint32_t w = r * 4 + wave;
-        const uint64_t i = tile * TBK_DUMP_ENTRY_TILE + (uint64_t)w * 64 + lane;
-        bool emit = false;
-        if (i < n) {
-            if (MODE == 0) {
-                emit = i == 0 || keys[i] != keys[i - 1];
-            } else {
-                const uint32_t c = counts[i];
-                emit = c >= lo && c <= hi;
-            }
-        }
-        const uint64_t mask = __builtin_amdgcn_ballot_w64(emit);
-        if (lane == 0) {
-            flags[tile * TBK_DUMP_ENTRY_WORDS + w] = mask;
-            wave_count[w] = (uint32_t)__popcll(mask);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-        for (uint32_t w = 0; w < TBK_DUMP_ENTRY_WORDS; w++) sum += wave_count[w];
-        tile_counts[tile] = sum;
-    }
+    compact_flag_tile(n, flags, tile_counts, [=](uint64_t i) {
+        if (MODE == 0) return i == 0 || keys[i] != keys[i - 1];
+        const uint32_t c = counts[i];
+        return c >= lo && c <= hi;
+    });
 }
 
-// Every head to tile_offsets[its tile] + the heads before it in the tile, with min(255, sum of its run's counters): the head's
-// lane walks forward and stops at 255, and every counter is at least 1, so a run costs at most 255 steps however long it is.
+// Every head to its place with min(255, sum of its run's counters): the head's lane walks forward and stops at 255, and
+// every counter is at least 1, so a run costs at most 255 steps however long it is.
 __global__ void __launch_bounds__(256)
 tbk_dump_fold_kernel(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ counts, uint64_t n, const uint64_t *__restrict__ flags,
                      const unsigned long long *__restrict__ tile_offsets, uint64_t *__restrict__ out_keys, uint8_t *__restrict__ out_counts,
                      uint64_t n_out) {
-    __shared__ uint64_t word_mask[TBK_DUMP_ENTRY_WORDS];
-    __shared__ uint32_t word_before[TBK_DUMP_ENTRY_WORDS];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t tile = blockIdx.x;
-    if (threadIdx.x < TBK_DUMP_ENTRY_WORDS) word_mask[threadIdx.x] = flags[tile * TBK_DUMP_ENTRY_WORDS + threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-        for (uint32_t w = 0; w < TBK_DUMP_ENTRY_WORDS; w++) {
-            word_before[w] = sum;
-            sum += (uint32_t)__popcll(word_mask[w]);
+    compact_scatter_tile(n, flags, tile_offsets, [=](uint64_t i, uint64_t at) {
+        const uint64_t key = keys[i];
+        uint32_t sum = counts[i];
+        for (uint64_t j = i + 1; sum < 255u && j < n && keys[j] == key; j++) sum += counts[j];
+        if (at < n_out) {
+            out_keys[at] = key;
+            out_counts[at] = (uint8_t)(sum > 255u ? 255u : sum);
         }
-    }
-    __syncthreads();
-    const uint64_t base = tile_offsets[tile];
-    for (uint32_t r = 0; r < TBK_DUMP_ENTRY_TILE / 256; r++) {
-        const uint32_t w = r * 4 + wave;
-        const uint64_t mask = word_mask[w];
-        const uint64_t i = tile * TBK_DUMP_ENTRY_TILE + (uint64_t)w * 64 + lane;
-        if (((mask >> lane) & 1ull) && i < n) {
-            const uint64_t at = base + word_before[w] + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-            const uint64_t key = keys[i];
-            uint32_t sum = counts[i];
-            for (uint64_t j = i + 1; sum < 255u && j < n && keys[j] == key; j++) sum += counts[j];
-            if (at < n_out) {
-                out_keys[at] = key;
-                out_counts[at] = (uint8_t)(sum > 255u ? 255u : sum);
-            }
-        }
-    }
+    });
 }
 
 // =======================================================================================
@@ -260,32 +216,18 @@ extern "C" hipError_t tbk_launch_dump_parse(const uint8_t *d_text, uint64_t len,
     return hipGetLastError();
 }
 
-static inline uint64_t dump_entry_tiles(uint64_t n) { return (n + TBK_DUMP_ENTRY_TILE - 1) / TBK_DUMP_ENTRY_TILE; }
-
-// d_flags: tbk_kmerdb_table_flag_words(n) words; d_tile_counts: one per tile of 1024 entries
 extern "C" hipError_t tbk_launch_dump_heads(const uint64_t *d_keys, uint64_t n, uint64_t *d_flags, unsigned long long *d_tile_counts, hipStream_t stream) {
-    const uint64_t tiles = dump_entry_tiles(n);
-    if (!tiles) return hipSuccess;
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tbk_dump_flag_kernel<0>, dim3((unsigned)tiles), dim3(256), 0, stream, d_keys, (const uint8_t *)nullptr, n, 0u, 0u, d_flags, d_tile_counts);
-    return hipGetLastError();
+    return compact_launch_tiles(n, stream, tbk_dump_flag_kernel<0>, d_keys, (const uint8_t *)nullptr, n, 0u, 0u, d_flags, d_tile_counts);
 }
 
 extern "C" hipError_t tbk_launch_dump_select(const uint8_t *d_counts, uint64_t n, uint32_t lo, uint32_t hi, uint64_t *d_flags,
                                              unsigned long long *d_tile_counts, hipStream_t stream) {
-    const uint64_t tiles = dump_entry_tiles(n);
-    if (!tiles) return hipSuccess;
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tbk_dump_flag_kernel<1>, dim3((unsigned)tiles), dim3(256), 0, stream, (const uint64_t *)nullptr, d_counts, n, lo, hi, d_flags, d_tile_counts);
-    return hipGetLastError();
+    return compact_launch_tiles(n, stream, tbk_dump_flag_kernel<1>, (const uint64_t *)nullptr, d_counts, n, lo, hi, d_flags, d_tile_counts);
 }
 
 extern "C" hipError_t tbk_launch_dump_fold(const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, const uint64_t *d_flags,
                                            const unsigned long long *d_tile_offsets, uint64_t *d_out_keys, uint8_t *d_out_counts, uint64_t n_out,
                                            hipStream_t stream) {
-    const uint64_t tiles = dump_entry_tiles(n);
-    if (!tiles || !n_out) return hipSuccess;
-    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tbk_dump_fold_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, d_keys, d_counts, n, d_flags, d_tile_offsets, d_out_keys, d_out_counts, n_out);
-    return hipGetLastError();
+    if (!n_out) return hipSuccess;
+    return compact_launch_tiles(n, stream, tbk_dump_fold_kernel, d_keys, d_counts, n, d_flags, d_tile_offsets, d_out_keys, d_out_counts, n_out);
 }

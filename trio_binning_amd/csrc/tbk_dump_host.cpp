@@ -25,6 +25,7 @@
 
 #include "../../include/tbk.h"
 #include "tbk_common.h"
+#include "tbk_compact_host.h"
 #include "tbk_dump_text.h"
 
 extern "C" void tbk_set_error_(int code, const char *msg);
@@ -34,19 +35,6 @@ extern "C" uint32_t tbk_dump_tile(void);
 extern "C" hipError_t tbk_launch_dump_lines(const uint8_t *, uint64_t, uint64_t *, unsigned long long *, hipStream_t);
 extern "C" hipError_t tbk_launch_dump_parse(const uint8_t *, uint64_t, const uint64_t *, const unsigned long long *, int, int, uint64_t, uint64_t, uint64_t *,
                                             uint8_t *, unsigned long long *, hipStream_t);
-extern "C" hipError_t tbk_launch_dump_heads(const uint64_t *, uint64_t, uint64_t *, unsigned long long *, hipStream_t);
-extern "C" hipError_t tbk_launch_dump_select(const uint8_t *, uint64_t, uint32_t, uint32_t, uint64_t *, unsigned long long *, hipStream_t);
-extern "C" hipError_t tbk_launch_dump_fold(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, const unsigned long long *, uint64_t *, uint8_t *,
-                                           uint64_t, hipStream_t);
-extern "C" uint64_t tbk_kmerdb_table_tiles(uint64_t);
-extern "C" uint64_t tbk_kmerdb_table_flag_words(uint64_t);
-extern "C" hipError_t tbk_launch_kmerdb_check(const uint64_t *, const uint8_t *, uint64_t, int, uint32_t, unsigned long long *, hipStream_t);
-extern "C" hipError_t tbk_launch_kmerdb_flag(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, uint64_t, uint32_t, uint32_t, uint64_t *,
-                                             unsigned long long *, hipStream_t);
-extern "C" hipError_t tbk_launch_kmerdb_scan(const unsigned long long *, unsigned long long *, uint64_t, hipStream_t);
-extern "C" hipError_t tbk_launch_kmerdb_scatter_pairs(const uint64_t *, const uint8_t *, uint64_t, const uint64_t *, const unsigned long long *, uint64_t *,
-                                                      uint8_t *, uint64_t, hipStream_t);
-extern "C" hipError_t tbk_launch_kmerdb_tally(const uint8_t *, uint64_t, unsigned long long *, hipStream_t);
 extern "C" hipError_t tbk_launch_sort_u64_u8(const uint64_t *, uint64_t *, const uint8_t *, uint8_t *, uint64_t, int, hipStream_t);
 extern "C" int tbk_kmerdb_make_(uint64_t *, uint8_t *, uint64_t, int, int, int, int, const uint64_t *, uint64_t, uint64_t, tbk_kmerdb **);
 extern "C" int tbk_kmerdb_arrays_(const tbk_kmerdb *, const uint64_t **, const uint8_t **);
@@ -137,6 +125,13 @@ struct Import {
         dev_bytes += bytes;
         return hipSuccess;
     }
+    hipError_t reserve(Compaction &c, uint64_t n) {  // (c frees its own two buffers; their bytes count all the same)
+        const uint64_t limit = g_alloc_limit.load();
+        if (limit && dev_bytes + Compaction::bytes(n) > limit) return hipErrorOutOfMemory;
+        const hipError_t e = c.reserve(n, stream);
+        if (e == hipSuccess) dev_bytes += Compaction::bytes(n);
+        return e;
+    }
     void release(void *p) {  // free now
         if (!p) return;
         disown(p);
@@ -225,34 +220,6 @@ extern "C" int tbk_dump_file_k(const char *path, int *k) {
     if (first < 1 || first > 32) return dfail(TBK_ERR_FORMAT, "%s: line 1: a k-mer of %lld bases (k must lie in 1..32)", path, (long long)first);
     *k = (int)first;
     return TBK_OK;
-}
-
-// flag / scan / total of a compaction over n entries: the flags and the scanned tile offsets stay for the scatter
-struct Compaction {
-    uint64_t *d_flags = nullptr;
-    unsigned long long *d_tiles = nullptr;  // tiles + 1 counts (the last one 0), then their tiles + 1 offsets (the last one the total)
-    uint64_t tiles = 0;
-    const unsigned long long *offsets() const { return d_tiles + tiles + 1; }
-};
-
-static hipError_t compaction_alloc(Import &im, uint64_t n, Compaction *c) {
-    c->tiles = tbk_kmerdb_table_tiles(n);
-    hipError_t e = im.alloc((void **)&c->d_flags, (size_t)tbk_kmerdb_table_flag_words(n) * sizeof(uint64_t));
-    if (e == hipSuccess) e = im.alloc((void **)&c->d_tiles, (size_t)(2 * (c->tiles + 1)) * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_tiles + c->tiles, 0, sizeof(unsigned long long), im.stream);
-    return e;
-}
-static hipError_t compaction_total(Import &im, Compaction *c, unsigned long long *total) {
-    hipError_t e = tbk_launch_kmerdb_scan(c->d_tiles, c->d_tiles + c->tiles + 1, c->tiles + 1, im.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(total, c->d_tiles + 2 * c->tiles + 1, sizeof *total, hipMemcpyDeviceToHost, im.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(im.stream);
-    return e;
-}
-static void compaction_free(Import &im, Compaction *c) {
-    im.release(c->d_flags);
-    im.release(c->d_tiles);
-    c->d_flags = nullptr;
-    c->d_tiles = nullptr;
 }
 
 extern "C" int tbk_kmerdb_import_text(const char *const *paths, int n_paths, const tbk_dump_options *opts, int device, tbk_kmerdb **out) {
@@ -434,9 +401,9 @@ extern "C" int tbk_kmerdb_import_text(const char *const *paths, int n_paths, con
             d_counts = nullptr;
             Compaction heads;
             unsigned long long m = 0;
-            DHIP(compaction_alloc(im, n, &heads));
-            DHIP(tbk_launch_dump_heads(d_k2, n, heads.d_flags, heads.d_tiles, im.stream));
-            DHIP(compaction_total(im, &heads, &m));
+            DHIP(im.reserve(heads, n));
+            DHIP(tbk_launch_dump_heads(d_k2, n, heads.d_flags, heads.counts(), im.stream));
+            DHIP(heads.total(&m));
             if (!m || m > n) return dfail(TBK_ERR_HIP, "tbk_kmerdb_import_text: %llu distinct keys among %llu pairs", m, (unsigned long long)n);
             DHIP(im.alloc((void **)&d_keys, (size_t)m * sizeof(uint64_t)));
             DHIP(im.alloc((void **)&d_counts, (size_t)m));
@@ -444,7 +411,7 @@ extern "C" int tbk_kmerdb_import_text(const char *const *paths, int n_paths, con
             DHIP(tbk_launch_kmerdb_tally(d_counts, m, d_words + 260, im.stream));
             DHIP(hipMemcpyAsync(words, d_words, sizeof words, hipMemcpyDeviceToHost, im.stream));
             DHIP(hipStreamSynchronize(im.stream));
-            compaction_free(im, &heads);
+            heads.release();
             im.release(d_k2);
             im.release(d_c2);
             n = m;
@@ -464,9 +431,9 @@ extern "C" int tbk_kmerdb_import_text(const char *const *paths, int n_paths, con
         unsigned long long total = 0;
         uint64_t *d_k2 = nullptr;
         uint8_t *d_c2 = nullptr;
-        DHIP(compaction_alloc(im, n, &solid));
-        DHIP(tbk_launch_kmerdb_flag(d_keys, d_counts, n, nullptr, 0, 2, 255, solid.d_flags, solid.d_tiles, im.stream));
-        DHIP(compaction_total(im, &solid, &total));
+        DHIP(im.reserve(solid, n));
+        DHIP(tbk_launch_kmerdb_flag(d_keys, d_counts, n, nullptr, 0, 2, 255, solid.d_flags, solid.counts(), im.stream));
+        DHIP(solid.total(&total));
         if (total != want) return dfail(TBK_ERR_HIP, "tbk_kmerdb_import_text: %llu counters of 2 or more, the tally states %llu", total, (unsigned long long)want);
         if (want) {
             DHIP(im.alloc((void **)&d_k2, (size_t)want * sizeof(uint64_t)));
@@ -474,7 +441,7 @@ extern "C" int tbk_kmerdb_import_text(const char *const *paths, int n_paths, con
             DHIP(tbk_launch_kmerdb_scatter_pairs(d_keys, d_counts, n, solid.d_flags, solid.offsets(), d_k2, d_c2, want, im.stream));
             DHIP(hipStreamSynchronize(im.stream));
         }
-        compaction_free(im, &solid);
+        solid.release();
         im.release(d_keys);
         im.release(d_counts);
         d_keys = d_k2;
@@ -595,15 +562,15 @@ extern "C" int tbk_kmerdb_dump_text(const tbk_kmerdb *db, uint32_t min_count, ui
             unsigned long long total = 0;
             uint64_t *d_k2 = nullptr;
             uint8_t *d_c2 = nullptr;
-            DHIP(compaction_alloc(im, n, &sel));
-            DHIP(tbk_launch_dump_select(db_counts, n, lo, hi, sel.d_flags, sel.d_tiles, im.stream));
-            DHIP(compaction_total(im, &sel, &total));
+            DHIP(im.reserve(sel, n));
+            DHIP(tbk_launch_dump_select(db_counts, n, lo, hi, sel.d_flags, sel.counts(), im.stream));
+            DHIP(sel.total(&total));
             if (total != want) return dfail(TBK_ERR_HIP, "tbk_kmerdb_dump_text: %llu entries selected, the histogram states %llu", total, (unsigned long long)want);
             DHIP(im.alloc((void **)&d_k2, (size_t)want * sizeof(uint64_t)));
             DHIP(im.alloc((void **)&d_c2, (size_t)want));
             DHIP(tbk_launch_kmerdb_scatter_pairs(db_keys, db_counts, n, sel.d_flags, sel.offsets(), d_k2, d_c2, want, im.stream));
             DHIP(hipStreamSynchronize(im.stream));
-            compaction_free(im, &sel);
+            sel.release();
             d_keys = d_k2;
             d_counts = d_c2;
         }

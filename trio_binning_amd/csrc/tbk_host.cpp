@@ -31,6 +31,7 @@
 
 #include "../../include/tbk.h"
 #include "tbk_common.h"
+#include "tbk_compact_host.h"
 #include "tbk_pack.h"
 
 // ---- kernels' launchers (tbk_kernels.hip, tbk_synth.hip) -------------------------------
@@ -3172,7 +3173,6 @@ extern "C" hipError_t tbk_launch_track_runs(const uint64_t *, uint64_t, const ui
                                             tbk_hit_run *, uint64_t *, uint64_t, int32_t *, hipStream_t);
 extern "C" uint64_t tbk_track_tiles(uint64_t n_markers);
 extern "C" uint64_t tbk_track_flag_words(uint64_t n_markers);
-extern "C" hipError_t tbk_launch_kmerdb_scan(const unsigned long long *, unsigned long long *, uint64_t, hipStream_t);
 extern "C" hipError_t tbk_launch_track_endpoints(const tbk_hit_run *, uint64_t, const uint64_t *, int, uint64_t *, hipStream_t);
 extern "C" hipError_t tbk_launch_track_lifted(const tbk_hit_run *, uint64_t, const uint64_t *, const uint64_t *, tbk_hit_run_lifted *, hipStream_t);
 extern "C" int tbk_hpc_lift_device_(tbk_hpc *, const uint64_t *, uint64_t, uint64_t *, hipStream_t);    // tbk_hpc_host.cpp
