@@ -92,3 +92,73 @@ def absent_stretches(counts, clean):
         out.append((start, len(clean) - 1))
     return out
 
+
+# ---- the same with numpy, for databases and batches that the loop above cannot follow -----------------------------------------
+# tests/test_host_db_query_ref_np.py holds it to the loop on small inputs before it judges the device on large ones.
+_CODE = np.full(256, 255, dtype=np.uint8)
+for _i, _c in enumerate(b"ACGT"):
+    _CODE[_c] = _CODE[_c + 32] = _i
+
+
+def window_ranks(bases, offsets, k):
+    """(rank, clean), one per base of the batch: the database key of the canonical k-mer of the window that starts there -
+    the smaller of the forward and the reverse-complement rank, which is the lexicographic minimum - and whether the window is
+    clean (k bases of ACGT, either case, inside one sequence).  rank is 0 where clean is False."""
+    bases = np.asarray(bases, dtype=np.uint8)
+    off = np.asarray(offsets).astype(np.int64)
+    total = int(off[-1]) if off.size else 0
+    codes = _CODE[bases[:total]]
+    bad = np.concatenate([[0], np.cumsum(codes == 255)])
+    nw = max(total - k + 1, 0)
+    clean = np.zeros(total, dtype=bool)
+    rank = np.zeros(total, dtype=np.uint64)
+    if not nw:
+        return rank, clean
+    clean[:nw] = bad[k:k + nw] == bad[:nw]
+    left = np.repeat(off[1:], np.diff(off)) - np.arange(total)  # bases from here to the end of the sequence
+    clean &= left >= k
+    c = (codes & 3).astype(np.uint64)
+    fwd = np.zeros(nw, dtype=np.uint64)
+    rc = np.zeros(nw, dtype=np.uint64)
+    for j in range(k):
+        fwd |= c[j:j + nw] << np.uint64(2 * (k - 1 - j))
+        rc |= (np.uint64(3) - c[j:j + nw]) << np.uint64(2 * j)
+    rank[:nw] = np.minimum(fwd, rc)
+    rank[~clean] = 0
+    return rank, clean
+
+
+class TallyNp:
+    """Tally for a database given as its sorted ranks and their counters: the same answers, from searchsorted and bincount."""
+
+    def __init__(self, ranks, counters):
+        self.ranks = np.asarray(ranks, dtype=np.uint64)
+        self.counters = np.asarray(counters, dtype=np.uint8)
+        assert self.ranks.size == self.counters.size and (self.ranks.size < 2 or (self.ranks[1:] > self.ranks[:-1]).all())
+        self.hist = np.zeros(256, dtype=np.uint64)
+        self.copies = np.zeros(self.ranks.size, dtype=np.uint64)
+
+    def add(self, bases, offsets, k, min_count=2):
+        """(per_read (n, 2) uint64, counts uint8 per base of the batch) of one batch, which is added to the tally"""
+        off = np.asarray(offsets).astype(np.int64)
+        rank, clean = window_ranks(bases, offsets, k)
+        counts = np.zeros(rank.size, dtype=np.uint8)
+        if self.ranks.size:
+            at = np.minimum(np.searchsorted(self.ranks, rank), self.ranks.size - 1)
+            hit = clean & (self.ranks[at] == rank)
+            counts[hit] = self.counters[at[hit]]
+            self.copies += np.bincount(at[hit], minlength=self.ranks.size).astype(np.uint64)
+        self.hist += np.bincount(counts[clean], minlength=256).astype(np.uint64)
+        before = np.zeros((rank.size + 1, 2), dtype=np.uint64)
+        np.cumsum(clean, out=before[1:, 0])
+        np.cumsum(clean & (counts >= max(2, min_count)), out=before[1:, 1])
+        return before[off[1:]] - before[off[:-1]], counts
+
+    def completeness(self, min_count=2, max_count=255):
+        solid = (self.counters >= max(2, min_count)) & (self.counters <= min(255, max_count))
+        return int((solid & (self.copies > 0)).sum()), int(solid.sum())
+
+    def spectrum(self):
+        spec = np.zeros((6, 256), dtype=np.uint64)
+        np.add.at(spec, (np.minimum(self.copies, 5).astype(np.int64), self.counters.astype(np.int64)), 1)
+        return spec

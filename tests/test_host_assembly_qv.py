@@ -186,6 +186,16 @@ def test_the_new_symbols_and_their_signatures(built):
     assert alias is impl or alias.main is impl.main
 
 
+def test_the_grid_hooks_are_no_part_of_the_header_and_refuse_null(built):
+    from trio_binning_amd import _lib
+
+    header = open(os.path.join(os.path.dirname(DATA), "..", "include", "tbk.h")).read()
+    for name in ("tbk_kmerdb_query_set_wave_slots_", "tbk_hit_tracker_set_wave_slots_"):
+        fn = getattr(_lib.lib, name)
+        assert fn.restype == C.c_int and list(fn.argtypes) == [C.c_void_p, C.c_uint64] and name not in header
+        assert fn(None, 3) == _lib.TBK_ERR_INVALID and fn(None, 0) == _lib.TBK_ERR_INVALID
+
+
 # ---- the reference of the GPU tests against the oracle -------------------------------------------------------------------------------
 def _fastq_reads(path):
     return [line.strip() for i, line in enumerate(open(path)) if i % 4 == 1]

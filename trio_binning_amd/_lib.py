@@ -236,6 +236,7 @@ if HAS_HIT_TRACKER:
     _sig("tbk_hit_tracker_marks", C.c_int, _vp, _vp, _vp, _u64, C.c_int, _vp)
     _sig("tbk_hit_tracker_runs_compressed", C.c_int, _vp, _vp, _vp, _u64, C.c_int, C.POINTER(_vp), _u64p, _vp)
     _sig("tbk_hit_tracker_marks_compressed", C.c_int, _vp, _vp, _vp, _u64, C.c_int, _vp)
+    _sig("tbk_hit_tracker_set_wave_slots_", C.c_int, _vp, _u64)  # (test hook: the grid of the launches that stride over passes or reads)
 HAS_KMERDB_FULL = hasattr(lib, "tbk_kmerdb_union")  # (variant builds of tools/build_variant.sh may predate full databases)
 if HAS_KMERDB_FULL:
     _sig("tbk_kmerdb_floor", C.c_int, _vp, C.POINTER(C.c_int))
@@ -252,6 +253,7 @@ if HAS_DB_QUERY:
     _sig("tbk_kmerdb_query_copy_spectrum", C.c_int, _vp, _vp)
     _sig("tbk_kmerdb_query_reset", C.c_int, _vp)
     _sig("tbk_kmerdb_query_set_windows_", C.c_int, _vp, _u64)  # (test hook: the running total of window starts)
+    _sig("tbk_kmerdb_query_set_wave_slots_", C.c_int, _vp, _u64)  # (test hook: the grid of the launches that stride over passes or reads)
 
 class DumpOptions(C.Structure):
     """tbk_dump_options (include/tbk.h)."""

@@ -1538,6 +1538,15 @@ extern "C" int tbk_kmerdb_query_set_windows_(tbk_kmerdb_query *q, uint64_t windo
     return TBK_OK;
 }
 
+// (test hook, not in tbk.h: the grid of the launches that stride over passes or reads, so that a small batch takes a
+// second trip of their loops)
+extern "C" int tbk_kmerdb_query_set_wave_slots_(tbk_kmerdb_query *q, uint64_t wave_slots) {
+    if (!q) return cfail(TBK_ERR_INVALID, "query is NULL");
+    if (!wave_slots) return cfail(TBK_ERR_INVALID, "wave_slots is 0");
+    q->wave_slots = wave_slots;
+    return TBK_OK;
+}
+
 extern "C" int tbk_kmerdb_query_add(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t min_count,
                                     uint64_t *per_read, uint8_t *counts) {
     if (!q) return cfail(TBK_ERR_INVALID, "query is NULL");

@@ -3224,6 +3224,15 @@ extern "C" int tbk_hit_tracker_create(tbk_table *hap_a, tbk_table *hap_b, tbk_hi
     return TBK_OK;
 }
 
+// (test hook, not in tbk.h: the grid of the launches that stride over passes or reads, so that a small batch takes a
+// second trip of their loops)
+extern "C" int tbk_hit_tracker_set_wave_slots_(tbk_hit_tracker *t, uint64_t wave_slots) {
+    if (!t) return fail(TBK_ERR_INVALID, "tracker is NULL");
+    if (!wave_slots) return fail(TBK_ERR_INVALID, "wave_slots is 0");
+    t->wave_slots = wave_slots;
+    return TBK_OK;
+}
+
 extern "C" void tbk_hit_tracker_destroy(tbk_hit_tracker *t) {
     if (!t) return;
     if (hipSetDevice(t->device) == hipSuccess)
