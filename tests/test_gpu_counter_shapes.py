@@ -13,7 +13,8 @@ compare counts, histograms and A-minus-B lists with oracle/unique_oracle.py's nu
   test_load_and_growth                   TBK_COUNT_LOAD at and beyond its clamps, tables that start at 16 buckets
   test_multi_piece_add                   one add of four pieces (> 3 x 64 M window starts), the table growing between them
   test_multi_piece_add_in_passes         the same add with passes = 3: the rebuild between the pieces falls into class 0
-  test_clamp_keeps_a_counter_below_the_carry   one counter past 2^32 window starts with seven witnesses in its bucket
+  test_clamp_keeps_a_counter_below_the_carry   one counter past 2^32 window starts with seven witnesses in its bucket; with the
+                                         table kernels' grid capped at one block too (the clamp's later trips)
 
 The matrix runs W = 0 at k = 15, 21, 32, every W from 1 to 8 with m <= 16 (45 triples, m = 4 .. 16, and W = 9, which is clamped
 to 8) and every W from 1 to 8 with m >= 17 (47 triples, m = 17 .. 32, and W = 9); the whole file takes 37 s on an MI355X, 27 s of
@@ -433,7 +434,20 @@ def _mix32(key):
     return h
 
 
-def test_clamp_keeps_a_counter_below_the_carry(gpu, tmp_path, monkeypatch):
+@pytest.fixture
+def entry_cap(gpu):
+    """set(entry_blocks): the cap of tbk_count_set_grid_caps_ on the launches that stride over table slots, the stream cap left
+    at 0; (0, 0) again when the test ends, however it ends"""
+    def set_cap(entry_blocks):
+        assert gpu.lib.tbk_count_set_grid_caps_(0, entry_blocks) == 0
+    try:
+        yield set_cap
+    finally:
+        gpu.lib.tbk_count_set_grid_caps_(0, 0)
+
+
+@pytest.mark.parametrize("entry_blocks", [0, 1])
+def test_clamp_keeps_a_counter_below_the_carry(gpu, tmp_path, monkeypatch, entry_cap, entry_blocks):
     """The eight 32-bit counters of a line are added to as four 64-bit words, so a counter that passed 2^32 would carry into its
     neighbour; counter_run sets every counter above 2^31 back to 2^31 (readers cap at 255) before 2^31 more window starts can have
     been added.  Here poly-A at k = 13 gets more than 2^32 + 2^28 window starts, with seven witnesses seen three times each in the
@@ -443,7 +457,12 @@ def test_clamp_keeps_a_counter_below_the_carry(gpu, tmp_path, monkeypatch):
     and its reverse complement packed with base 0 in the low bits; slots fill in index order.  Without the clamp the first witness
     reads 4.
 
+    entry_blocks = 1: the clamp (and the rebuild, the histogram and the dump) run as one block of 256 threads, so poly-A's
+    counter is set back on a later trip of tbk_count_clamp_kernel's loop, as every counter of a real parental library's table is;
+    the counting kernel keeps its grid.
+
     Measured on an MI355X: 3.0 s for the 545 adds of 8 Mbases (4096 launches' worth of same-address adds each), 3.4 s for the test."""
+    entry_cap(entry_blocks)
     k, read, per_add = 13, 1 << 20, 8
     batch = uo.pack(["A" * read] * per_add)
     windows = per_add * (read - k + 1)
@@ -457,6 +476,7 @@ def test_clamp_keeps_a_counter_below_the_carry(gpu, tmp_path, monkeypatch):
         keys = np.arange(1, 1 << 26, dtype=np.uint64)
         home = (_mix32(keys).astype(np.uint64) * np.uint64(n_buckets)) >> np.uint64(32)
         home0 = (int(_mix32(np.zeros(1, dtype=np.uint64))[0]) * n_buckets) >> 32
+        assert home0 * 8 >= entry_blocks * 256  # poly-A's slot (in its home bucket or a later one) lies past the capped clamp's first trip
         cand = keys[home == np.uint64(home0)]
         names = []
         for key in cand:

@@ -199,6 +199,9 @@ _sig("tbk_counter_distinct", C.c_int, _vp, _u64p)
 _sig("tbk_counter_stats", C.c_int, _vp, _u64p, _u64p, _u64p, _u64p)
 _sig("tbk_counter_params", C.c_int, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
 _sig("tbk_counter_unique", C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, C.c_char_p, _u64p)
+if hasattr(lib, "tbk_count_set_grid_caps_"):  # (variant builds of tools/build_variant.sh may predate it)
+    # (test hook: caps on the grids of the counter's and the databases' strided launches - stream blocks, entry blocks; 0 = none)
+    _sig("tbk_count_set_grid_caps_", C.c_int, C.c_uint32, C.c_uint32)
 HAS_KMERDB = hasattr(lib, "tbk_kmerdb_load")  # (variant builds of tools/build_variant.sh may predate the count databases)
 if HAS_KMERDB:
     _u8p = C.POINTER(C.c_uint8)

@@ -59,6 +59,9 @@
 // fast path do not see guests at all: only a lookup that found its own half left by keys looks for
 // them (in slots it already holds in registers).  k = 32 has no free bit: no guests there.
 #define TBK_GUEST 0x8000000000000000ull
+// The most blocks (one wave, one pass of 2048 window starts each) a tbk_count_kernel launch takes: tbk_launch_count and
+// tbk_launch_count_class form their grid with it, count_stream (tbk_count.cpp) holds its pieces below it.
+#define TBK_COUNT_GRID_BLOCKS (1u << 20)
 
 // ---- bucket selection --------------------------------------------------------------------
 // Not the reference's hash_function (c/kmers.c:98-103): hash values are not observable, so

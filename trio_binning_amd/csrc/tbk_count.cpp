@@ -252,7 +252,10 @@ static int count_stream(tbk_counter *c, const void *d_stream, uint64_t sep_total
     for (uint64_t p0 = 0; p0 < passes;) {
         uint64_t slots = (uint64_t)c->n_buckets * TBK_SLOTS_PER_BUCKET;
         // (at most 2^30 window starts however large the table: a piece on top of counters just set back to 2^31 must stay below 2^32 - see below)
-        const uint64_t piece = std::min<uint64_t>(std::max<uint64_t>(32768, slots / 4 / 2048), (1u << 19));
+        // A piece never exceeds the count launch's grid, so in product the kernel's pass loop takes one trip per block.
+        constexpr uint64_t piece_cap = 1u << 19;
+        static_assert(piece_cap <= TBK_COUNT_GRID_BLOCKS, "a piece of count_stream must fit the grid of one tbk_count_kernel launch");
+        const uint64_t piece = std::min<uint64_t>(std::max<uint64_t>(32768, slots / 4 / 2048), piece_cap);
         const uint64_t np = std::min(piece, passes - p0), windows = np * 2048;
         if ((double)(c->used + windows) > 0.85 * (double)slots) {
             uint64_t want = (uint64_t)((double)slots * c->load) * 2;  // twice the present capacity

@@ -21,6 +21,20 @@
 // consecutive windows of a read update the same line while it sits in L2), probe sequence
 // tbk_next_bucket.
 
+// (test hook, not in tbk.h: caps on the grids of this file's strided launches, so that a small input takes the later trips of
+// their loops.  stream_blocks holds the launches that stride over reads, chunks or passes - separate, retain, both count
+// launches - and entry_blocks those that stride over table slots or database entries; 0 = no cap, the state at load.  The
+// tile-per-block launches of tbk_compact.h and the rocPRIM scan and sorts take no cap.  Plain globals, read at every launch of
+// the process: for a single-threaded test that puts (0, 0) back.)
+static uint32_t g_stream_blocks = 0, g_entry_blocks = 0;
+extern "C" int tbk_count_set_grid_caps_(uint32_t stream_blocks, uint32_t entry_blocks) {
+    g_stream_blocks = stream_blocks;
+    g_entry_blocks = entry_blocks;
+    return 0;
+}
+static inline unsigned stream_grid(uint64_t blocks) { return (unsigned)(g_stream_blocks && blocks > g_stream_blocks ? g_stream_blocks : blocks); }
+static inline unsigned entry_grid(uint64_t blocks) { return (unsigned)(g_entry_blocks && blocks > g_entry_blocks ? g_entry_blocks : blocks); }
+
 // Copy reads that lie back to back into a stream where every read is followed by one 'N', upper-
 // casing on the way (KMC counts lower-case bases like upper-case ones): a window can then never
 // span two reads and validity is the not-ACGT mask alone.  One wave per read.
@@ -260,7 +274,7 @@ tbk_count_clamp_kernel(TbkCountView t) {
 }
 
 extern "C" hipError_t tbk_launch_count_clamp(uint64_t *d_lines, uint32_t n_buckets, TbkMz mz, hipStream_t stream) {
-    hipLaunchKernelGGL(tbk_count_clamp_kernel, dim3(4096), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz});
+    hipLaunchKernelGGL(tbk_count_clamp_kernel, dim3(entry_grid(4096)), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz});
     return hipGetLastError();
 }
 
@@ -755,13 +769,13 @@ extern "C" hipError_t tbk_launch_separate(const uint8_t *d_bases, const uint64_t
     if (!n_reads) return hipSuccess;
     uint64_t blocks = (n_reads + 3) / 4;
     if (blocks > 262144) blocks = 262144;
-    hipLaunchKernelGGL(tbk_separate_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_bases, d_offsets, n_reads, d_out);
+    hipLaunchKernelGGL(tbk_separate_kernel, dim3(stream_grid(blocks)), dim3(256), 0, stream, d_bases, d_offsets, n_reads, d_out);
     return hipGetLastError();
 }
 
 extern "C" hipError_t tbk_launch_count_rehash(uint64_t *from_lines, uint32_t from_buckets, TbkMz from_mz, uint64_t *to_lines,
                                               uint32_t to_buckets, TbkMz to_mz, int *d_failed, hipStream_t stream) {
-    hipLaunchKernelGGL(tbk_count_rehash_kernel, dim3(8192), dim3(256), 0, stream, TbkCountView{from_lines, from_buckets, from_mz},
+    hipLaunchKernelGGL(tbk_count_rehash_kernel, dim3(entry_grid(8192)), dim3(256), 0, stream, TbkCountView{from_lines, from_buckets, from_mz},
                        TbkCountView{to_lines, to_buckets, to_mz}, d_failed);
     return hipGetLastError();
 }
@@ -771,7 +785,7 @@ extern "C" hipError_t tbk_launch_count(const uint8_t *d_sep, uint64_t total, uin
                                        uint64_t *d_lines, uint32_t n_buckets, TbkMz mz, int *d_failed, unsigned long long *d_used,
                                        hipStream_t stream) {
     if (total < (uint64_t)k || !n_passes) return hipSuccess;
-    const uint64_t blocks = n_passes < (1u << 20) ? n_passes : (1u << 20);
+    const uint64_t blocks = stream_grid(n_passes < TBK_COUNT_GRID_BLOCKS ? n_passes : TBK_COUNT_GRID_BLOCKS);
     const TbkCountView view{d_lines, n_buckets, mz};
     const dim3 grid((unsigned)blocks), block(64);
     const bool m64 = mz.m > 16;
@@ -789,14 +803,14 @@ extern "C" hipError_t tbk_launch_count(const uint8_t *d_sep, uint64_t total, uin
 
 extern "C" hipError_t tbk_launch_count_histogram(uint64_t *d_lines, uint32_t n_buckets, TbkMz mz, unsigned long long *d_hist,
                                                  hipStream_t stream) {
-    hipLaunchKernelGGL(tbk_count_histogram_kernel, dim3(4096), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz}, d_hist);
+    hipLaunchKernelGGL(tbk_count_histogram_kernel, dim3(entry_grid(4096)), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz}, d_hist);
     return hipGetLastError();
 }
 
 extern "C" hipError_t tbk_launch_count_unique(uint64_t *a_lines, uint32_t a_buckets, TbkMz a_mz, uint64_t *b_lines, uint32_t b_buckets,
                                               TbkMz b_mz, int k, uint32_t ci, uint32_t cx, uint64_t *d_out, uint64_t capacity,
                                               unsigned long long *d_n, hipStream_t stream) {
-    hipLaunchKernelGGL(tbk_count_unique_kernel, dim3(8192), dim3(256), 0, stream, TbkCountView{a_lines, a_buckets, a_mz},
+    hipLaunchKernelGGL(tbk_count_unique_kernel, dim3(entry_grid(8192)), dim3(256), 0, stream, TbkCountView{a_lines, a_buckets, a_mz},
                        TbkCountView{b_lines, b_buckets, b_mz}, k, ci, cx, d_out, capacity, d_n);
     return hipGetLastError();
 }
@@ -805,7 +819,7 @@ extern "C" hipError_t tbk_launch_count_unique(uint64_t *a_lines, uint32_t a_buck
 extern "C" hipError_t tbk_launch_retain(const uint8_t *d_sep, uint64_t total, uint64_t *d_store, uint64_t n_chunks, hipStream_t stream) {
     if (!n_chunks) return hipSuccess;
     const uint64_t blocks = (n_chunks + 255) / 256;
-    hipLaunchKernelGGL(tbk_retain_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, d_sep, total, d_store, n_chunks);
+    hipLaunchKernelGGL(tbk_retain_kernel, dim3(stream_grid(blocks < 65536 ? blocks : 65536)), dim3(256), 0, stream, d_sep, total, d_store, n_chunks);
     return hipGetLastError();
 }
 
@@ -816,7 +830,7 @@ extern "C" hipError_t tbk_launch_count_class(const uint64_t *d_store, uint64_t n
     const uint64_t total = n_chunks * 16;
     if (total < (uint64_t)k || !n_passes) return hipSuccess;
     if (!n_classes || cls >= n_classes) return hipErrorInvalidValue;
-    const uint64_t blocks = n_passes < (1u << 20) ? n_passes : (1u << 20);
+    const uint64_t blocks = stream_grid(n_passes < TBK_COUNT_GRID_BLOCKS ? n_passes : TBK_COUNT_GRID_BLOCKS);
     const TbkCountView view{d_lines, n_buckets, mz};
     const TbkClassSel sel{n_classes, cls};
     const uint8_t *d_bases = reinterpret_cast<const uint8_t *>(d_store);
@@ -837,7 +851,7 @@ extern "C" hipError_t tbk_launch_count_class(const uint64_t *d_store, uint64_t n
 extern "C" hipError_t tbk_launch_count_distil(uint64_t *d_lines, uint32_t n_buckets, TbkMz mz, uint32_t floor, uint64_t *d_keys, uint8_t *d_counts,
                                               uint64_t capacity, unsigned long long *d_n, hipStream_t stream) {
     if (floor < 1 || floor > 2) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tbk_count_distil_kernel, dim3(4096), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz}, floor, d_keys, d_counts, capacity, d_n);
+    hipLaunchKernelGGL(tbk_count_distil_kernel, dim3(entry_grid(4096)), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz}, floor, d_keys, d_counts, capacity, d_n);
     return hipGetLastError();
 }
 
@@ -846,7 +860,7 @@ extern "C" hipError_t tbk_launch_db_unique(const uint64_t *a_keys, const uint8_t
                                            hipStream_t stream) {
     if (!n_a) return hipSuccess;
     const uint64_t blocks = (n_a + 255) / 256;
-    hipLaunchKernelGGL(tbk_db_unique_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, a_keys, a_counts, n_a, b_sorted, n_b,
+    hipLaunchKernelGGL(tbk_db_unique_kernel, dim3(entry_grid(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, a_keys, a_counts, n_a, b_sorted, n_b,
                        k, ci, cx, d_out, capacity, d_n);
     return hipGetLastError();
 }
@@ -855,7 +869,7 @@ extern "C" hipError_t tbk_launch_db_unique(const uint64_t *a_keys, const uint8_t
 extern "C" hipError_t tbk_launch_count_export(uint64_t *d_lines, uint32_t n_buckets, TbkMz mz, int k, uint32_t floor, uint64_t *d_keys, uint8_t *d_counts,
                                               uint64_t capacity, unsigned long long *d_n, hipStream_t stream) {
     if (floor < 1 || floor > 2) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(tbk_count_export_kernel, dim3(4096), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz}, k, floor, d_keys, d_counts, capacity, d_n);
+    hipLaunchKernelGGL(tbk_count_export_kernel, dim3(entry_grid(4096)), dim3(256), 0, stream, TbkCountView{d_lines, n_buckets, mz}, k, floor, d_keys, d_counts, capacity, d_n);
     return hipGetLastError();
 }
 
@@ -863,7 +877,7 @@ extern "C" hipError_t tbk_launch_db_rank(const uint64_t *d_keys, const uint8_t *
                                          uint8_t *d_out_counts, hipStream_t stream) {
     if (!n) return hipSuccess;
     const uint64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(tbk_db_rank_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, d_keys, d_counts, n, k, d_out_keys, d_out_counts);
+    hipLaunchKernelGGL(tbk_db_rank_kernel, dim3(entry_grid(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, d_keys, d_counts, n, k, d_out_keys, d_out_counts);
     return hipGetLastError();
 }
 
@@ -874,7 +888,7 @@ extern "C" hipError_t tbk_launch_kmerdb_check(const uint64_t *d_keys, const uint
     if (floor < 1 || floor > 2) return hipErrorInvalidValue;
     const uint64_t high_mask = k >= 32 ? 0ull : ~0ull << (2 * k);
     const uint64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(tbk_kmerdb_check_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, d_keys, d_counts, n, high_mask, floor, d_tally);
+    hipLaunchKernelGGL(tbk_kmerdb_check_kernel, dim3(entry_grid(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, d_keys, d_counts, n, high_mask, floor, d_tally);
     return hipGetLastError();
 }
 
@@ -883,7 +897,7 @@ extern "C" hipError_t tbk_launch_kmerdb_unique(const uint64_t *a_keys, const uin
                                                hipStream_t stream) {
     if (!n_a) return hipSuccess;
     const uint64_t blocks = (n_a + 255) / 256;
-    hipLaunchKernelGGL(tbk_kmerdb_unique_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, a_keys, a_counts, n_a, b_keys, n_b,
+    hipLaunchKernelGGL(tbk_kmerdb_unique_kernel, dim3(entry_grid(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, a_keys, a_counts, n_a, b_keys, n_b,
                        ci, cx, d_out, capacity, d_n);
     return hipGetLastError();
 }
@@ -941,7 +955,7 @@ extern "C" hipError_t tbk_launch_db_solid_keys(const uint64_t *d_keys, const uin
                                                unsigned long long *d_n, hipStream_t stream) {
     if (!n) return hipSuccess;
     const uint64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(tbk_db_solid_keys_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, d_keys, d_counts, n, d_out, capacity, d_n);
+    hipLaunchKernelGGL(tbk_db_solid_keys_kernel, dim3(entry_grid(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, d_keys, d_counts, n, d_out, capacity, d_n);
     return hipGetLastError();
 }
 
@@ -975,6 +989,6 @@ extern "C" hipError_t tbk_launch_kmerdb_union_scatter(const uint64_t *a_keys, co
 extern "C" hipError_t tbk_launch_kmerdb_tally(const uint8_t *d_counts, uint64_t n, unsigned long long *d_hist, hipStream_t stream) {
     if (!n) return hipSuccess;
     const uint64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(tbk_kmerdb_tally_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, d_counts, n, d_hist);
+    hipLaunchKernelGGL(tbk_kmerdb_tally_kernel, dim3(entry_grid(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, d_counts, n, d_hist);
     return hipGetLastError();
 }
