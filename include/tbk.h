@@ -475,6 +475,49 @@ int tbk_gzip_bench_device(int device, const char *text, const uint64_t *member_l
  * block's CRC-32 checked there.  data / size: the file's bytes (or a run of whole blocks); *text_len: bytes of text.  The reader
  * (tbk_fastx_set_device) drives the same inflater four windows deep. */
 int tbk_bgzf_inflate_device(int device, const uint8_t *data, uint64_t size, uint8_t *dst, uint64_t cap, uint64_t *text_len);
+/* ---- BAM input: unaligned BAM (PacBio HiFi, ONT uBAM) read as FASTQ ------------------------------------------------------------------
+ * tbk_fastx_open reads a path that ends in ".bam" as a BAM file: a bgzf stream (its first 18 bytes must be a bgzf block, TBK_ERR_FORMAT
+ * otherwise) whose text is
+ *     magic "BAM\1", l_text (int32), text[l_text], n_ref (int32), n_ref x { l_name (int32), name[l_name], l_ref (int32) }
+ * and then records: block_size (int32: the bytes that follow) and a 32-byte fixed part.  Counted from the block_size field:
+ *     +12 l_read_name (u8, counts the NUL)   +16 n_cigar_op (u16)   +18 flag (u16)   +20 l_seq (u32)   +36 read_name
+ * then cigar[4 * n_cigar_op], seq[(l_seq + 1) / 2], qual[l_seq] and tags up to block_size.  Everything is little-endian.  Base i is
+ * (seq[i >> 1] >> (4 * (1 - (i & 1)))) & 15 - the high nibble first - read through the table "=ACMGRSVTWYHKDBN".  The header and a
+ * record may span any number of bgzf blocks; a missing bgzf end-of-file marker is accepted.
+ *
+ * The text of a record, which the reader's parser then sees in the file's place, is
+ *     '@' name '\n' SEQ '\n' '+' '\n' QUAL '\n'        (l_read_name - 1 + 2 * l_seq + 6 bytes)
+ * with name = the l_read_name - 1 bytes before the NUL and QUAL[i] = min(qual[i], 93) + 33.  When qual[0] == 0xFF the quality is
+ * absent and the record is written as FASTA, '>' name '\n' SEQ '\n': has_qual is 0 and no quality is invented.  With flag & 0x10
+ * SEQ is the reverse complement (the complement of the letters in code order is "=TGKCYSBAWRDMHVN") and QUAL is reversed, as samtools
+ * fastq writes them.  Records with flag & skip_flags, and records with l_seq == 0, are skipped and counted; the reader's skip_flags
+ * are 0x900 (secondary and supplementary: samtools fastq's default).  No /1 or /2 is added and no tag reaches the header.
+ *
+ * Refused with TBK_ERR_FORMAT and the record's 0-based number in tbk_last_error(), the first bad record in file order:
+ *     block_size > TBK_BAM_MAX_RECORD;  block_size < 32 + l_read_name + 4 * n_cigar_op + (l_seq + 1) / 2 + l_seq;  l_read_name < 2;
+ *     a name without a NUL at its end;  a name byte outside 0x21..0x7E;  a file that ends inside a record
+ * and, without a record number, a file that ends inside the header and a text that does not begin with "BAM\1".
+ *
+ * With tbk_fastx_set_device the bgzf blocks are inflated and the records turned into text on that device (csrc/tbk_bam.hip), window
+ * after window (TBK_BGZF_GPU_WINDOW bytes of the file each); without one, or when the inflater cannot be set up, the host's threads
+ * do both.  An error ends the reader: every later call gives it again. */
+#define TBK_BAM_MAX_RECORD (1u << 28)
+/* The transcoder by itself, on `device`: records / size = a run of whole BAM records in host memory, offsets[n] = where each begins
+ * (each must lie wholly within size: TBK_ERR_INVALID otherwise).  The text of the records that are not skipped is written back to back
+ * into dst; *text_len = its bytes - also with TBK_ERR_NOMEM, when cap is too small (dst may then be NULL) - and *n_written /
+ * *n_skipped count the records.  TBK_ERR_FORMAT names the first refused record's index in tbk_last_error(). */
+int tbk_bam_fastq_device(int device, const uint8_t *records, uint64_t size, const uint64_t *offsets, uint64_t n, uint32_t skip_flags, uint8_t *dst,
+                         uint64_t cap, uint64_t *text_len, uint64_t *n_written, uint64_t *n_skipped);
+/* The same by the plain C++ of csrc/tbk_bam.h (what the reader runs without a device, on all its threads). */
+int tbk_bam_fastq(const uint8_t *records, uint64_t size, const uint64_t *offsets, uint64_t n, uint32_t skip_flags, uint8_t *dst, uint64_t cap,
+                  uint64_t *text_len, uint64_t *n_written, uint64_t *n_skipped);
+/* The kernels timed by themselves (tools/measure_bam.py): the window resident on the device, one warm-up, then `reps` times
+ * whole_s[i] = measure, scan, the text's size home and the write kernel (wall clock, the stream idle either side) and write_s[i] = the
+ * write kernel alone between HIP events; *text_len: the window's text. */
+int tbk_bam_bench_device(int device, const uint8_t *records, uint64_t size, const uint64_t *offsets, uint64_t n, uint32_t skip_flags, int reps,
+                         double *whole_s, double *write_s, uint64_t *text_len);
+/* 1 when the reader's file is read as BAM; out[0] = records seen so far, out[1] = of them skipped. */
+int tbk_fastx_bam_counts(const tbk_fastx_reader *r, uint64_t out[2]);
 /* The inflater timed by itself (bench.py's `input_bgzf_inflater`): one window of bgzf blocks, `reps` times - *kernels_s per window with the
  * input resident (HIP events around inflate, CRC-32 and check), *ring_s per window through the ring as the reader drives it (staging
  * copy, copy in, kernels, text home; two windows in flight); *text_bytes: a window's text. */

@@ -44,7 +44,7 @@ COPY_LABELS = ("0", "1", "2", "3", "4", ">4")
 
 def _parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(prog=PROG, description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    parser.add_argument("assembly", help="contigs (or reads) to score, in fasta/q format. Can be gzipped.")
+    parser.add_argument("assembly", help="contigs (or reads) to score, FASTA/FASTQ(.gz) or BAM.")
     parser.add_argument("database", help="the count database of the reads (*.tbkdb, kept by find-unique-kmers --keep-databases)")
     parser.add_argument("--min-count", type=int, default=2, metavar="N",
                         help="the counter a k-mer needs to count as found, and as solid for completeness (2..255; default 2). "

@@ -92,7 +92,7 @@ def _parser(kmer_list_type) -> argparse.ArgumentParser:
     )
     parser.add_argument(
         "reads",
-        help="reads to classify into bins, in fasta/q format. Can be gzipped.",
+        help="reads to classify into bins, in fasta/q format: FASTA/FASTQ(.gz) or BAM (unaligned, such as reads.hifi_reads.bam).",
     )
     parser.add_argument(
         "haplotype_a_kmers",
@@ -278,6 +278,8 @@ def output_extension(reads_path: str) -> str:
     """Extension of the bin files.  The reference computes
     ``splitext(reads.rstrip(".gz"))[1]`` (classify_by_kmers.py:90): ``rstrip`` strips the
     character set {'.', 'g', 'z'}, not the suffix, and that quirk decides file names."""
+    if reads_path.endswith(".bam"):  # BAM input: the bins hold the reads' FASTQ text (include/tbk.h "BAM input")
+        return ".fastq"
     return path.splitext(reads_path.rstrip(".gz"))[1]
 
 

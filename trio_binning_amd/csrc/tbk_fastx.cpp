@@ -47,6 +47,7 @@
 #include "tbk_pack.h"
 #include "tbk_gdeflate.h"
 #include "tbk_gzplan.h"
+#include "tbk_bam.h"
 
 uint32_t tbk_crc32(uint32_t crc, const uint8_t *p, size_t n);  // tbk_crc.cpp: zlib's crc32() by carry-less multiplication
 
@@ -161,6 +162,11 @@ struct LineSource {
     // by side.  Same bytes as the sequential path; taken while every member at hand is such a block.
     bool bgzf = false;
     bool bgzf_seen = false;  // a BGZF member has been read: zero padding may follow it (Python's GzipFile skips it)
+    // The bgzf file's text is a BAM file (a path that ends in .bam): bam_loop turns its records into FASTQ text, and that is the text
+    // the parser gets.  err_code: what a failed refill is reported as (TBK_ERR_FORMAT for a refused BAM record or header).
+    bool bam = false;
+    int err_code = TBK_ERR_IO;
+    std::atomic<uint64_t> bam_records{0}, bam_skipped{0};   // records seen (the number of the next one), records skipped
     // BGZF blocks inflated on the GPU (tbk_fastx_set_device; csrc/tbk_gdeflate.hip, second half): one wave per block, windows of
     // 96 MB of the file four deep.  -1: on the host's threads.
     int gpu_device = -1;
@@ -183,10 +189,11 @@ struct LineSource {
     uint32_t member_crc = 0;   // CRC-32 of the member's output so far
     uint64_t member_size = 0;
 
-    bool open_path(const char *path, bool gzip) {
+    bool open_path(const char *path, bool gzip, bool is_bam = false) {
         fd = ::open(path, O_RDONLY);
         if (fd < 0) { err = std::string("cannot open ") + path + ": " + strerror(errno); return false; }
-        gz = gzip;
+        gz = gzip || is_bam;
+        bam = is_bam;
         buf.resize(1 << 22);
         if (gz) {
             zin.resize(1 << 20);
@@ -196,7 +203,8 @@ struct LineSource {
             threads = std::max(1, tbk_host_threads());
             uint8_t head[18];
             const ssize_t n = ::pread(fd, head, sizeof head, 0);
-            bgzf = threads > 1 && n == (ssize_t)sizeof head && bgzf_block_size(head, sizeof head) > 0;
+            bgzf = (threads > 1 || bam) && n == (ssize_t)sizeof head && bgzf_block_size(head, sizeof head) > 0;
+            if (bam && !bgzf) { err = std::string(path) + ": not a BAM file (its first 18 bytes are no bgzf block)"; err_code = TBK_ERR_FORMAT; return false; }
             const char *how = getenv("TBK_INFLATE");
             struct stat st;
             if (bgzf && fstat(fd, &st) == 0 && st.st_size > 0) {
@@ -485,6 +493,131 @@ struct LineSource {
             if (at_end) { (void)drain(); return; }
         }
     }
+    // ---- BAM input ----------------------------------------------------------------------------------
+    // The FASTQ text of records[offsets[0 .. n)] on the host's threads (tbk_bam.h: a pass for the lengths, a pass that writes, into a
+    // recycled buffer).  Returns TBK_BAM_NO_BAD or (index << 8 | reason) of the first refused record.
+    uint64_t bam_text_host(const uint8_t *records, const uint64_t *offsets, uint64_t n, std::vector<uint8_t> &dst, uint64_t *text_len, uint64_t *n_skipped) {
+        TbkBamShares shares;
+        uint64_t written = 0;
+        const uint64_t bad = tbk_bam_fastq_shares(records, offsets, n, TBK_BAM_SKIP_DEFAULT_, threads, shares, nullptr, text_len, &written, n_skipped);
+        if (bad != TBK_BAM_NO_BAD || !*text_len) return bad;
+        dst = take_buffer((size_t)*text_len);
+        return tbk_bam_fastq_shares(records, offsets, n, TBK_BAM_SKIP_DEFAULT_, threads, shares, dst.data(), text_len, &written, n_skipped);
+    }
+    // A .bam path on the worker thread.  Window after window: the bgzf blocks are inflated (on the device through one slot of the GPU
+    // inflater when tbk_fastx_set_device was called and the file is mapped, else by bgzf_window on the host's threads), what the window
+    // before left over - part of the header, part of a record - goes in front of the inflated bytes, the header is skipped once, the
+    // whole records are indexed (tbk_bam_index) and turned into FASTQ text (csrc/tbk_bam.hip's kernels on the device,
+    // tbk_bam_fastq_host's threads without one), and the text is pushed as a chunk that owns it.  The windows go one after another, and
+    // the records are copied to the device again from the inflater's pinned output, where what was left over lies in front of them.  No inflater or transcoder, or no
+    // pinned memory for the first window: the host does both, from the first block on.
+    void bam_loop() {
+        tbk_ginflate *g = nullptr;
+        tbk_bamdev *dev = nullptr;
+        struct Free { tbk_ginflate *&g; tbk_bamdev *&dev; ~Free() { if (g) tbk_ginflate_destroy(g); if (dev) tbk_bamdev_destroy(dev); } } free_them{g, dev};
+        const char *limit = getenv("TBK_BGZF_GPU_SLOTS");   // (tests: as if the memory for the windows were not there)
+        bool on_device = gpu_device >= 0 && map && !(limit && atoi(limit) < 2);
+        if (on_device && tbk_ginflate_create(gpu_device, &g) != TBK_OK) on_device = false;
+        if (on_device && tbk_bamdev_create(gpu_device, &dev) != TBK_OK) on_device = false;
+        if (!on_device) gpu_device = -1;
+        const size_t window = std::max<size_t>((size_t)1 << 16, env_size("TBK_BGZF_GPU_WINDOW", (size_t)96 << 20));
+        auto fail_with = [&](int code, const std::string &msg) { err_code = code; Chunk c; c.err = msg; c.last = true; push(std::move(c)); };
+        auto refuse = [&](uint64_t record, uint32_t why) { fail_with(TBK_ERR_FORMAT, "BAM record " + std::to_string(record) + ": " + tbk_bam_reason(why)); };
+        std::vector<uint8_t> left, acc, host_text;   // left: what the windows so far have left over; acc: that and the window at hand (host path)
+        std::vector<uint64_t> offsets;
+        bool in_header = true, first_window = true;
+        for (;;) {
+            { std::lock_guard<std::mutex> lk(mu); if (stop) return; }
+            // the window at hand, what was left over in front of it: cur[0 .. cur_size)
+            const uint8_t *cur = left.data();
+            size_t cur_size = left.size(), cur_pos = 0;
+            bool at_end = false, truncated = false;   // truncated: the file ends inside a bgzf block (said once the records in front of it have been)
+            if (on_device) {
+                std::vector<tbk_ginflate_block> blks;
+                size_t span = 0, out_total = 0;
+                if (bgzf_scan(bgzf_map_pos, window, blks, &span, &out_total) < 0) { fail_with(TBK_ERR_IO, err); return; }
+                at_end = bgzf_map_pos + span >= map_size;
+                if (blks.empty() && !at_end) {
+                    if (span > 0) { bgzf_map_pos += span; continue; }   // only padding: drop it and look again
+                    if (map_size - bgzf_map_pos >= 18 && bgzf_block_size(map + bgzf_map_pos, map_size - bgzf_map_pos) == 0) { fail_with(TBK_ERR_FORMAT, "BAM: not a bgzf block"); return; }
+                    at_end = truncated = true;
+                }
+                if (out_total) {
+                    uint8_t *in = tbk_ginflate_input(g, 0, span);
+                    if (!in && first_window) { on_device = false; gpu_device = -1; continue; }   // the host's threads, from this very block on
+                    if (!in) { fail_with(TBK_ERR_IO, "inflate: no pinned memory for a BGZF window"); return; }
+                    memcpy(in, map + bgzf_map_pos, span);
+                    uint8_t *base = nullptr;
+                    size_t got = 0;
+                    uint32_t bad_blocks = 0;
+                    // (room in front of the window's text for what was left over: the records then lie in one piece of pinned memory)
+                    if (tbk_ginflate_submit(g, 0, span, blks.data(), blks.size(), left.size()) != TBK_OK || tbk_ginflate_wait(g, 0, &base, &got, &bad_blocks) != TBK_OK) {
+                        fail_with(TBK_ERR_IO, std::string("inflate: ") + tbk_last_error());
+                        return;
+                    }
+                    if (bad_blocks) { fail_with(TBK_ERR_IO, "inflate: corrupt BGZF block"); return; }
+                    if (!left.empty()) memcpy(base, left.data(), left.size());
+                    cur = base; cur_size = left.size() + got;
+                    gpu_windows++; gpu_blocks += blks.size();
+                }
+                first_window = false;
+                bgzf_map_pos += span;
+            } else {
+                size_t got = 0;
+                const int r = bgzf_window(host_text, &got, &at_end);
+                if (r < 0 && err == "truncated gzip file") at_end = truncated = true;
+                else if (r < 0) { fail_with(TBK_ERR_IO, err); return; }
+                else if (r == 0) { fail_with(TBK_ERR_FORMAT, "BAM: not a bgzf block"); return; }
+                if (got) {
+                    acc.assign(left.begin(), left.end());
+                    acc.insert(acc.end(), host_text.data(), host_text.data() + got);
+                    cur = acc.data(); cur_size = acc.size();
+                }
+            }
+            if (in_header) {
+                uint64_t len = 0;
+                if (tbk_bam_header_len(cur, cur_size, &len) != 0) { fail_with(TBK_ERR_FORMAT, "not a BAM file: its text does not begin with a BAM header"); return; }
+                if (len) { in_header = false; cur_pos = (size_t)len; }
+            }
+            while (!in_header) {
+                { std::lock_guard<std::mutex> lk(mu); if (stop) return; }
+                constexpr uint64_t CAP = (uint64_t)1 << 20;
+                offsets.resize(CAP);
+                uint64_t n = 0, consumed = 0, text_len = 0, skipped = 0, written = 0, bad = TBK_BAM_NO_BAD;
+                const uint8_t *recs = cur + cur_pos;
+                const uint32_t why = tbk_bam_index(recs, cur_size - cur_pos, offsets.data(), CAP, &n, &consumed);
+                Chunk c;
+                if (on_device) {
+                    if (tbk_bamdev_measure(dev, recs, consumed, offsets.data(), n, TBK_BAM_SKIP_DEFAULT_, bam_records, &text_len, &written, &skipped, &bad) != TBK_OK) {
+                        fail_with(TBK_ERR_IO, tbk_last_error());
+                        return;
+                    }
+                    if (bad != TBK_BAM_NO_BAD) { refuse(bad >> 8, (uint32_t)(bad & 0xFFu)); return; }
+                    if (text_len) {
+                        c.data = take_buffer((size_t)text_len);
+                        if (tbk_bamdev_write(dev, c.data.data()) != TBK_OK) { fail_with(TBK_ERR_IO, tbk_last_error()); return; }
+                    }
+                } else {
+                    bad = bam_text_host(recs, offsets.data(), n, c.data, &text_len, &skipped);
+                    if (bad != TBK_BAM_NO_BAD) { refuse(bam_records + (bad >> 8), (uint32_t)(bad & 0xFFu)); return; }
+                }
+                bam_records += n; bam_skipped += skipped;
+                cur_pos += (size_t)consumed;
+                if (why != TBK_BAM_OK) { refuse(bam_records, why); return; }
+                if (text_len) { c.off = 0; c.len = (size_t)text_len; push(std::move(c)); }
+                if (n < CAP) break;   // (the walk stopped for want of bytes, not of room)
+            }
+            if (at_end) {
+                if (in_header) { fail_with(TBK_ERR_FORMAT, "BAM: the file ends inside the header"); return; }
+                if (cur_pos < cur_size) { refuse(bam_records, TBK_BAM_CUT_OFF); return; }
+                if (truncated) { fail_with(TBK_ERR_IO, "truncated gzip file"); return; }
+                Chunk c; c.last = true; push(std::move(c));
+                return;
+            }
+            std::vector<uint8_t> rest(cur + cur_pos, cur + cur_size);   // (part of a record, or of the header: the slot's buffer is the next window's)
+            left.swap(rest);
+        }
+    }
     void inflate_loop() {
         constexpr size_t HIST = 32768, ROOM = (size_t)8 << 20;
         std::vector<uint8_t> tail;  // the last 32 KiB inflated so far
@@ -757,7 +890,7 @@ struct LineSource {
     // own decoder: returns like refill()
     bool refill_fast() {
         if (!worker_err.empty()) { err = worker_err; return false; }   // (the worker ended with it: said again, not waited for)
-        if (!started) { started = true; worker = std::thread([this] { if (bgzf && gpu_device >= 0 && map) bgzf_loop_gpu(); else if (bgzf) bgzf_loop(); else if (gzip_gpu) gzip_loop_gpu(); else if (guessing()) pinflate_loop(); else inflate_loop(); }); }
+        if (!started) { started = true; worker = std::thread([this] { if (bam) bam_loop(); else if (bgzf && gpu_device >= 0 && map) bgzf_loop_gpu(); else if (bgzf) bgzf_loop(); else if (gzip_gpu) gzip_loop_gpu(); else if (guessing()) pinflate_loop(); else inflate_loop(); }); }
         Chunk c;
         {
             const auto t0 = std::chrono::steady_clock::now();
@@ -1317,17 +1450,19 @@ extern "C" int tbk_fastx_open(const char *path, tbk_fastx_reader **out) {
     *out = nullptr;
     const size_t n = strlen(path);
     const bool gz = n >= 3 && strcmp(path + n - 3, ".gz") == 0;  // seq.py:88: by file name
+    const bool bam = n >= 4 && strcmp(path + n - 4, ".bam") == 0;  // unaligned BAM (include/tbk.h "BAM input"): its records reach the parser as FASTQ text
     tbk_fastx_reader *r = new tbk_fastx_reader();
-    if (!r->src.open_path(path, gz)) {
+    if (!r->src.open_path(path, gz, bam)) {
         std::string e = r->src.err;
+        const int code = r->src.err_code;
         r->src.close_all();
         delete r;
-        return ffail(TBK_ERR_IO, "%s", e.c_str());
+        return ffail(code, "%s", e.c_str());
     }
     // plain FASTQ: records are found and copied by several threads while they stay regular
     const char *scan_env = getenv("TBK_FASTQ_SCAN");
     struct stat st;
-    if (!gz && !(scan_env && *scan_env == '0') && fstat(r->src.fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
+    if (!gz && !bam && !(scan_env && *scan_env == '0') && fstat(r->src.fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
         void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, r->src.fd, 0);
         if (m != MAP_FAILED) {
             r->mapping = std::make_shared<FastxMapping>((const uint8_t *)m, (size_t)st.st_size);
@@ -1340,7 +1475,7 @@ extern "C" int tbk_fastx_open(const char *path, tbk_fastx_reader **out) {
     // than the sequential machine behind the inflater (3.4 against 3.6 GB/s): the inflating threads
     // are the limit and the scan's threads compete with them; it pays where cores are plentiful.
     const char *inflated_env = getenv("TBK_INFLATED_SCAN");
-    r->scan.inflated = gz && inflated_env && *inflated_env == '1' && !(scan_env && *scan_env == '0');
+    r->scan.inflated = (gz || bam) && inflated_env && *inflated_env == '1' && !(scan_env && *scan_env == '0');
     *out = r;
     return TBK_OK;
 }
@@ -1629,7 +1764,7 @@ static int regular_next_inflated(tbk_fastx_reader *r, tbk_fastx_batch *b, uint64
         if (max_bases != ~0ull) want = (size_t)std::min<double>((double)window, (double)(max_bases - have_bases) * sc.bytes_per_base * 1.02 + (double)((size_t)1 << 20));
         want = std::max(want, at_least);
         while (!src.text_eof && src.end - src.pos < want)
-            if (!src.refill()) return ffail(TBK_ERR_IO, "%s", src.err.c_str());
+            if (!src.refill()) return ffail(src.err_code, "%s", src.err.c_str());
         if (src.pos == src.end) return TBK_OK;  // nothing left: the machine will say so
         if (src.text()[src.pos] != '@') { sc.inflated = false; return TBK_OK; }
         size_t new_pos = src.pos;
@@ -1682,6 +1817,11 @@ extern "C" int tbk_fastx_set_device(tbk_fastx_reader *r, int device) {
 }
 // 1 when the reader's BGZF blocks are (being) inflated on a device
 extern "C" int tbk_fastx_inflates_on_device(const tbk_fastx_reader *r) { return r && (r->src.bgzf || r->src.gzip_gpu) && r->src.gpu_device >= 0 && r->src.map ? 1 : 0; }
+// BAM input: 1 when the reader's file is read as BAM; out[0] = records seen so far, out[1] = of them skipped (secondary, supplementary, no bases)
+extern "C" int tbk_fastx_bam_counts(const tbk_fastx_reader *r, uint64_t out[2]) {
+    if (out) { out[0] = r ? r->src.bam_records.load() : 0; out[1] = r ? r->src.bam_skipped.load() : 0; }
+    return r && r->src.bam ? 1 : 0;
+}
 // the gzip inflater's counts so far (tbk_gzip_inflate_stats's six), for a reader whose ordinary gzip input is inflated on a device
 extern "C" void tbk_fastx_gzip_stats(const tbk_fastx_reader *r, uint64_t out[6]) {
     const TbkGzStats z = {0, 0, 0, 0, 0, 0.0, 0};
@@ -1812,7 +1952,7 @@ static int fastx_next_records(tbk_fastx_reader *r, tbk_fastx_batch *b, uint64_t 
     bool term;
     for (;;) {
         int got = r->src.next(p, len, term);
-        if (got < 0) return ffail(TBK_ERR_IO, "%s", r->src.err.c_str());
+        if (got < 0) return ffail(r->src.err_code, "%s", r->src.err.c_str());
         if (got == 0) {  // input exhausted
             if (r->state == tbk_fastx_reader::SEQ) b->finish(false);
             else if (r->state == tbk_fastx_reader::QUAL) b->finish(false);  // short quality: FASTA (seq.py:81-83)

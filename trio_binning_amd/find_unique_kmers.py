@@ -101,7 +101,7 @@ def parse_args(argv=None):
     parser.add_argument(
         "read_files", nargs=2,
         help="one comma-separated list of file paths for both libraries being compared. Files can "
-             "be in fasta or fastq format, and uncompressed or gzipped. A single path ending in .tbkdb is a count "
+             "be FASTA/FASTQ(.gz) or BAM (unaligned). A single path ending in .tbkdb is a count "
              "database kept by --keep-databases: it is loaded instead of counted. A list may also mix full databases "
              "(kept with --keep-singletons) and read files: the reads are counted and united with the databases.",
     )
@@ -265,11 +265,11 @@ def count_library(paths: List[str], k: int, capacity: int, passes: int = 1, comp
 
 def estimate_bases(paths: List[str]) -> int:
     """Bases of a library from its file sizes: uncompressed FASTQ spends two bytes per base, gzip
-    compresses it about fourfold."""
+    compresses it about fourfold; a BAM file (bgzf) is counted as a gzip file."""
     bases = 0
     for p in paths:
         size = os.path.getsize(p)
-        bases += size * 2 if p.endswith(".gz") else size // 2 + 1
+        bases += size * 2 if p.endswith((".gz", ".bam")) else size // 2 + 1
     return bases
 
 

@@ -36,7 +36,7 @@ TSV_COLUMNS = ("name", "length", "markers_a", "markers_b", "blocks", "switches",
 
 def _parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(prog=PROG, description=__doc__, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
-    parser.add_argument("sequences", help="contigs or reads to locate the k-mers in, in fasta/q format. Can be gzipped.")
+    parser.add_argument("sequences", help="contigs or reads to locate the k-mers in, FASTA/FASTQ(.gz) or BAM.")
     parser.add_argument(
         "haplotype_a_kmers", metavar="hapA",
         help="a list of k-mers unique to haplotype A, one per line; or the count database of that parent kept by "

@@ -1,4 +1,4 @@
-"""FASTA/FASTQ(.gz) records in, three bins out.
+"""FASTA/FASTQ(.gz) or BAM records in, three bins out.
 
 Host-side mirror of the reference's ``trio_binning.seq`` (src/trio_binning/seq.py):
 ``Read``, ``readfq``, ``open_fastx_read`` and ``open_outfiles`` with the same record
@@ -99,10 +99,23 @@ def readfq(fp: Iterable[str]) -> Iterator[Read]:
 
 def open_fastx_read(filename: str) -> Iterator[Read]:
     """Open a fasta/q(.gz) file for reading (reference seq.py:86-92): gzip by file name,
-    text mode with universal newlines."""
+    text mode with universal newlines.  A name ending in ``.bam`` is an unaligned BAM file: its reads come from the native
+    reader's batches (include/tbk.h "BAM input")."""
+    if filename.endswith(".bam"):
+        return _native_reads(filename)
     if filename.endswith(".gz"):
         return readfq(gzip.open(filename, "rt"))
     return readfq(open(filename, "r"))
+
+
+def _native_reads(filename: str) -> Iterator[Read]:
+    with BatchReader(filename) as reader:
+        batch = Batch()
+        try:
+            while reader.next_batch(batch, 1 << 24, 0):
+                yield from batch.reads()
+        finally:
+            batch.close()
 
 
 TextOrGzip = Union[TextIO, IO[str]]
@@ -265,11 +278,11 @@ class Batch:
 
 
 class BatchReader:
-    """Native FASTA/FASTQ(.gz) reader: ``next_batch(batch, max_bases, max_reads)`` fills a
-    ``Batch`` and returns the number of records (0 at end of input)."""
+    """Native FASTA/FASTQ(.gz) or BAM reader: ``next_batch(batch, max_bases, max_reads)`` fills a
+    ``Batch`` and returns the number of records (0 at end of input).  A name ending in ``.bam`` is read as unaligned BAM."""
 
     def __init__(self, filename: str, packing: bool = False, borrowing: bool = False, device: Optional[int] = None):
-        """``device``: BGZF input is inflated on that GPU (``tbk_fastx_set_device``: what ``classify-by-kmers`` does by itself),
+        """``device``: BGZF input is inflated on that GPU, and BAM records are turned into FASTQ text there (``tbk_fastx_set_device``: what ``classify-by-kmers`` does by itself),
         and with ``TBK_GZIP_INFLATE=gpu`` an ordinary gzip file as well (``gzip_stats``); None: on the host's threads.
         ``inflates_on_device`` says which it is."""
         import ctypes as C
@@ -323,11 +336,25 @@ class BatchReader:
             lib.tbk_fastx_gzip_stats(self._h, out)
         return dict(zip(("windows", "guessed", "accepted", "redecoded", "handed_back", "most_accepted"), (int(v) for v in out)))
 
+    def bam_counts(self) -> Optional[Tuple[int, int]]:
+        """(records seen so far, of them skipped) of a reader whose file is BAM; None for any other."""
+        import ctypes as C
+
+        from ._lib import lib
+
+        out = (C.c_uint64 * 2)()
+        if not self._h or not lib.tbk_fastx_bam_counts(self._h, out):
+            return None
+        return int(out[0]), int(out[1])
+
     def __enter__(self):
         return self
 
     def __exit__(self, *exc):
         self.close()
+
+
+NativeReader = BatchReader
 
 
 class BinWriter:
@@ -419,6 +446,38 @@ def bgzf_inflate_device(data: bytes, device: int = 0) -> bytes:
     buf = C.create_string_buffer(n.value)
     check(lib.tbk_bgzf_inflate_device(device, data, len(data), buf, n.value, C.byref(n)))
     return C.string_at(C.addressof(buf), n.value)
+
+
+def _bam_fastq(call, records: bytes, offsets, skip_flags: int):
+    import ctypes as C
+
+    from ._lib import check
+
+    n = len(offsets)
+    offs = (C.c_uint64 * max(1, n))(*offsets)
+    need, written, skipped = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    status = call(records, len(records), offs, n, skip_flags, None, 0, C.byref(need), C.byref(written), C.byref(skipped))
+    if need.value == 0:
+        check(status)
+        return b"", written.value, skipped.value
+    buf = C.create_string_buffer(need.value)
+    check(call(records, len(records), offs, n, skip_flags, buf, need.value, C.byref(need), C.byref(written), C.byref(skipped)))
+    return C.string_at(C.addressof(buf), need.value), written.value, skipped.value
+
+
+def bam_fastq_device(records: bytes, offsets, skip_flags: int = 0x900, device: int = 0):
+    """(FASTQ text, records written, records skipped) of a run of whole BAM records (bytes; ``offsets``: where each begins),
+    made on the GPU (``tbk_bam_fastq_device``: the reader's BAM kernels by themselves)."""
+    from ._lib import lib
+
+    return _bam_fastq(lambda *a: lib.tbk_bam_fastq_device(device, *a), records, offsets, skip_flags)
+
+
+def bam_fastq_host(records: bytes, offsets, skip_flags: int = 0x900):
+    """The same by the host's transcoder (``tbk_bam_fastq``)."""
+    from ._lib import lib
+
+    return _bam_fastq(lib.tbk_bam_fastq, records, offsets, skip_flags)
 
 
 def _gzip_inflate(call, data: bytes) -> bytes:
