@@ -49,7 +49,8 @@ typedef enum tbk_status {
     TBK_ERR_NO_DEVICE = -4, /* no usable HIP device                                         */
     TBK_ERR_HIP = -5,       /* a HIP runtime call failed                                    */
     TBK_ERR_NOMEM = -6,
-    TBK_ERR_STATE = -7      /* call sequence error (wait without submit, ...)               */
+    TBK_ERR_STATE = -7,     /* call sequence error (wait without submit, ...)               */
+    TBK_ERR_INTERNAL = -8   /* the library found its own state inconsistent (never the caller's doing) */
 } tbk_status;
 
 typedef struct tbk_table tbk_table;           /* one k-mer list resident in HBM           */
@@ -366,6 +367,8 @@ typedef struct tbk_run_stats {
     double read_s, gpu_wait_s, write_s, total_s;  /* busy seconds of the reader / waiting for tickets / of the writer; wall */
     int32_t gzip_encoder, reserved_;              /* who coded the bins' gzip members: 0 nobody (plain bins), 1 the host, 2 the device */
 } tbk_run_stats;
+/* gzip_output = 2: BAM bins ("BAM output" below) - the input must be BAM (TBK_ERR_INVALID otherwise), out_a/out_b/out_u name BAM
+ * files, and tbk_run_stats.gzip_encoder says who coded their bgzf blocks, as for gzip. */
 int tbk_classify_file(tbk_pipeline *p, const char *reads_path, uint64_t num_kmers_a, uint64_t num_kmers_b, const char *out_a,
                       const char *out_b, const char *out_u, int gzip_output, int gzip_level, int tsv_fd, uint64_t batch_bases,
                       uint64_t batch_reads, tbk_run_stats *stats);
@@ -547,6 +550,52 @@ int tbk_gzip_inflate_bench_device(int device, const uint8_t *data, uint64_t size
  * *boundary_bit - on by a second one that is told nothing but the bit: the text of both, in dst. */
 int tbk_inflate_resume_at_bit(const uint8_t *data, uint64_t size, uint64_t stop_bit, uint8_t *dst, uint64_t cap, uint64_t *text_len,
                               uint64_t *boundary_bit);
+/* ---- BAM output: BAM bins from BAM input, records kept whole ----------------------------------------------------------------------------
+ * With BAM input and BAM output each of the three bins is a BAM file (the reference has no such mode: an extension, opt-in):
+ *   header   the input's header bytes verbatim, "BAM\1" through the last reference entry; no @PG line is added;
+ *   records  for every read of the TSV its input record verbatim - block_size and all the bytes that follow, tags included, flag
+ *            untouched; a reverse-strand record is NOT reverse-complemented here - in the bin the read was sorted into, in input order;
+ *   skipped  records the reader skips (flag & 0x900, l_seq == 0) are in no bin, as they are in no FASTQ bin; tbk_fastx_bam_counts counts them;
+ *   end      the 28-byte bgzf end-of-file marker;  a bin with no reads is header plus marker.
+ * The container is bgzf: every block a gzip member 1f 8b 08 04, mtime 0, xfl 0, os ff, xlen 6, the BC subfield 02 00 and BSIZE = the
+ * block's bytes - 1, a raw deflate stream, CRC-32 and ISIZE; at most 65280 bytes of payload and 65536 bytes in all.  The header may
+ * span several blocks, records straddle blocks freely.  The decompressed bytes are specified, the container bytes are not.
+ *
+ * Reader.  tbk_fastx_set_keep_records (before the first read; TBK_ERR_INVALID when the file is not BAM): every batch then carries,
+ * beside its text arrays, its reads' records back to back - tbk_fastx_batch_records, rec_off with n_reads + 1 entries; it returns NULL
+ * (and sets both to NULL) for a batch that carries none.  A window's chunk of text owns the window's record bytes and where every
+ * WRITTEN record lies; a chunk's text is whole records, so the k-th record parsed from it is its k-th written record, and the batch
+ * filler takes them in that order.  Each read is checked against its record (name, number of bases), and none may be left over at
+ * the end of the input: a difference is TBK_ERR_INTERNAL, never a silent shift.  With the option off nothing more is kept or copied.
+ * tbk_fastx_bam_header: the header's bytes (the reader's, valid until it is closed), at the latest once the first batch has been read -
+ * called before, it starts the reader's worker and waits for the header.
+ *
+ * Encoder.  tbk_bgzf_members_device: data[0 .. size) as bgzf blocks of 65280 bytes of payload (the last one shorter), coded on `device`
+ * (csrc/tbk_gdeflate.hip in its bgzf mode), no BAM header and no marker; *n_members blocks in *need bytes of dst - TBK_ERR_NOMEM with
+ * *need set when cap is short.  hints: a non-decreasing list of offsets into data (duplicates allowed; one beyond size: TBK_ERR_INVALID)
+ * where the kind of the bytes changes.  A deflate block ends at the first hint in (8192, 16384] bytes from its start, else at 16384,
+ * and always at the member's end; without hints the cuts are fixed.  (Packed seq, qual and tag arrays each want a code of their own,
+ * as bases and qualities do in text.)  Each block is coded by itself or stored, so that a member of 8 blocks fits 65536 bytes whatever
+ * its bytes are.  tbk_bgzf_members: the same contract and cut rule on the host (tbk_deflate.cpp's coder per block with the stored
+ * fallback; zlib under TBK_GZIP_ENCODER=zlib), what the writer runs without a device.  tbk_bgzf_members_bench_device: the bgzf mode
+ * timed as tbk_gzip_bench_device times the gzip mode (data in pinned memory).
+ *
+ * Writer.  tbk_bin_writer_open_bam codes the header into each file at once, on the host.  tbk_bin_writer_write then appends the reads'
+ * records (TBK_ERR_STATE for a batch that carries none) and collects four hints per record: start of seq, of qual, of the tags, the
+ * record's end.  Pieces are 65280 bytes; tbk_bin_writer_close codes the remainder and writes the marker.  tbk_bin_writer_use_device as
+ * for gzip, except that the host's coder stays when the device's cannot be set up (tbk_bin_writer_encoder says which). */
+int tbk_fastx_set_keep_records(tbk_fastx_reader *r, int on);
+const uint8_t *tbk_fastx_batch_records(const tbk_fastx_batch *b, const uint8_t **records, const uint64_t **rec_off);
+int tbk_fastx_bam_header(tbk_fastx_reader *r, const uint8_t **ptr, uint64_t *len);
+int tbk_bgzf_members_device(int device, const uint8_t *data, uint64_t size, const uint64_t *hints, uint64_t n_hints, uint8_t *dst, uint64_t cap, uint64_t *need,
+                            uint64_t *n_members);
+int tbk_bgzf_members(const uint8_t *data, uint64_t size, const uint64_t *hints, uint64_t n_hints, uint8_t *dst, uint64_t cap, uint64_t *need, uint64_t *n_members);
+int tbk_bgzf_members_threads_(const uint8_t *data, uint64_t size, const uint64_t *hints, uint64_t n_hints, uint8_t *dst, uint64_t cap, uint64_t *need, uint64_t *n_members,
+                              int threads);
+int tbk_bgzf_members_bench_device(int device, const uint8_t *data, uint64_t size, const uint64_t *hints, uint64_t n_hints, int reps, double *pipelined_s, double *kernels_s,
+                                  uint64_t *out_bytes);
+int tbk_bin_writer_open_bam(const char *path_a, const char *path_b, const char *path_u, const uint8_t *header, uint64_t header_len, int level, int threads,
+                            tbk_bin_writer **out);
 int tbk_bin_writer_encoder(const tbk_bin_writer *w);
 int tbk_bin_writer_write(tbk_bin_writer *w, const tbk_fastx_batch *b, const char *bins);
 int tbk_bin_writer_close(tbk_bin_writer *w);

@@ -19,6 +19,7 @@ TBK_ERR_NO_DEVICE = -4
 TBK_ERR_HIP = -5
 TBK_ERR_NOMEM = -6
 TBK_ERR_STATE = -7
+TBK_ERR_INTERNAL = -8
 
 
 class TbkError(RuntimeError):
@@ -306,6 +307,17 @@ if hasattr(lib, "tbk_gzip_members_device"):
         _sig("tbk_bam_fastq", C.c_int, C.c_char_p, _u64, _u64p, _u64, C.c_uint32, C.c_char_p, _u64, _u64p, _u64p, _u64p)
         _sig("tbk_fastx_bam_counts", C.c_int, _vp, _u64p)
         _sig("tbk_bam_bench_device", C.c_int, C.c_int, C.c_char_p, _u64, _u64p, _u64, C.c_uint32, C.c_int, _dp, _dp, _u64p)
+    if hasattr(lib, "tbk_bgzf_members_device"):  # BAM bins (include/tbk.h "BAM output")
+        _u8pp = C.POINTER(C.c_void_p)
+        _sig("tbk_fastx_set_keep_records", C.c_int, _vp, C.c_int)
+        _sig("tbk_fastx_batch_records", C.c_void_p, _vp, _u8pp, _u8pp)
+        _sig("tbk_fastx_bam_header", C.c_int, _vp, _u8pp, _u64p)
+        _sig("tbk_bgzf_members_device", C.c_int, C.c_int, C.c_char_p, _u64, _u64p, _u64, C.c_char_p, _u64, _u64p, _u64p)
+        _sig("tbk_bgzf_members_tagged_device_", C.c_int, C.c_int, C.c_char_p, _u64, _u64p, _u64, _i32p, C.c_char_p, _u64, _u64p, _u64p, _i32p, _u64p)
+        _sig("tbk_bgzf_members", C.c_int, C.c_char_p, _u64, _u64p, _u64, C.c_char_p, _u64, _u64p, _u64p)
+        _sig("tbk_bgzf_members_threads_", C.c_int, C.c_char_p, _u64, _u64p, _u64, C.c_char_p, _u64, _u64p, _u64p, C.c_int)
+        _sig("tbk_bgzf_members_bench_device", C.c_int, C.c_int, _vp, _u64, _u64p, _u64, C.c_int, _dp, _dp, _u64p)
+        _sig("tbk_bin_writer_open_bam", C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _u64, C.c_int, C.c_int, C.POINTER(_vp))
     if hasattr(lib, "tbk_bgzf_bench_device"):
         _sig("tbk_bgzf_bench_device", C.c_int, C.c_int, C.c_char_p, _u64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _u64p)
     if hasattr(lib, "tbk_gzip_inflate_device"):

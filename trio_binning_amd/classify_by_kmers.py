@@ -110,6 +110,11 @@ def _parser(kmer_list_type) -> argparse.ArgumentParser:
     parser.add_argument("--unclassified-out-prefix", default="unclassified", help="prefix for unclassified output file")
     parser.add_argument("--no-gzip-output", action="store_true", default=False, help="don't gzip the output")
     parser.add_argument(
+        "--bam-output", action="store_true", default=False,
+        help="BAM input only: write the bins as BAM files (<prefix>.bam) that hold every read's input record whole - tags, flags "
+             "and the header as they came - instead of FASTQ text",
+    )
+    parser.add_argument(
         "--compress", action="store_true", default=False,
         help="k-mer lists made by find-unique-kmers --compress: every run of equal bases of a read is written once before it is "
              "probed (the bins still hold the reads as they came). Count databases say by themselves which space they are in",
@@ -241,6 +246,11 @@ def parse_args():
 def _check_kmer_arguments(parser, args, prog: str = "classify-by-kmers") -> bool:
     """What the two k-mer arguments name - True: two count databases, False: two text lists - and every refusal of the
     options beside them that needs no file opened (shared with phase_blocks)."""
+    if getattr(args, "bam_output", False):
+        if not args.reads.endswith(".bam"):
+            parser.error("--bam-output keeps BAM records whole: the reads must be a .bam file, not {}".format(args.reads))
+        if args.no_gzip_output:
+            parser.error("--bam-output and --no-gzip-output exclude each other: BAM bins are bgzf-compressed")
     is_db = [fu.is_database_path(args.haplotype_a_kmers), fu.is_database_path(args.haplotype_b_kmers)]
     if is_db[0] != is_db[1]:
         sys.exit(prog + ": {} is a {} and {} is a {}: give two k-mer lists or two count databases (*{})".format(
@@ -320,8 +330,19 @@ def classify_compressed(args, num_a: int, num_b: int) -> dict:
     device = classifier.device
     print("Classifying in homopolymer-compressed space: the reads are compressed on device {} before they are probed.".format(device), file=sys.stderr)
     gzip_output = not args.no_gzip_output
-    writer = seq.BinWriter(args.haplotype_a_out_prefix, args.haplotype_b_out_prefix, args.unclassified_out_prefix, output_extension(args.reads),
-                           gzip_output, int(os.environ.get("TBK_GZIP_LEVEL", "-1")), device=device if gzip_output else None)
+    reader = None
+    if args.bam_output:  # (BAM bins begin with the input's header: the reader comes first)
+        reader = seq.BatchReader(args.reads, keep_records=True)
+        try:
+            writer = seq.BinWriter(args.haplotype_a_out_prefix, args.haplotype_b_out_prefix, args.unclassified_out_prefix, ".bam", True,
+                                   int(os.environ.get("TBK_GZIP_LEVEL", "-1")), device=device, bam_header=reader.bam_header())
+        except BaseException:
+            reader.close()
+            classifier.close()
+            raise
+    else:
+        writer = seq.BinWriter(args.haplotype_a_out_prefix, args.haplotype_b_out_prefix, args.unclassified_out_prefix, output_extension(args.reads),
+                               gzip_output, int(os.environ.get("TBK_GZIP_LEVEL", "-1")), device=device if gzip_output else None)
     batches = [seq.Batch(), seq.Batch()]
     sessions = [kmers.HomopolymerCompressor(device), kmers.HomopolymerCompressor(device)]
     out = sys.stdout
@@ -337,7 +358,7 @@ def classify_compressed(args, num_a: int, num_b: int) -> dict:
         spent["write_s"] += time.perf_counter() - t1
 
     try:
-        with seq.BatchReader(args.reads) as reader:
+        with (reader if reader is not None else seq.BatchReader(args.reads)) as reader:
             pending, turn = None, 0
             while True:
                 batch, session = batches[turn], sessions[turn]
@@ -400,8 +421,11 @@ def main():
     # packed for the link on the way), this thread feeding the device(s) and taking the batches back in
     # input order, a writer scoring, binning, writing the three bins and the TSV.  Python only names the
     # files; the TSV goes to the process's stdout descriptor.
-    names = seq.output_names(args.haplotype_a_out_prefix, args.haplotype_b_out_prefix, args.unclassified_out_prefix,
-                             output_extension(args.reads), not args.no_gzip_output)
+    if args.bam_output:
+        names = seq.output_names(args.haplotype_a_out_prefix, args.haplotype_b_out_prefix, args.unclassified_out_prefix, ".bam", False)
+    else:
+        names = seq.output_names(args.haplotype_a_out_prefix, args.haplotype_b_out_prefix, args.unclassified_out_prefix,
+                                 output_extension(args.reads), not args.no_gzip_output)
     # zlib level of the gzip members when zlib is asked for (TBK_GZIP_ENCODER): default 6; the reference's
     # gzip.open uses 9, which only changes the container bytes, never the decompressed bins
     level = int(os.environ.get("TBK_GZIP_LEVEL", "-1"))
@@ -415,7 +439,7 @@ def main():
         spool = tempfile.TemporaryFile()
         tsv_fd = spool.fileno()
     try:
-        stats = classifier.classify_file(args.reads, num_a, num_b, names, not args.no_gzip_output, level, tsv_fd, _BATCH_BASES, _BATCH_READS)
+        stats = classifier.classify_file(args.reads, num_a, num_b, names, 2 if args.bam_output else not args.no_gzip_output, level, tsv_fd, _BATCH_BASES, _BATCH_READS)
     finally:
         if spool is not None:
             spool.seek(0)

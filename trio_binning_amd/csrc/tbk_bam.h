@@ -220,6 +220,30 @@ static inline uint64_t tbk_bam_fastq_shares(const uint8_t *records, const uint64
     return TBK_BAM_NO_BAD;
 }
 
+// ---- records kept whole (include/tbk.h "BAM output") -----------------------------------------------------------------------
+// Of the records tbk_bam_index handed out and the transcoder accepted: where the WRITTEN ones (not skipped) begin and how long
+// they are, block_size field included, in file order - the k-th entry is the record behind the k-th record of the window's text.
+struct TbkBamSlice { uint64_t off; uint32_t len; };
+static inline void tbk_bam_written(const uint8_t *records, const uint64_t *offsets, uint64_t n, uint32_t skip_flags, std::vector<TbkBamSlice> &out) {
+    out.clear();
+    for (uint64_t i = 0; i < n; i++) {
+        const uint8_t *rec = records + offsets[i];
+        const uint32_t l_seq = tbk_bam_u32(rec + 20), flag = tbk_bam_u16(rec + 18);
+        if (l_seq == 0 || (flag & skip_flags)) continue;
+        out.push_back(TbkBamSlice{offsets[i], 4u + tbk_bam_u32(rec)});
+    }
+}
+// The four places of a whole, accepted record where the kind of its bytes changes - start of seq, of qual, of the tags, the
+// record's end - as offsets from `base` (where the record lies in a bin's bytes): the bgzf coder's cut hints.
+static inline void tbk_bam_hints(const uint8_t *rec, uint32_t len, uint64_t base, uint64_t out[4]) {
+    const uint32_t l_seq = tbk_bam_u32(rec + 20);
+    const uint64_t seq_at = 36ull + rec[12] + 4ull * tbk_bam_u16(rec + 16), qual_at = seq_at + ((uint64_t)l_seq + 1) / 2, tags_at = qual_at + l_seq;
+    out[0] = base + (seq_at < len ? seq_at : len);
+    out[1] = base + (qual_at < len ? qual_at : len);
+    out[2] = base + (tags_at < len ? tags_at : len);
+    out[3] = base + len;
+}
+
 // ---- the device side (tbk_bam.hip): a transcoder that keeps its buffers from window to window ------------------------------
 // tbk_bamdev_measure copies a window (records, the offsets tbk_bam_index gave) to the device, measures and scans it: *text_len,
 // the counts, *bad = TBK_BAM_NO_BAD or ((first_record + index of the first refused record) << 8 | reason).  tbk_bamdev_write

@@ -14,12 +14,15 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <thread>
 #include <vector>
 
 uint32_t tbk_crc32(uint32_t crc, const uint8_t *p, size_t n);  // tbk_crc.cpp
+extern "C" void tbk_set_error_(int code, const char *msg) __attribute__((weak));  // tbk_host.cpp (absent from a stand-alone build of this file)
 
 namespace {
 
@@ -259,7 +262,134 @@ void encode_block(BitWriter &bw, const uint8_t *src, size_t n, bool final) {
     bw.put(code[256], len[256]);
 }
 
+// ---- bgzf members (include/tbk.h "BAM output") ---------------------------------------------------------------------
+// A member is a piece of at most 65280 bytes, coded block by block the way csrc/tbk_gdeflate.hip codes it: every block
+// by itself - its dynamic-Huffman code, the end-of-block code and an empty stored block that brings the stream back to a
+// byte boundary - or, when that would not be smaller, as a stored block; the member ends with a final empty stored block.
+// The size bound: a block other than a member's last is longer than BGZF_LEAST bytes, so a member has at most
+// (BGZF_PAYLOAD - 1) / (BGZF_LEAST + 1) + 1 = 8 blocks; a block takes at most its bytes + 5 (the stored form: one header
+// byte, LEN, NLEN; the coded form with its 4-5 sync bytes is taken only when it is smaller); the final empty block is 5
+// bytes and the framing 18 + 8.  65280 + 8 * 5 + 5 + 26 = 65351 <= 65536: BSIZE fits whatever the bytes are.
+constexpr size_t BGZF_PAYLOAD = 65280, BGZF_LEAST = 8192, BGZF_MOST = 16384, BGZF_FRAME = 26;
+constexpr size_t BGZF_MAX_BLOCKS = (BGZF_PAYLOAD - 1) / (BGZF_LEAST + 1) + 1;
+static_assert(BGZF_PAYLOAD + BGZF_MAX_BLOCKS * 5 + 5 + BGZF_FRAME <= 65536, "a bgzf member of stored blocks must fit 64 KiB: raise BGZF_LEAST");
+
+// where the block that starts at `at` (a position in the job's bytes) ends: at the first cut hint in (at + 8192, at + 16384],
+// else 16384 bytes on, and at the member's end (`end`) at the latest
+inline uint64_t bgzf_block_end(uint64_t at, uint64_t end, const uint64_t *hints, uint64_t n_hints) {
+    const uint64_t m = end - at;
+    if (m <= BGZF_LEAST) return end;
+    const uint64_t most = at + std::min<uint64_t>(m, BGZF_MOST);
+    const uint64_t *h = std::upper_bound(hints, hints + n_hints, at + BGZF_LEAST);
+    return h != hints + n_hints && *h <= most ? *h : most;
+}
+
+void bgzf_stored(std::vector<char> &out, const uint8_t *src, size_t n, bool final) {
+    const unsigned char head[5] = {(unsigned char)(final ? 1 : 0), (unsigned char)(n & 0xFF), (unsigned char)(n >> 8), (unsigned char)(~n & 0xFF), (unsigned char)((~n >> 8) & 0xFF)};
+    out.insert(out.end(), (const char *)head, (const char *)head + 5);
+    out.insert(out.end(), (const char *)src, (const char *)src + n);
+}
+
 }  // namespace
+
+// One bgzf member for the job's bytes [at, at + n), n <= 65280 (job: the job's first byte; hints: cut hints as offsets into the
+// job).  level 0: stored; zlib: through zlib's deflate at `level`, stored when that does not fit.  Appends to `out`.
+bool tbk_bgzf_member_(const uint8_t *job, uint64_t at, size_t n, const uint64_t *hints, uint64_t n_hints, int level, bool zlib, std::vector<char> &out) {
+    if (n > BGZF_PAYLOAD) return false;
+    const uint8_t *src = job + at;
+    const size_t start = out.size();
+    static const unsigned char head[18] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0, 0};
+    out.insert(out.end(), (const char *)head, (const char *)head + 18);
+    bool done = false;
+    if (level == 0) { bgzf_stored(out, src, n, true); done = true; }
+    if (!done && zlib) {
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (deflateInit2(&zs, level < 0 ? 6 : level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) == Z_OK) {
+            const size_t room = 65536 - BGZF_FRAME;
+            out.resize(start + 18 + room);
+            zs.next_in = (Bytef *)src; zs.avail_in = (uInt)n;
+            zs.next_out = (Bytef *)out.data() + start + 18; zs.avail_out = (uInt)room;
+            const int rc = deflate(&zs, Z_FINISH);
+            const size_t made = room - zs.avail_out;
+            deflateEnd(&zs);
+            out.resize(start + 18 + (rc == Z_STREAM_END ? made : 0));
+            done = rc == Z_STREAM_END;
+        }
+        if (!done) { bgzf_stored(out, src, n, true); done = true; }
+    }
+    if (!done) {
+        static thread_local std::vector<char> tmp;
+        for (uint64_t off = at; off < at + n;) {
+            const uint64_t end = bgzf_block_end(off, at + n, hints, n_hints);
+            const size_t m = (size_t)(end - off);
+            tmp.clear();
+            BitWriter bw(tmp);
+            encode_block(bw, job + off, m, false);
+            bw.ensure(32);
+            bw.put(0u, 3);                          // an empty stored block, not the last: BFINAL = 0, BTYPE = 00,
+            if (bw.n) bw.put(0u, 8 - bw.n);         // zero bits up to the byte,
+            bw.put(0u, 16); bw.put(0xFFFFu, 16);    // LEN = 0, NLEN = FFFF
+            bw.finish();
+            if (tmp.size() >= m + 5) bgzf_stored(out, job + off, m, false);
+            else out.insert(out.end(), tmp.begin(), tmp.end());
+            off = end;
+        }
+        static const unsigned char last[5] = {1, 0, 0, 0xff, 0xff};
+        out.insert(out.end(), (const char *)last, (const char *)last + 5);
+    }
+    const uint32_t tail[2] = {tbk_crc32(0u, src, n), (uint32_t)n};
+    out.insert(out.end(), (const char *)tail, (const char *)tail + 8);
+    const size_t total = out.size() - start;
+    if (total > 65536) return false;
+    out[start + 16] = (char)((total - 1) & 0xFF);
+    out[start + 17] = (char)((total - 1) >> 8);
+    return true;
+}
+
+// non-decreasing, none beyond `size`
+bool tbk_bgzf_hints_ok_(const uint64_t *hints, uint64_t n_hints, uint64_t size) {
+    for (uint64_t i = 0; i < n_hints; i++)
+        if (hints[i] > size || (i && hints[i] < hints[i - 1])) return false;
+    return true;
+}
+
+// C-ABI (include/tbk.h): data[0 .. size) as bgzf members of 65280 bytes (the last one shorter), on `threads` threads
+extern "C" int tbk_bgzf_members_threads_(const uint8_t *data, uint64_t size, const uint64_t *hints, uint64_t n_hints, uint8_t *dst, uint64_t cap, uint64_t *need,
+                                         uint64_t *n_members, int threads) {
+    if ((!data && size) || (!hints && n_hints) || !need || !n_members) { if (tbk_set_error_) tbk_set_error_(-1, "tbk_bgzf_members: NULL argument"); return -1; }  // TBK_ERR_INVALID
+    if (!tbk_bgzf_hints_ok_(hints, n_hints, size)) { if (tbk_set_error_) tbk_set_error_(-1, "tbk_bgzf_members: cut hints must not decrease nor pass the end of the bytes"); return -1; }
+    static const bool zlib = getenv("TBK_GZIP_ENCODER") && strcmp(getenv("TBK_GZIP_ENCODER"), "zlib") == 0;
+    const uint64_t nm = (size + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD;
+    std::vector<std::vector<char>> outs((size_t)nm);
+    std::atomic<uint64_t> next{0};
+    std::atomic<bool> ok{true};
+    auto work = [&]() {
+        for (uint64_t i; (i = next.fetch_add(1)) < nm;) {
+            const uint64_t at = i * BGZF_PAYLOAD;
+            if (!tbk_bgzf_member_(data, at, (size_t)std::min<uint64_t>(BGZF_PAYLOAD, size - at), hints, n_hints, 6, zlib, outs[(size_t)i])) ok.store(false);
+        }
+    };
+    const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(threads, 1), nm));
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt; t++) pool.emplace_back(work);
+    work();
+    for (std::thread &t : pool) t.join();
+    if (!ok.load()) return -2;  // TBK_ERR_IO (cannot happen: the bound above)
+    uint64_t used = 0;
+    for (const std::vector<char> &o : outs) used += o.size();
+    *need = used;
+    *n_members = nm;
+    if (used > cap || (!dst && used)) { if (tbk_set_error_) tbk_set_error_(-6, "tbk_bgzf_members: dst too small"); return -6; }  // TBK_ERR_NOMEM: *need says what is needed
+    uint64_t w = 0;
+    for (const std::vector<char> &o : outs) { memcpy(dst + w, o.data(), o.size()); w += o.size(); }
+    return 0;
+}
+extern "C" int tbk_bgzf_members(const uint8_t *data, uint64_t size, const uint64_t *hints, uint64_t n_hints, uint8_t *dst, uint64_t cap, uint64_t *need,
+                                uint64_t *n_members) {
+    const unsigned hc = std::thread::hardware_concurrency();
+    return tbk_bgzf_members_threads_(data, size, hints, n_hints, dst, cap, need, n_members, (int)std::min(16u, std::max(1u, hc)));
+}
 
 // One gzip member holding src[0..n), entropy-coded only.  Appends to `out` (which is cleared first).
 bool tbk_gzip_member_literal(const char *src, size_t n, std::vector<char> &out) {

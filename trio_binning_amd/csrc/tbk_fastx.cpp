@@ -126,6 +126,10 @@ struct WindowHold {
     ~WindowHold() { { std::lock_guard<std::mutex> lk(w->mu); w->slot_free[slot] = true; } w->cv.notify_all(); }
 };
 
+// BAM input with records kept (tbk_fastx_set_keep_records): beside its text a chunk of bam_loop owns the window's record bytes and
+// where each WRITTEN record lies in them; `next` is the first one no batch has taken yet.
+struct BamRecChunk { std::vector<uint8_t> bytes; std::vector<TbkBamSlice> recs; size_t next = 0; };
+
 struct LineSource {
     int fd = -1;
     bool gz = false;
@@ -167,6 +171,10 @@ struct LineSource {
     bool bam = false;
     int err_code = TBK_ERR_IO;
     std::atomic<uint64_t> bam_records{0}, bam_skipped{0};   // records seen (the number of the next one), records skipped
+    bool keep_records = false;                              // chunks carry their records; refill_fast queues them here for the batch filler
+    std::deque<std::shared_ptr<BamRecChunk>> rec_fifo;
+    std::vector<uint8_t> bam_header;                        // the header's bytes, magic through the last reference (set under `mu`, once)
+    bool bam_header_set = false;
     // BGZF blocks inflated on the GPU (tbk_fastx_set_device; csrc/tbk_gdeflate.hip, second half): one wave per block, windows of
     // 96 MB of the file four deep.  -1: on the host's threads.
     int gpu_device = -1;
@@ -253,7 +261,7 @@ struct LineSource {
     // A chunk owns the buffer it was inflated into: [ up to 32 KiB of the text before it | new text ].
     // (ext / slot: the text lies in a pinned output buffer of the GPU inflater instead of `data`; the slot is the inflater's again once
     // the parser has taken the text over)
-    struct Chunk { std::vector<uint8_t> data; size_t off = 0, len = 0; bool last = false, fallback = false; std::string err; uint8_t *ext = nullptr; size_t room = 0; std::shared_ptr<WindowHold> hold; };
+    struct Chunk { std::vector<uint8_t> data; size_t off = 0, len = 0; bool last = false, fallback = false; std::string err; uint8_t *ext = nullptr; size_t room = 0; std::shared_ptr<WindowHold> hold; std::shared_ptr<BamRecChunk> recs; };
     std::thread worker;
     std::mutex mu;
     std::condition_variable cv;
@@ -577,7 +585,11 @@ struct LineSource {
             if (in_header) {
                 uint64_t len = 0;
                 if (tbk_bam_header_len(cur, cur_size, &len) != 0) { fail_with(TBK_ERR_FORMAT, "not a BAM file: its text does not begin with a BAM header"); return; }
-                if (len) { in_header = false; cur_pos = (size_t)len; }
+                if (len) {
+                    in_header = false; cur_pos = (size_t)len;
+                    { std::lock_guard<std::mutex> lk(mu); bam_header.assign(cur, cur + len); bam_header_set = true; }
+                    cv.notify_all();
+                }
             }
             while (!in_header) {
                 { std::lock_guard<std::mutex> lk(mu); if (stop) return; }
@@ -604,6 +616,14 @@ struct LineSource {
                 bam_records += n; bam_skipped += skipped;
                 cur_pos += (size_t)consumed;
                 if (why != TBK_BAM_OK) { refuse(bam_records, why); return; }
+                if (text_len && keep_records) {
+                    // the records behind the text: the k-th record the parser finds in this chunk is the k-th of these
+                    auto rc = std::make_shared<BamRecChunk>();
+                    tbk_bam_written(recs, offsets.data(), n, TBK_BAM_SKIP_DEFAULT_, rc->recs);
+                    if (rc->recs.size() != n - skipped) { fail_with(TBK_ERR_INTERNAL, "BAM: the records kept and the records written differ in number"); return; }
+                    rc->bytes.assign(recs, recs + consumed);
+                    c.recs = std::move(rc);
+                }
                 if (text_len) { c.off = 0; c.len = (size_t)text_len; push(std::move(c)); }
                 if (n < CAP) break;   // (the walk stopped for want of bytes, not of room)
             }
@@ -890,7 +910,7 @@ struct LineSource {
     // own decoder: returns like refill()
     bool refill_fast() {
         if (!worker_err.empty()) { err = worker_err; return false; }   // (the worker ended with it: said again, not waited for)
-        if (!started) { started = true; worker = std::thread([this] { if (bam) bam_loop(); else if (bgzf && gpu_device >= 0 && map) bgzf_loop_gpu(); else if (bgzf) bgzf_loop(); else if (gzip_gpu) gzip_loop_gpu(); else if (guessing()) pinflate_loop(); else inflate_loop(); }); }
+        start_worker();
         Chunk c;
         {
             const auto t0 = std::chrono::steady_clock::now();
@@ -902,6 +922,23 @@ struct LineSource {
             cv.notify_all();
         }
         if (!c.err.empty()) { worker_err = err = c.err; return false; }
+        if (c.recs) rec_fifo.push_back(std::move(c.recs));
+        return take_chunk(c);
+    }
+    void start_worker() {
+        if (!started) { started = true; worker = std::thread([this] { if (bam) bam_loop(); else if (bgzf && gpu_device >= 0 && map) bgzf_loop_gpu(); else if (bgzf) bgzf_loop(); else if (gzip_gpu) gzip_loop_gpu(); else if (guessing()) pinflate_loop(); else inflate_loop(); }); }
+    }
+    // BAM input: the header's bytes once the worker has read them (it is started if need be); false when it ended without (its error: the first chunk's)
+    bool wait_bam_header() {
+        if (!worker_err.empty()) { err = worker_err; return false; }
+        start_worker();
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return bam_header_set || !ready.empty(); });
+        if (bam_header_set) return true;
+        err = ready.front().err.empty() ? std::string("BAM: no header") : ready.front().err;
+        return false;
+    }
+    bool take_chunk(Chunk &c) {
         if (c.ext && c.hold && end - pos <= c.room) {
             // a window of the GPU inflater, and room in front of it for what is left of the text at hand: parsed where it lies
             const size_t left = end - pos;
@@ -1253,6 +1290,10 @@ struct tbk_fastx_batch {
     std::vector<FastqRec> recs;
     std::shared_ptr<void> hold;  // keeps `text` where it is while this batch refers to it: the reader's mapping of the file, or a window of the GPU inflater
     bool text_mapped = false;    // `text` is the file's mapping (its pages are let go when the batch is refilled)
+    // BAM input with tbk_fastx_set_keep_records: the reads' input records, whole, back to back; rec_off has n_reads + 1 entries
+    bool has_records = false;
+    std::vector<uint8_t> records;
+    std::vector<uint64_t> rec_off;
 
     ~tbk_fastx_batch() {
         release();
@@ -1300,6 +1341,7 @@ struct tbk_fastx_batch {
         fused = want_packed; packed_ok = false;
         exc.clear(); exc_chunk.clear(); exc_mask.clear();
         borrowed = false; text = nullptr; recs.clear(); hold.reset(); text_mapped = false;
+        has_records = false; records.clear(); rec_off.clear();
     }
     void begin(const uint8_t *name, size_t n) {
         names.insert(names.end(), name, name + n);
@@ -1879,12 +1921,66 @@ static int finish_packing(tbk_fastx_batch *b) {
     return TBK_OK;
 }
 
+// BAM input with records kept: the batch's reads take their records off the queue the chunks left them in (refill_fast), in order.
+// Whatever path filled the batch, read i must be the record next in line - same name, same number of bases - and when the input
+// is exhausted none may be left: anything else is a shift between text and records, TBK_ERR_INTERNAL.
+static int take_records(tbk_fastx_reader *r, tbk_fastx_batch *b) {
+    std::deque<std::shared_ptr<BamRecChunk>> &fifo = r->src.rec_fifo;
+    const uint64_t n = b->n_reads();
+    b->has_records = true;
+    b->rec_off.assign(1, 0);
+    b->records.reserve((size_t)(b->n_bases + b->n_bases / 2 + 64 * n));
+    for (uint64_t i = 0; i < n; i++) {
+        while (!fifo.empty() && fifo.front()->next == fifo.front()->recs.size()) fifo.pop_front();
+        if (fifo.empty()) return ffail(TBK_ERR_INTERNAL, "BAM: read %llu of a batch has no record (the text holds more records than were kept)", (unsigned long long)i);
+        BamRecChunk &c = *fifo.front();
+        const TbkBamSlice sl = c.recs[c.next++];
+        const uint8_t *rec = c.bytes.data() + sl.off;
+        const uint64_t nn = b->name_off[i + 1] - b->name_off[i], nb = b->base_off[i + 1] - b->base_off[i];
+        if ((uint64_t)rec[12] != nn + 1 || memcmp(rec + 36, b->names.data() + b->name_off[i], (size_t)nn) != 0 || (uint64_t)tbk_bam_u32(rec + 20) != nb)
+            return ffail(TBK_ERR_INTERNAL, "BAM: read %llu of a batch and the record kept for it differ (text and records have shifted)", (unsigned long long)i);
+        b->records.insert(b->records.end(), rec, rec + sl.len);
+        b->rec_off.push_back(b->records.size());
+    }
+    if (n == 0) {
+        while (!fifo.empty() && fifo.front()->next == fifo.front()->recs.size()) fifo.pop_front();
+        if (!fifo.empty()) return ffail(TBK_ERR_INTERNAL, "BAM: records were kept that the text does not hold");
+    }
+    return TBK_OK;
+}
+
 extern "C" int tbk_fastx_next(tbk_fastx_reader *r, tbk_fastx_batch *b, uint64_t max_bases, uint64_t max_reads) {
     if (!r || !b) return ffail(TBK_ERR_INVALID, "NULL argument");
     b->want_packed = r->packing;
-    const int rc = fastx_next_records(r, b, max_bases, max_reads);
+    int rc = fastx_next_records(r, b, max_bases, max_reads);
     if (rc) return rc;
+    if (r->src.keep_records) { rc = take_records(r, b); if (rc) return rc; }
     return finish_packing(b);
+}
+
+extern "C" int tbk_fastx_set_keep_records(tbk_fastx_reader *r, int on) {
+    if (!r) return ffail(TBK_ERR_INVALID, "NULL argument");
+    if (!r->src.bam) return ffail(TBK_ERR_INVALID, "tbk_fastx_set_keep_records: the reader's file is not BAM");
+    if (r->src.started) return ffail(TBK_ERR_STATE, "tbk_fastx_set_keep_records after the first read");
+    r->src.keep_records = on != 0;
+    return TBK_OK;
+}
+
+extern "C" const uint8_t *tbk_fastx_batch_records(const tbk_fastx_batch *b, const uint8_t **records, const uint64_t **rec_off) {
+    static const uint8_t nothing = 0;
+    const bool have = b && b->has_records;
+    if (records) *records = have ? (b->records.empty() ? &nothing : b->records.data()) : nullptr;
+    if (rec_off) *rec_off = have ? b->rec_off.data() : nullptr;
+    return have ? (b->records.empty() ? &nothing : b->records.data()) : nullptr;
+}
+
+extern "C" int tbk_fastx_bam_header(tbk_fastx_reader *r, const uint8_t **ptr, uint64_t *len) {
+    if (!r || !ptr || !len) return ffail(TBK_ERR_INVALID, "NULL argument");
+    *ptr = nullptr; *len = 0;
+    if (!r->src.bam) return ffail(TBK_ERR_INVALID, "tbk_fastx_bam_header: the reader's file is not BAM");
+    if (!r->src.wait_bam_header()) return ffail(r->src.err_code, "%s", r->src.err.c_str());
+    *ptr = r->src.bam_header.data(); *len = r->src.bam_header.size();
+    return TBK_OK;
 }
 
 extern "C" int tbk_fastx_batch_packed(const tbk_fastx_batch *b, const uint32_t **codes, const uint32_t **exc_chunk, const uint16_t **exc_mask,
@@ -2187,6 +2283,10 @@ struct tbk_bin_writer {
     IoLane lane[3];
     bool lanes_on = false;
     double gpu_submit_s = 0, gpu_crc_s = 0, gpu_text_wait_s = 0, gpu_collect_s = 0, gpu_io_wait_s = 0, fill_s = 0;
+    // BAM bins (tbk_bin_writer_open_bam; include/tbk.h "BAM output"): the bins' bytes are the reads' input records, the members bgzf
+    // blocks of 65280 bytes; hints[b]: the cut hints of bin b's pending bytes (four per record, offsets into bin[b].text)
+    bool bam = false, bam_zlib = false;
+    std::vector<uint64_t> hints[3];
 };
 
 static bool write_all(int fd, const char *p, size_t n, std::string &err) {
@@ -2223,6 +2323,8 @@ static int deflate_strategy(const char *src, size_t n) {
 }
 
 bool tbk_gzip_member_literal(const char *src, size_t n, std::vector<char> &out);  // tbk_deflate.cpp
+bool tbk_bgzf_member_(const uint8_t *job, uint64_t at, size_t n, const uint64_t *hints, uint64_t n_hints, int level, bool zlib, std::vector<char> &out);  // tbk_deflate.cpp
+static const unsigned char BGZF_EOF_MARKER[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 // one gzip member per chunk; concatenated members are a valid gzip file
 static bool deflate_member(const char *src, size_t n, int level, std::vector<char> &dst) {
@@ -2277,7 +2379,7 @@ static int hand_to_lanes(tbk_bin_writer *w, const std::vector<tbk_gdeflate_out> 
 // The gzip members of this flush coded on the device (tbk_gdeflate.hip).  Three jobs deep: this flush's text goes to the
 // device and is coded while the host sums the members' CRC-32s; the previous flush's members travel home; the one before
 // that is handed to the bins' writer threads.  The text buffers are free again when this returns.
-static int flush_bins_gpu(tbk_bin_writer *w, bool final, std::vector<Piece> &pieces, const size_t keep[3]) {
+static int flush_bins_gpu(tbk_bin_writer *w, bool final, std::vector<Piece> &pieces, const size_t keep[3], const std::vector<uint64_t> &job_hints) {
     std::vector<tbk_gdeflate_out> outs;
     int rc = TBK_OK;
     bool swapped = false;
@@ -2290,7 +2392,8 @@ static int flush_bins_gpu(tbk_bin_writer *w, bool final, std::vector<Piece> &pie
         std::vector<tbk_gdeflate_member> members;
         members.reserve(pieces.size());
         for (const Piece &pc : pieces) members.push_back(tbk_gdeflate_member{pc.src, pc.n, pc.bin});
-        rc = tbk_gdeflate_submit(w->gpu, members.data(), members.size());
+        rc = w->bam ? tbk_gdeflate_submit_bgzf(w->gpu, members.data(), members.size(), job_hints.data(), job_hints.size())
+                    : tbk_gdeflate_submit(w->gpu, members.data(), members.size());
         if (rc) return rc;
         w->gpu_submit_s += wall_now() - t0;
         t0 = wall_now();
@@ -2363,12 +2466,40 @@ static int flush_bins(tbk_bin_writer *w, bool final) {
         if (final && n > off) { pieces.push_back(Piece{b, f.text.data() + off, n - off, {}, true}); off = n; }
         keep[b] = n - off;
     }
-    if (w->gz && w->gpu) return flush_bins_gpu(w, final, pieces, keep);
+    // BAM bins: the hints of the bytes that leave go with them (the device's job: its members' bytes back to back, bin after bin), the rest move up
+    std::vector<uint64_t> job_hints;
+    auto shift_hints = [&]() {
+        for (int b = 0; b < 3 && w->bam; b++) {
+            const uint64_t gone = w->bin[b].text.size() - keep[b];
+            std::vector<uint64_t> &h = w->hints[b];
+            const size_t used = (size_t)(std::upper_bound(h.begin(), h.end(), gone) - h.begin());
+            h.erase(h.begin(), h.begin() + (ptrdiff_t)used);
+            for (uint64_t &v : h) v -= gone;
+        }
+    };
+    if (w->gz && w->gpu) {
+        if (w->bam) {
+            uint64_t base = 0;
+            for (int b = 0; b < 3; b++) {
+                const uint64_t gone = w->bin[b].text.size() - keep[b];
+                for (const uint64_t v : w->hints[b]) { if (v > gone) break; job_hints.push_back(base + v); }
+                base += gone;
+            }
+            shift_hints();
+        }
+        return flush_bins_gpu(w, final, pieces, keep, job_hints);
+    }
     if (w->gz && !pieces.empty()) {
         std::atomic<size_t> next{0};
         auto work = [&]() {
             for (size_t i; (i = next.fetch_add(1)) < pieces.size();) {
                 Piece &pc = pieces[i];
+                if (w->bam) {
+                    const BinFile &f = w->bin[pc.bin];
+                    pc.out.clear();
+                    pc.ok = tbk_bgzf_member_((const uint8_t *)f.text.p, (uint64_t)(pc.src - f.text.p), pc.n, w->hints[pc.bin].data(), w->hints[pc.bin].size(), w->level, w->bam_zlib, pc.out);
+                    continue;
+                }
                 // zlib's avail_in is 32-bit; chunks are far below that
                 pc.ok = deflate_member(pc.src, pc.n, w->level, pc.out);
             }
@@ -2420,6 +2551,7 @@ static int flush_bins(tbk_bin_writer *w, bool final) {
         for (std::thread &th : pool) th.join();
         if (failed_errno.load()) return ffail(TBK_ERR_IO, "write: %s", strerror(failed_errno.load()));
     }
+    shift_hints();
     for (int b = 0; b < 3; b++) {
         BinFile &f = w->bin[b];
         if (keep[b] && keep[b] != f.text.size()) memmove(f.text.data(), f.text.data() + f.text.size() - keep[b], keep[b]);
@@ -2461,6 +2593,28 @@ extern "C" int tbk_bin_writer_open(const char *path_a, const char *path_b, const
             if (c != b && have[b] && have[c] && st[b].st_dev == st[c].st_dev && st[b].st_ino == st[c].st_ino) w->bin[b].positional = false, w->bin[b].shared = true;
     *out = w;
     return TBK_OK;
+}
+
+// BAM bins (include/tbk.h "BAM output"): the three files get the input's header at once, as bgzf blocks coded here on the host;
+// the records follow with tbk_bin_writer_write, the end-of-file marker with tbk_bin_writer_close.
+extern "C" int tbk_bin_writer_open_bam(const char *path_a, const char *path_b, const char *path_u, const uint8_t *header, uint64_t header_len, int level, int threads,
+                                       tbk_bin_writer **out) {
+    if (!out || !header || header_len < 12 || memcmp(header, "BAM\1", 4) != 0) return ffail(TBK_ERR_INVALID, "tbk_bin_writer_open_bam: no BAM header");
+    int rc = tbk_bin_writer_open(path_a, path_b, path_u, 1, level, threads, out);
+    if (rc) return rc;
+    tbk_bin_writer *w = *out;
+    w->bam = true;
+    w->bam_zlib = getenv("TBK_GZIP_ENCODER") && strcmp(getenv("TBK_GZIP_ENCODER"), "zlib") == 0;
+    w->chunk = 65280;
+    std::vector<char> coded;
+    for (uint64_t at = 0; at < header_len; at += 65280)
+        if (!tbk_bgzf_member_(header, at, (size_t)std::min<uint64_t>(65280, header_len - at), nullptr, 0, w->level, w->bam_zlib, coded)) rc = ffail(TBK_ERR_IO, "deflate failed");
+    for (int b = 0; b < 3 && !rc; b++) {
+        if (!write_all(w->bin[b].fd, coded.data(), coded.size(), w->err)) rc = ffail(TBK_ERR_IO, "%s", w->err.c_str());
+        w->bin[b].file_off += coded.size();
+    }
+    if (rc) { *out = nullptr; (void)tbk_bin_writer_close(w); }
+    return rc;
 }
 
 // The bytes Read.print writes for record i (seq.py:27-31: FASTQ when the record has a non-empty quality string, else
@@ -2508,6 +2662,7 @@ static inline int record_pieces(const tbk_fastx_batch *b, size_t i, struct iovec
 extern "C" int tbk_bin_writer_write(tbk_bin_writer *w, const tbk_fastx_batch *b, const char *bins) {
     if (!w || !b || (b->n_reads() && !bins)) return ffail(TBK_ERR_INVALID, "NULL argument");
     const uint64_t n = b->n_reads();
+    if (w->bam && !b->has_records) return ffail(TBK_ERR_STATE, "tbk_bin_writer_write: BAM bins, and the batch carries no records (tbk_fastx_set_keep_records)");
     // where every record goes: its bin and its offset in that bin's pending text (one serial pass
     // over the records' lengths), then the bytes are put there by several threads
     std::vector<uint64_t> dst((size_t)n), upto((size_t)n + 1);
@@ -2519,7 +2674,12 @@ extern "C" int tbk_bin_writer_write(tbk_bin_writer *w, const tbk_fastx_batch *b,
         const size_t ns = b->base_off[i + 1] - b->base_off[i];
         const size_t nq = b->qual_off[i + 1] - b->qual_off[i];
         const bool fq = b->has_qual[i] && nq > 0;
-        const size_t len = 1 + nn + 1 + ns + 1 + (fq ? 2 + nq + 1 : 0);
+        const size_t len = w->bam ? (size_t)(b->rec_off[i + 1] - b->rec_off[i]) : 1 + nn + 1 + ns + 1 + (fq ? 2 + nq + 1 : 0);
+        if (w->bam) {
+            uint64_t h[4];
+            tbk_bam_hints(b->records.data() + b->rec_off[i], (uint32_t)len, at[which], h);
+            w->hints[which].insert(w->hints[which].end(), h, h + 4);
+        }
         dst[(size_t)i] = at[which];
         at[which] += len;
         upto[(size_t)i + 1] = upto[(size_t)i] + len;
@@ -2600,6 +2760,7 @@ extern "C" int tbk_bin_writer_write(tbk_bin_writer *w, const tbk_fastx_batch *b,
         for (size_t i = cut(t); i < last; i++) {
             const int which = bins[i] == 'A' ? 0 : bins[i] == 'B' ? 1 : 2;
             char *p = w->bin[which].text.data() + dst[i];
+            if (w->bam) { memcpy(p, b->records.data() + b->rec_off[i], (size_t)(b->rec_off[i + 1] - b->rec_off[i])); continue; }
             struct iovec pc[7];
             const int np = record_pieces(b, i, pc);
             for (int j = 0; j < np; j++) { memcpy(p, pc[j].iov_base, pc[j].iov_len); p += pc[j].iov_len; }
@@ -2628,6 +2789,7 @@ extern "C" int tbk_bin_writer_use_device(tbk_bin_writer *w, int device) {
     // another target that cannot seek is fine, a lane writes its bin in order)
     for (int b = 0; b < 3; b++) if (w->bin[b].shared) return TBK_OK;
     int rc = tbk_gdeflate_create(device, &w->gpu);
+    if (rc && w->bam) { w->gpu = nullptr; return TBK_OK; }   // (BAM bins: the host's coder stays; tbk_bin_writer_encoder says so)
     if (rc) return rc;
     for (int b = 0; b < 3; b++) { w->bin[b].text.release(); w->bin[b].text.pinned = true; w->lane[b].start(w->bin[b].fd); }
     w->lanes_on = true;
@@ -2654,7 +2816,10 @@ extern "C" int tbk_bin_writer_close(tbk_bin_writer *w) {
         tbk_gdeflate_destroy(w->gpu);
         w->gpu = nullptr;
     }
-    if (w->gz) {
+    if (w->bam) {
+        for (int b = 0; b < 3; b++)
+            if (!write_all(w->bin[b].fd, (const char *)BGZF_EOF_MARKER, sizeof BGZF_EOF_MARKER, w->err) && !rc) rc = ffail(TBK_ERR_IO, "%s", w->err.c_str());
+    } else if (w->gz) {
         // an empty bin is still a valid (empty) gzip file, as gzip.open(...).close() leaves it
         for (int b = 0; b < 3; b++) {
             struct stat st;

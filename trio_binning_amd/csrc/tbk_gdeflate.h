@@ -13,6 +13,9 @@ void tbk_gdeflate_destroy(tbk_gdeflate *g);
 // Queue a job: the members' text is copied to the device and coded, asynchronously.  The caller then sums each member's CRC-32
 // (tbk_gdeflate_set_crc, any time before the job is collected; the device sums them too) and waits for tbk_gdeflate_text_done before it touches the text again.
 int tbk_gdeflate_submit(tbk_gdeflate *g, const tbk_gdeflate_member *members, size_t n_members);
+// The same with bgzf framing (include/tbk.h "BAM output"): every member (<= 65280 bytes) becomes one bgzf block, its deflate blocks cut at
+// the job's cut hints (non-decreasing offsets into the members' bytes laid back to back, none beyond their end; n_hints may be 0).
+int tbk_gdeflate_submit_bgzf(tbk_gdeflate *g, const tbk_gdeflate_member *members, size_t n_members, const uint64_t *hints, size_t n_hints);
 void tbk_gdeflate_set_crc(tbk_gdeflate *g, size_t member, uint32_t crc);
 int tbk_gdeflate_text_done(tbk_gdeflate *g, int back = 0);   // back: how many jobs before the newest
 // Move the pipeline on and take the oldest finished job's members (none when nothing is ready and !drain).  The bytes lie in the

@@ -25,6 +25,10 @@
 // codes.  HBM roofline: the kernels read the text twice and write ~0.45 of it twice: ~3 B of HBM traffic per byte
 // of text; PCIe carries 1 B in and ~0.45 B out per byte.  Any inflater reads the result; the decompressed bytes are
 // what went in (tests/test_gpu_deflate.py: zlib on every member).
+//
+// The same kernels frame BAM bins (include/tbk.h "BAM output"; tbk_gdeflate_submit_bgzf): a job in bgzf mode makes one bgzf block
+// of every member (<= 65280 bytes of records), and cuts its deflate blocks at the caller's cut hints (gd_hint_kernel marks them in
+// the bitmap that gd_newline_kernel fills for text) instead of at line ends - see "bgzf framing" below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -405,6 +409,31 @@ gd_newline_kernel(const uint8_t *__restrict__ text, uint64_t n_words, uint32_t *
     bitmap[wi] = bits;
 }
 
+// ---- bgzf framing (include/tbk.h "BAM output") ----
+// A job in bgzf mode frames every member as one bgzf block: 18 bytes of header (the gzip header with the BC subfield and BSIZE) in the
+// 10-byte gzip header's place, the same trailer.  Its text is binary: no line ends to cut at, so the bitmap gd_cut_kernel reads is
+// zeroed and gd_hint_kernel marks the byte in FRONT of every cut hint - a block may end there, as it may end behind a '\n' in text.
+// The size bound: a block other than a member's last is longer than GD_BGZF_LEAST bytes, so a member of GD_BGZF_PAYLOAD bytes has at
+// most (GD_BGZF_PAYLOAD - 1) / (GD_BGZF_LEAST + 1) + 1 = 8 blocks; gd_encode_kernel writes a block in at most its bytes + 5 (the stored
+// form: BFINAL/BTYPE byte, LEN, NLEN; the coded form, its empty stored block behind it included, is taken only when it is smaller); the
+// member's final empty stored block is 5 bytes, header and trailer 18 + 8: 65280 + 8 * 5 + 5 + 26 = 65351 <= 65536, so BSIZE
+// always fits, whatever the bytes are.
+constexpr uint32_t GD_BGZF_PAYLOAD = 65280, GD_BGZF_LEAST = 8192, GD_BGZF_HEAD = 18, GD_GZIP_HEAD = 10;
+constexpr uint32_t GD_BGZF_MAX_BLOCKS = (GD_BGZF_PAYLOAD - 1) / (GD_BGZF_LEAST + 1) + 1;
+static_assert(GD_BGZF_PAYLOAD + GD_BGZF_MAX_BLOCKS * 5 + 5 + GD_BGZF_HEAD + 8 <= 65536, "a bgzf member of stored blocks must fit 64 KiB: raise GD_BGZF_LEAST");
+static_assert(GD_BGZF_LEAST < GD_MAX_BLOCK, "a hinted cut needs room between the least and the most block");
+
+// hints[i] in [0, text_total] (checked by the host): bit (h - 1) of the zeroed bitmap; a hint at 0 marks nothing.  Vector atomics:
+// neighbouring hints share words.
+__global__ void __launch_bounds__(GD_T)
+gd_hint_kernel(const uint64_t *__restrict__ hints, uint64_t n_hints, uint32_t *__restrict__ bitmap) {
+    const uint64_t i = (uint64_t)blockIdx.x * GD_T + threadIdx.x;
+    if (i >= n_hints) return;
+    const uint64_t h = hints[i];
+    if (h == 0) return;
+    atomicOr(&bitmap[(h - 1) >> 5], 1u << ((h - 1) & 31u));
+}
+
 // position of the first line end in text[start, start + count) relative to start, or -1: the whole WAVE looks, 64 words of the
 // bitmap (2 KiB of text) per load and four loads in flight, and every lane returns the same answer
 __device__ inline int64_t gd_find_nl(const uint32_t *__restrict__ bitmap, uint64_t start, uint64_t count) {
@@ -445,7 +474,7 @@ struct GdMember {
 // at the first line end past 8 KiB, so that the bases of a long read and its qualities get codes of their own; short lines:
 // blocks of 32 KiB.  Entries of the table a member does not use keep n = 0.
 __global__ void __launch_bounds__(64)
-gd_cut_kernel(const GdMember *__restrict__ members, uint32_t n_members, const uint32_t *__restrict__ bitmap, GdBlock *__restrict__ blocks) {
+gd_cut_kernel(const GdMember *__restrict__ members, uint32_t n_members, const uint32_t *__restrict__ bitmap, GdBlock *__restrict__ blocks, int binary) {
     const uint32_t j = blockIdx.x, lane = threadIdx.x;
     if (j >= n_members) return;
     const GdMember mb = members[j];
@@ -455,10 +484,14 @@ gd_cut_kernel(const GdMember *__restrict__ members, uint32_t n_members, const ui
     for (uint64_t off = 0; off < mb.n;) {
         uint64_t m = mb.n - off;
         const uint64_t at = mb.text_off + off;
-        const int64_t first = gd_find_nl(bitmap, at, m < 2048 ? m : 2048);
-        const uint64_t used = first >= 0 ? (uint64_t)first + 1 : m;
-        const bool short_lines = first >= 0 && (used == m || gd_find_nl(bitmap, at + used, (m - used) < 2048 ? (m - used) : 2048) >= 0);
-        const uint64_t least = short_lines ? GD_MAX_BLOCK : 8192, most = GD_MAX_BLOCK;
+        // (binary: the marks are cut hints, not line ends - there are no short lines to tell from long ones, the least is always 8192)
+        bool short_lines = false;
+        if (!binary) {
+            const int64_t first = gd_find_nl(bitmap, at, m < 2048 ? m : 2048);
+            const uint64_t used = first >= 0 ? (uint64_t)first + 1 : m;
+            short_lines = first >= 0 && (used == m || gd_find_nl(bitmap, at + used, (m - used) < 2048 ? (m - used) : 2048) >= 0);
+        }
+        const uint64_t least = short_lines ? GD_MAX_BLOCK : GD_BGZF_LEAST, most = GD_MAX_BLOCK;
         if (m > least) {
             const uint64_t span = (m < most ? m : most) - least;
             const int64_t nl = gd_find_nl(bitmap, at + least, span);
@@ -685,11 +718,11 @@ gd_encode_kernel(const uint8_t *__restrict__ text, const GdBlock *__restrict__ b
     GD_MARK(7);  // codes out
 }
 
-// dense[] = for every member: 10 bytes of gzip header, its blocks back to back, the final empty stored block (5 bytes),
+// dense[] = for every member: `head` bytes of header (10: gzip; 18: bgzf), its blocks back to back, the final empty stored block (5 bytes),
 // CRC-32 and ISIZE (8 bytes).  offsets[b]: where block b's bytes start; member_end[j]: where member j ends.
 __global__ void __launch_bounds__(GD_T)
 gd_scan_kernel(const GdBlock *__restrict__ blocks, const uint32_t *__restrict__ sizes, uint32_t n_blocks, uint64_t *__restrict__ offsets,
-               uint64_t *__restrict__ member_end, uint32_t n_members) {
+               uint64_t *__restrict__ member_end, uint32_t n_members, uint32_t head) {
     __shared__ uint32_t wave_sum[GD_T / 64];
     __shared__ uint64_t carry;
     __shared__ uint32_t used;
@@ -699,13 +732,13 @@ gd_scan_kernel(const GdBlock *__restrict__ blocks, const uint32_t *__restrict__ 
     for (uint32_t base = 0; base < n_blocks; base += GD_T) {
         const uint32_t i = base + t;
         uint32_t v = 0, flags = 0;
-        if (i < n_blocks && blocks[i].n) { flags = blocks[i].flags; v = sizes[i] + ((flags & 1u) ? 10u : 0u) + ((flags & 2u) ? 13u : 0u); }
+        if (i < n_blocks && blocks[i].n) { flags = blocks[i].flags; v = sizes[i] + ((flags & 1u) ? head : 0u) + ((flags & 2u) ? 13u : 0u); }
         uint32_t total = 0;
         const uint32_t ex = gd_block_exclusive_scan(wave_sum, v, total);
         const uint64_t start = carry + ex;
         if (i < n_blocks && v) {
             atomicAdd(&used, 1u);
-            offsets[i] = start + ((flags & 1u) ? 10u : 0u);
+            offsets[i] = start + ((flags & 1u) ? head : 0u);
             if (flags & 2u) member_end[blocks[i].member] = start + v;
         }
         __syncthreads();
@@ -717,7 +750,7 @@ gd_scan_kernel(const GdBlock *__restrict__ blocks, const uint32_t *__restrict__ 
 
 __global__ void __launch_bounds__(GD_T)
 gd_gather_kernel(const GdBlock *__restrict__ blocks, const uint32_t *__restrict__ sizes, const uint64_t *__restrict__ offsets, const uint8_t *__restrict__ slots,
-                 uint8_t *__restrict__ dense) {
+                 uint8_t *__restrict__ dense, const uint64_t *__restrict__ member_end, uint32_t head) {
     const int t = threadIdx.x;
     const GdBlock b = blocks[blockIdx.x];
     if (b.n == 0) return;
@@ -732,9 +765,16 @@ gd_gather_kernel(const GdBlock *__restrict__ blocks, const uint32_t *__restrict_
     } else {
         for (uint32_t i = t; i < size; i += GD_T) dst[i] = src[i];
     }
-    if ((b.flags & 1u) && t < 10) {
-        const uint8_t head[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
-        dst[(int)t - 10] = head[t];
+    if ((b.flags & 1u) && head == GD_GZIP_HEAD && t < 10) {
+        const uint8_t gz[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
+        dst[(int)t - 10] = gz[t];
+    }
+    if ((b.flags & 1u) && head == GD_BGZF_HEAD && t < 18) {
+        // FEXTRA, XLEN 6, the BC subfield of 2 bytes: BSIZE = the member's bytes - 1, from where it starts (18 bytes in front of this
+        // block, its first) and where gd_scan_kernel found it to end - at most 65535 by the bound above
+        const uint32_t bsize = (uint32_t)(member_end[b.member] - (offsets[blockIdx.x] - GD_BGZF_HEAD)) - 1u;
+        const uint8_t bg[18] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)(bsize & 0xFF), (uint8_t)((bsize >> 8) & 0xFF)};
+        dst[(int)t - 18] = bg[t];
     }
     if ((b.flags & 2u) && t < 13) {
         // BFINAL = 1, BTYPE = 00 (one byte with the padding), LEN = 0, NLEN = FFFF; the CRC-32 is the host's; ISIZE
@@ -788,7 +828,10 @@ struct PinBuf {
 struct Job {
     int state = 0;  // 0 free, 1 coding (text in, kernels, the members' ends on their way home), 2 the members on their way home
     DevBuf d_text, d_bitmap, d_members, d_blocks, d_slots, d_sizes, d_offsets, d_member_end, d_dense;  // (d_member_end: the members' ends, the block count, then the members' CRCs)
-    PinBuf h_members, h_member_end, h_dense;
+    PinBuf h_members, h_member_end, h_dense, h_hints;
+    DevBuf d_hints;
+    bool bgzf = false;              // bgzf framing, cuts from hints (tbk_gdeflate_submit_bgzf)
+    uint64_t n_hints = 0;
     hipEvent_t text_in = nullptr, meta_home = nullptr, dense_home = nullptr;
     std::vector<int> tags;          // per member: the caller's tag (the bin)
     std::vector<uint32_t> crc;      // per member, when the caller has summed it itself (tbk_gdeflate_set_crc); else the device's is used
@@ -797,7 +840,7 @@ struct Job {
     uint64_t dense_bytes = 0;
     void drop() {
         d_text.drop(); d_bitmap.drop(); d_members.drop(); d_blocks.drop(); d_slots.drop(); d_sizes.drop(); d_offsets.drop(); d_member_end.drop(); d_dense.drop();
-        h_members.drop(); h_member_end.drop(); h_dense.drop();
+        h_members.drop(); h_member_end.drop(); h_dense.drop(); h_hints.drop(); d_hints.drop();
         if (text_in) (void)hipEventDestroy(text_in);
         if (meta_home) (void)hipEventDestroy(meta_home);
         if (dense_home) (void)hipEventDestroy(dense_home);
@@ -860,13 +903,48 @@ void tbk_gdeflate_destroy(tbk_gdeflate *g) {
     delete g;
 }
 
-int tbk_gdeflate_submit(tbk_gdeflate *g, const tbk_gdeflate_member *members, size_t n_members) {
+// A job's kernels on the encoder's stream, its text (and hints) on the device: marks, cuts, CRC-32s, the blocks, where they go, the gather.
+static void gd_launch(tbk_gdeflate *g, Job &j, size_t n_members, uint64_t nb, uint64_t n_words, uint64_t longest) {
+    const uint32_t head = j.bgzf ? GD_BGZF_HEAD : GD_GZIP_HEAD;
+    if (!j.bgzf) hipLaunchKernelGGL(gd_newline_kernel, dim3((unsigned)((n_words + GD_T - 1) / GD_T)), dim3(GD_T), 0, g->stream, (const uint8_t *)j.d_text.p, n_words, (uint32_t *)j.d_bitmap.p);
+    else {
+        (void)hipMemsetAsync(j.d_bitmap.p, 0, (n_words + 2) * 4, g->stream);
+        if (j.n_hints) hipLaunchKernelGGL(gd_hint_kernel, dim3((unsigned)((j.n_hints + GD_T - 1) / GD_T)), dim3(GD_T), 0, g->stream, (const uint64_t *)j.d_hints.p, j.n_hints, (uint32_t *)j.d_bitmap.p);
+    }
+    hipLaunchKernelGGL(gd_cut_kernel, dim3((unsigned)n_members), dim3(64), 0, g->stream, (const GdMember *)j.d_members.p, (uint32_t)n_members,
+                       (const uint32_t *)j.d_bitmap.p, (GdBlock *)j.d_blocks.p, j.bgzf ? 1 : 0);
+    hipLaunchKernelGGL(gd_crc_kernel, dim3((unsigned)(((longest + 63) / 64 + GD_T - 1) / GD_T), (unsigned)n_members), dim3(GD_T), 0, g->stream, (const uint8_t *)j.d_text.p,
+                       (const GdMember *)j.d_members.p, (const GdCrcTabs *)g->d_crc_tabs, g->x2n, (uint32_t *)((uint64_t *)j.d_member_end.p + n_members + 1));
+    hipLaunchKernelGGL(gd_encode_kernel, dim3((unsigned)nb), dim3(GD_T), 0, g->stream, (const uint8_t *)j.d_text.p, (const GdBlock *)j.d_blocks.p, (uint8_t *)j.d_slots.p,
+                       (uint32_t *)j.d_sizes.p);
+    hipLaunchKernelGGL(gd_scan_kernel, dim3(1), dim3(GD_T), 0, g->stream, (const GdBlock *)j.d_blocks.p, (const uint32_t *)j.d_sizes.p, (uint32_t)nb, (uint64_t *)j.d_offsets.p,
+                       (uint64_t *)j.d_member_end.p, (uint32_t)n_members, head);
+    hipLaunchKernelGGL(gd_gather_kernel, dim3((unsigned)nb), dim3(GD_T), 0, g->stream, (const GdBlock *)j.d_blocks.p, (const uint32_t *)j.d_sizes.p,
+                       (const uint64_t *)j.d_offsets.p, (const uint8_t *)j.d_slots.p, (uint8_t *)j.d_dense.p, (const uint64_t *)j.d_member_end.p, head);
+}
+
+static int gd_submit(tbk_gdeflate *g, const tbk_gdeflate_member *members, size_t n_members, bool bgzf, const uint64_t *hints, size_t n_hints);
+int tbk_gdeflate_submit(tbk_gdeflate *g, const tbk_gdeflate_member *members, size_t n_members) { return gd_submit(g, members, n_members, false, nullptr, 0); }
+int tbk_gdeflate_submit_bgzf(tbk_gdeflate *g, const tbk_gdeflate_member *members, size_t n_members, const uint64_t *hints, size_t n_hints) {
+    if (n_hints && !hints) { tbk_set_error_(TBK_ERR_INVALID, "GPU gzip encoder: NULL argument"); return TBK_ERR_INVALID; }
+    uint64_t total = 0;
+    for (size_t i = 0; i < n_members; i++) {
+        if (members[i].n > GD_BGZF_PAYLOAD) { tbk_set_error_(TBK_ERR_INVALID, "GPU gzip encoder: a bgzf member of more than 65280 bytes"); return TBK_ERR_INVALID; }
+        total += members[i].n;
+    }
+    for (size_t i = 0; i < n_hints; i++)
+        if (hints[i] > total || (i && hints[i] < hints[i - 1])) { tbk_set_error_(TBK_ERR_INVALID, "GPU gzip encoder: cut hints must not decrease nor pass the end of the bytes"); return TBK_ERR_INVALID; }
+    return gd_submit(g, members, n_members, true, hints, n_hints);
+}
+
+static int gd_submit(tbk_gdeflate *g, const tbk_gdeflate_member *members, size_t n_members, bool bgzf, const uint64_t *hints, size_t n_hints) {
     if (!g || (n_members && !members)) { tbk_set_error_(TBK_ERR_INVALID, "GPU gzip encoder: NULL argument"); return TBK_ERR_INVALID; }
     Job &j = g->jobs[g->submitted % 3];
     if (j.state != 0) { tbk_set_error_(TBK_ERR_STATE, "GPU gzip encoder: three jobs in flight; collect first"); return TBK_ERR_STATE; }
     hipError_t e = hipSetDevice(g->device);
     if (e != hipSuccess) return gfail(TBK_ERR_HIP, "hipSetDevice", e);
     j.tags.clear(); j.crc.assign(n_members, 0); j.crc_set.assign(n_members, 0); j.text_len.clear();
+    j.bgzf = bgzf; j.n_hints = bgzf ? n_hints : 0;
     // The host never reads the text (it is 30 GB a run): where the line ends are is found on the device (gd_newline_kernel), the
     // blocks are cut there (gd_cut_kernel).  Here: only what follows from the members' lengths - where a member's text, its
     // entries of the block table (as many as it could need: a block is 8 KiB or more, but for a member's last) and its slots begin.
@@ -887,8 +965,10 @@ int tbk_gdeflate_submit(tbk_gdeflate *g, const tbk_gdeflate_member *members, siz
     if (n_members > 65535) { tbk_set_error_(TBK_ERR_INVALID, "GPU gzip encoder: more than 65535 members in one job"); return TBK_ERR_INVALID; }
     if (nb > 0x7FFFFFF0ull) { tbk_set_error_(TBK_ERR_INVALID, "GPU gzip encoder: too much text in one job"); return TBK_ERR_INVALID; }
     const uint64_t n_words = (text_total + 31) / 32;
-    const uint64_t dense_cap = slot_total + 23 * (uint64_t)n_members + 64;
+    const uint64_t dense_cap = slot_total + 31 * (uint64_t)n_members + 64;   // (header and trailer: 10 + 13 bytes of a gzip member, 18 + 13 of a bgzf one)
     e = j.d_text.need(n_words * 32 + 64);
+    if (e == hipSuccess && j.n_hints) e = j.d_hints.need(j.n_hints * 8);
+    if (e == hipSuccess && j.n_hints) e = j.h_hints.need(j.n_hints * 8);
     if (e == hipSuccess) e = j.d_bitmap.need((n_words + 2) * 4);
     if (e == hipSuccess) e = j.d_members.need((n_members + 1) * sizeof(GdMember));
     if (e == hipSuccess) e = j.d_blocks.need((nb + 1) * sizeof(GdBlock));
@@ -912,24 +992,18 @@ int tbk_gdeflate_submit(tbk_gdeflate *g, const tbk_gdeflate_member *members, siz
     }
     if (e == hipSuccess && (text_total & 31)) e = hipMemsetAsync((uint8_t *)j.d_text.p + text_total, 0, 32 - (text_total & 31), g->stream_in);  // (the bitmap's last word reads whole)
     if (e == hipSuccess && n_members) e = hipMemcpyAsync(j.d_members.p, j.h_members.p, n_members * sizeof(GdMember), hipMemcpyHostToDevice, g->stream_in);
+    if (e == hipSuccess && j.n_hints) {
+        memcpy(j.h_hints.p, hints, j.n_hints * 8);
+        e = hipMemcpyAsync(j.d_hints.p, j.h_hints.p, j.n_hints * 8, hipMemcpyHostToDevice, g->stream_in);
+    }
     if (e == hipSuccess) e = hipEventRecord(j.text_in, g->stream_in);
     if (e == hipSuccess) e = hipStreamWaitEvent(g->stream, j.text_in, 0);
     if (e == hipSuccess) e = hipMemsetAsync(j.d_member_end.p, 0, (n_members + 1) * 12, g->stream);
     if (e == hipSuccess && slot_total) e = hipMemsetAsync(j.d_slots.p, 0, slot_total, g->stream);  // (the codes are ORed and stored into zeroed slots)
     if (e == hipSuccess && text_total) {
-        hipLaunchKernelGGL(gd_newline_kernel, dim3((unsigned)((n_words + GD_T - 1) / GD_T)), dim3(GD_T), 0, g->stream, (const uint8_t *)j.d_text.p, n_words, (uint32_t *)j.d_bitmap.p);
-        hipLaunchKernelGGL(gd_cut_kernel, dim3((unsigned)n_members), dim3(64), 0, g->stream, (const GdMember *)j.d_members.p, (uint32_t)n_members,
-                           (const uint32_t *)j.d_bitmap.p, (GdBlock *)j.d_blocks.p);
         uint64_t longest = 0;
         for (size_t i = 0; i < n_members; i++) longest = std::max<uint64_t>(longest, members[i].n);
-        hipLaunchKernelGGL(gd_crc_kernel, dim3((unsigned)(((longest + 63) / 64 + GD_T - 1) / GD_T), (unsigned)n_members), dim3(GD_T), 0, g->stream, (const uint8_t *)j.d_text.p,
-                           (const GdMember *)j.d_members.p, (const GdCrcTabs *)g->d_crc_tabs, g->x2n, (uint32_t *)((uint64_t *)j.d_member_end.p + n_members + 1));
-        hipLaunchKernelGGL(gd_encode_kernel, dim3((unsigned)nb), dim3(GD_T), 0, g->stream, (const uint8_t *)j.d_text.p, (const GdBlock *)j.d_blocks.p, (uint8_t *)j.d_slots.p,
-                           (uint32_t *)j.d_sizes.p);
-        hipLaunchKernelGGL(gd_scan_kernel, dim3(1), dim3(GD_T), 0, g->stream, (const GdBlock *)j.d_blocks.p, (const uint32_t *)j.d_sizes.p, (uint32_t)nb, (uint64_t *)j.d_offsets.p,
-                           (uint64_t *)j.d_member_end.p, (uint32_t)n_members);
-        hipLaunchKernelGGL(gd_gather_kernel, dim3((unsigned)nb), dim3(GD_T), 0, g->stream, (const GdBlock *)j.d_blocks.p, (const uint32_t *)j.d_sizes.p,
-                           (const uint64_t *)j.d_offsets.p, (const uint8_t *)j.d_slots.p, (uint8_t *)j.d_dense.p);
+        gd_launch(g, j, n_members, nb, n_words, longest);
         if (e == hipSuccess) e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(j.h_member_end.p, j.d_member_end.p, (n_members + 1) * 12, hipMemcpyDeviceToHost, g->stream);
@@ -996,10 +1070,12 @@ int tbk_gdeflate_collect(tbk_gdeflate *g, bool drain, std::vector<tbk_gdeflate_o
                 if (j.text_len[i] == 0) {
                     // an empty member (an empty bin's file is a valid gzip file, as gzip.open(...).close() leaves it)
                     static const uint8_t empty[23] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff, 0x01, 0x00, 0x00, 0xff, 0xff, 0, 0, 0, 0, 0, 0, 0, 0};
-                    memcpy(dense + spare, empty, 23);
-                    out.push_back(tbk_gdeflate_out{j.tags[i], (const char *)dense + spare, 23});
-                    spare += 23;
-                    g->member_bytes += 23;
+                    static const uint8_t empty_bgzf[31] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 30, 0, 0x01, 0x00, 0x00, 0xff, 0xff, 0, 0, 0, 0, 0, 0, 0, 0};
+                    const size_t en = j.bgzf ? 31 : 23;
+                    memcpy(dense + spare, j.bgzf ? empty_bgzf : empty, en);
+                    out.push_back(tbk_gdeflate_out{j.tags[i], (const char *)dense + spare, en});
+                    spare += en;
+                    g->member_bytes += en;
                     continue;
                 }
                 const uint64_t end = ends[i];
@@ -1518,18 +1594,81 @@ extern "C" int tbk_gdeflate_phases_(unsigned long long out[16]) {
 // holds it) go through the three-deep ring - text in, kernels, members out, overlapped - and *pipelined_s is the wall time per job in
 // the steady state (link included); *kernels_s the kernels' own time per job (HIP events around one job's kernels on an idle
 // device).  *out_bytes: bytes of members one job makes.
+static int gd_bench(int device, const std::vector<tbk_gdeflate_member> &members, bool bgzf, const uint64_t *hints, size_t n_hints, int reps, double *pipelined_s, double *kernels_s,
+                    uint64_t *out_bytes);
 extern "C" int tbk_gzip_bench_device(int device, const char *text, const uint64_t *member_len, uint64_t n_members, int reps, double *pipelined_s, double *kernels_s,
                                      uint64_t *out_bytes) {
     if (!text || !member_len || !n_members || reps < 4 || !pipelined_s || !kernels_s || !out_bytes) { tbk_set_error_(TBK_ERR_INVALID, "tbk_gzip_bench_device: bad argument"); return TBK_ERR_INVALID; }
-    tbk_gdeflate *g = nullptr;
-    int rc = tbk_gdeflate_create(device, &g);
-    if (rc) return rc;
     std::vector<tbk_gdeflate_member> members;
     uint64_t off = 0;
     for (uint64_t i = 0; i < n_members; i++) { members.push_back(tbk_gdeflate_member{text + off, (size_t)member_len[i], 0}); off += member_len[i]; }
+    return gd_bench(device, members, false, nullptr, 0, reps, pipelined_s, kernels_s, out_bytes);
+}
+
+// data[0 .. size) as the members of a bgzf job: pieces of 65280 bytes, the last one shorter
+static std::vector<tbk_gdeflate_member> bgzf_pieces(const uint8_t *data, uint64_t size) {
+    std::vector<tbk_gdeflate_member> members;
+    for (uint64_t at = 0; at < size; at += GD_BGZF_PAYLOAD) members.push_back(tbk_gdeflate_member{(const char *)data + at, (size_t)std::min<uint64_t>(GD_BGZF_PAYLOAD, size - at), 0});
+    return members;
+}
+
+// C-ABI (include/tbk.h): bytes -> bgzf blocks on `device`, no BAM header and no end-of-file marker; one job, synchronously.
+// (tests) tags: a tag per member going in (the bin writer's are its bins); out_tags / out_len: every member's tag and length as the job hands them back.
+extern "C" int tbk_bgzf_members_tagged_device_(int device, const uint8_t *data, uint64_t size, const uint64_t *hints, uint64_t n_hints, const int32_t *tags, uint8_t *dst,
+                                               uint64_t cap, uint64_t *need, uint64_t *n_members, int32_t *out_tags, uint64_t *out_len) {
+    if ((!data && size) || (!hints && n_hints) || !need || !n_members) { tbk_set_error_(TBK_ERR_INVALID, "tbk_bgzf_members_device: NULL argument"); return TBK_ERR_INVALID; }
+    for (uint64_t i = 0; i < n_hints; i++)
+        if (hints[i] > size || (i && hints[i] < hints[i - 1])) { tbk_set_error_(TBK_ERR_INVALID, "tbk_bgzf_members_device: cut hints must not decrease nor pass the end of the bytes"); return TBK_ERR_INVALID; }
+    *need = 0; *n_members = 0;
+    if (!size) return TBK_OK;
+    tbk_gdeflate *g = nullptr;
+    int rc = tbk_gdeflate_create(device, &g);
+    if (rc) return rc;
+    std::vector<tbk_gdeflate_member> members = bgzf_pieces(data, size);
+    for (size_t i = 0; tags && i < members.size(); i++) members[i].tag = tags[i];
+    rc = tbk_gdeflate_submit_bgzf(g, members.data(), members.size(), hints, (size_t)n_hints);
+    if (!rc) rc = tbk_gdeflate_text_done(g, 0);
+    std::vector<tbk_gdeflate_out> outs;
+    uint64_t used = 0, at = 0;
+    while (!rc && tbk_gdeflate_in_flight(g) > 0) {
+        rc = tbk_gdeflate_collect(g, true, outs);
+        for (const tbk_gdeflate_out &o : outs) {
+            if (dst && used + o.n <= cap) memcpy(dst + used, o.data, o.n);
+            if (out_tags && at < members.size()) out_tags[at] = o.tag;
+            if (out_len && at < members.size()) out_len[at] = o.n;
+            at++;
+            used += o.n;
+        }
+    }
+    tbk_gdeflate_destroy(g);
+    if (rc) return rc;
+    *need = used;
+    *n_members = members.size();
+    if (used > cap || !dst) { tbk_set_error_(TBK_ERR_NOMEM, "tbk_bgzf_members_device: dst too small"); return TBK_ERR_NOMEM; }
+    return TBK_OK;
+}
+
+extern "C" int tbk_bgzf_members_device(int device, const uint8_t *data, uint64_t size, const uint64_t *hints, uint64_t n_hints, uint8_t *dst, uint64_t cap, uint64_t *need,
+                                       uint64_t *n_members) {
+    return tbk_bgzf_members_tagged_device_(device, data, size, hints, n_hints, nullptr, dst, cap, need, n_members, nullptr, nullptr);
+}
+
+// The bgzf mode timed like tbk_gzip_bench_device (data in pinned host memory: tbk_host_alloc).
+extern "C" int tbk_bgzf_members_bench_device(int device, const uint8_t *data, uint64_t size, const uint64_t *hints, uint64_t n_hints, int reps, double *pipelined_s, double *kernels_s,
+                                             uint64_t *out_bytes) {
+    if (!data || !size || (!hints && n_hints) || reps < 4 || !pipelined_s || !kernels_s || !out_bytes) { tbk_set_error_(TBK_ERR_INVALID, "tbk_bgzf_members_bench_device: bad argument"); return TBK_ERR_INVALID; }
+    return gd_bench(device, bgzf_pieces(data, size), true, hints, (size_t)n_hints, reps, pipelined_s, kernels_s, out_bytes);
+}
+
+static int gd_bench(int device, const std::vector<tbk_gdeflate_member> &members, bool bgzf, const uint64_t *hints, size_t n_hints, int reps, double *pipelined_s, double *kernels_s,
+                    uint64_t *out_bytes) {
+    tbk_gdeflate *g = nullptr;
+    int rc = tbk_gdeflate_create(device, &g);
+    if (rc) return rc;
+    auto submit = [&]() { return bgzf ? tbk_gdeflate_submit_bgzf(g, members.data(), members.size(), hints, n_hints) : tbk_gdeflate_submit(g, members.data(), members.size()); };
     std::vector<tbk_gdeflate_out> outs;
     // warm-up: three jobs (every slot's buffers exist), drained
-    for (int i = 0; i < 3 && !rc; i++) { rc = tbk_gdeflate_submit(g, members.data(), members.size()); if (!rc) rc = tbk_gdeflate_collect(g, false, outs); }
+    for (int i = 0; i < 3 && !rc; i++) { rc = submit(); if (!rc) rc = tbk_gdeflate_collect(g, false, outs); }
     while (!rc && tbk_gdeflate_in_flight(g) > 0) rc = tbk_gdeflate_collect(g, true, outs);
     uint64_t bytes = 0;
     for (const tbk_gdeflate_out &o : outs) bytes += o.n;
@@ -1541,7 +1680,7 @@ extern "C" int tbk_gzip_bench_device(int device, const char *text, const uint64_
         if (e == hipSuccess) e = hipEventCreate(&e1);
         if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
         // (the kernels wait for the text's event: bracket them by recording behind the text's arrival and behind the last kernel)
-        if (e == hipSuccess) { rc = tbk_gdeflate_submit(g, members.data(), members.size()); }
+        if (e == hipSuccess) { rc = submit(); }
         if (e != hipSuccess) rc = gfail(TBK_ERR_HIP, "bench", e);
         while (!rc && tbk_gdeflate_in_flight(g) > 0) rc = tbk_gdeflate_collect(g, true, outs);
         // timed again with the text already resident: the same job's kernels re-launched are what the events bracket
@@ -1558,15 +1697,7 @@ extern "C" int tbk_gzip_bench_device(int device, const char *text, const uint64_
             (void)hipEventRecord(e0, g->stream);
             (void)hipMemsetAsync(j.d_member_end.p, 0, (nm + 1) * 12, g->stream);
             (void)hipMemsetAsync(j.d_slots.p, 0, slot_total, g->stream);
-            hipLaunchKernelGGL(gd_newline_kernel, dim3((unsigned)((n_words + GD_T - 1) / GD_T)), dim3(GD_T), 0, g->stream, (const uint8_t *)j.d_text.p, n_words, (uint32_t *)j.d_bitmap.p);
-            hipLaunchKernelGGL(gd_cut_kernel, dim3((unsigned)nm), dim3(64), 0, g->stream, (const GdMember *)j.d_members.p, (uint32_t)nm, (const uint32_t *)j.d_bitmap.p, (GdBlock *)j.d_blocks.p);
-            hipLaunchKernelGGL(gd_crc_kernel, dim3((unsigned)(((longest + 63) / 64 + GD_T - 1) / GD_T), (unsigned)nm), dim3(GD_T), 0, g->stream, (const uint8_t *)j.d_text.p,
-                               (const GdMember *)j.d_members.p, (const GdCrcTabs *)g->d_crc_tabs, g->x2n, (uint32_t *)((uint64_t *)j.d_member_end.p + nm + 1));
-            hipLaunchKernelGGL(gd_encode_kernel, dim3((unsigned)nb), dim3(GD_T), 0, g->stream, (const uint8_t *)j.d_text.p, (const GdBlock *)j.d_blocks.p, (uint8_t *)j.d_slots.p, (uint32_t *)j.d_sizes.p);
-            hipLaunchKernelGGL(gd_scan_kernel, dim3(1), dim3(GD_T), 0, g->stream, (const GdBlock *)j.d_blocks.p, (const uint32_t *)j.d_sizes.p, (uint32_t)nb, (uint64_t *)j.d_offsets.p,
-                               (uint64_t *)j.d_member_end.p, (uint32_t)nm);
-            hipLaunchKernelGGL(gd_gather_kernel, dim3((unsigned)nb), dim3(GD_T), 0, g->stream, (const GdBlock *)j.d_blocks.p, (const uint32_t *)j.d_sizes.p, (const uint64_t *)j.d_offsets.p,
-                               (const uint8_t *)j.d_slots.p, (uint8_t *)j.d_dense.p);
+            gd_launch(g, j, nm, nb, n_words, longest);
             (void)hipEventRecord(e1, g->stream);
             hipError_t e2 = hipEventSynchronize(e1);
             if (e2 == hipSuccess) e2 = hipEventElapsedTime(&ms, e0, e1);
@@ -1578,7 +1709,7 @@ extern "C" int tbk_gzip_bench_device(int device, const char *text, const uint64_
     if (!rc) {
         const auto t0 = std::chrono::steady_clock::now();
         for (int i = 0; i < reps && !rc; i++) {
-            rc = tbk_gdeflate_submit(g, members.data(), members.size());
+            rc = submit();
             if (!rc) rc = tbk_gdeflate_collect(g, false, outs);
         }
         while (!rc && tbk_gdeflate_in_flight(g) > 0) rc = tbk_gdeflate_collect(g, true, outs);

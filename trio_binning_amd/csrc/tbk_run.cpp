@@ -102,7 +102,17 @@ extern "C" int tbk_classify_file(tbk_pipeline *p, const char *reads_path, uint64
         if (c0) (void)tbk_fastx_set_device(reader, tbk_classifier_device(c0));
     }
     tbk_bin_writer *writer = nullptr;
-    rc = tbk_bin_writer_open(out_a, out_b, out_u, gzip_output, gzip_level, 0, &writer);
+    if (gzip_output == 2) {
+        // BAM bins (include/tbk.h "BAM output"): the batches carry their records, the bins begin with the input's header
+        const uint8_t *header = nullptr;
+        uint64_t header_len = 0;
+        if (!tbk_fastx_bam_counts(reader, nullptr)) { tbk_set_error_(TBK_ERR_INVALID, "BAM bins need BAM input"); rc = TBK_ERR_INVALID; }
+        if (!rc) rc = tbk_fastx_set_keep_records(reader, 1);
+        if (!rc) rc = tbk_fastx_bam_header(reader, &header, &header_len);
+        if (!rc) rc = tbk_bin_writer_open_bam(out_a, out_b, out_u, header, header_len, gzip_level, 0, &writer);
+    } else {
+        rc = tbk_bin_writer_open(out_a, out_b, out_u, gzip_output, gzip_level, 0, &writer);
+    }
     if (rc) { tbk_fastx_close(reader); return rc; }
     if (gzip_output) {
         // the bins' gzip members are coded on the (first) device of the pipeline - it is idle 95 % of an end-to-end run - unless

@@ -252,6 +252,19 @@ class Batch:
         em = np.ctypeslib.as_array(C.cast(p[2], C.POINTER(C.c_uint16)), (max(p[3], 1),))[:p[3]].copy()
         return codes, ec, em
 
+    def records(self) -> List[bytes]:
+        """The reads' BAM records, whole (``block_size`` and all that follows), one per read in the batch's order; empty
+        when the batch carries none (``BatchReader(..., keep_records=True)`` on a ``.bam`` file)."""
+        import ctypes as C
+
+        from ._lib import lib
+
+        recs, offs = C.c_void_p(), C.c_void_p()
+        if not lib.tbk_fastx_batch_records(self._h, C.byref(recs), C.byref(offs)) or not offs.value:
+            return []
+        off = C.cast(offs, C.POINTER(C.c_uint64))
+        return [C.string_at(recs.value + off[i], off[i + 1] - off[i]) for i in range(self.n_reads)]
+
     def reads(self) -> List[Read]:
         """The batch as ``Read`` objects (tests; the CLI never materialises them)."""
         bases, boff, names, noff, quals, qoff, hq = self.arrays()
@@ -281,8 +294,10 @@ class BatchReader:
     """Native FASTA/FASTQ(.gz) or BAM reader: ``next_batch(batch, max_bases, max_reads)`` fills a
     ``Batch`` and returns the number of records (0 at end of input).  A name ending in ``.bam`` is read as unaligned BAM."""
 
-    def __init__(self, filename: str, packing: bool = False, borrowing: bool = False, device: Optional[int] = None):
-        """``device``: BGZF input is inflated on that GPU, and BAM records are turned into FASTQ text there (``tbk_fastx_set_device``: what ``classify-by-kmers`` does by itself),
+    def __init__(self, filename: str, packing: bool = False, borrowing: bool = False, device: Optional[int] = None, keep_records: bool = False):
+        """``keep_records``: BAM input only (refused for any other file) - every batch also carries its reads' records, whole
+        (``Batch.records``), for ``BinWriter(..., bam_header=...)``.
+        ``device``: BGZF input is inflated on that GPU, and BAM records are turned into FASTQ text there (``tbk_fastx_set_device``: what ``classify-by-kmers`` does by itself),
         and with ``TBK_GZIP_INFLATE=gpu`` an ordinary gzip file as well (``gzip_stats``); None: on the host's threads.
         ``inflates_on_device`` says which it is."""
         import ctypes as C
@@ -300,6 +315,22 @@ class BatchReader:
             check(lib.tbk_fastx_set_packing(h, 1))
         if borrowing:  # batches of a plain FASTQ file leave their records in the reader's mapping (what the native loop does):
             check(lib.tbk_fastx_set_borrowing(h, 1))  # no sequence / quality arrays; valid until close()
+        if keep_records:
+            try:
+                check(lib.tbk_fastx_set_keep_records(h, 1))
+            except Exception:
+                self.close()
+                raise
+
+    def bam_header(self) -> bytes:
+        """The header bytes of a BAM input, ``BAM\\1`` through the last reference entry (read now if no batch has been yet)."""
+        import ctypes as C
+
+        from ._lib import check, lib
+
+        ptr, n = C.c_void_p(), C.c_uint64()
+        check(lib.tbk_fastx_bam_header(self._h, C.byref(ptr), C.byref(n)))
+        return C.string_at(ptr.value, n.value)
 
     def next_batch(self, batch: Batch, max_bases: int = 0, max_reads: int = 0) -> int:
         import ctypes as C
@@ -362,17 +393,23 @@ class BinWriter:
     ``open_outfiles`` + ``Read.print``); gzip members are deflated in parallel."""
 
     def __init__(self, haplotype_a_prefix: str, haplotype_b_prefix: str, unclassified_prefix: str,
-                 outfile_extension: str, gzip_output: bool, level: int = -1, threads: int = 0, device: Optional[int] = None):
-        """``device``: code the gzip members on that GPU (``tbk_bin_writer_use_device``: what ``classify-by-kmers`` does by itself);
+                 outfile_extension: str, gzip_output: bool, level: int = -1, threads: int = 0, device: Optional[int] = None,
+                 bam_header: Optional[bytes] = None):
+        """``bam_header``: BAM bins (include/tbk.h "BAM output") - the files are ``prefix + outfile_extension`` as given (``.bam``), begin
+        with these header bytes, and ``write`` takes batches that carry their records (``BatchReader(..., keep_records=True)``).
+        ``device``: code the gzip members on that GPU (``tbk_bin_writer_use_device``: what ``classify-by-kmers`` does by itself);
         None: on the host's threads.  ``gpu_encoder`` says which it is."""
         import ctypes as C
         import os
 
         from ._lib import check, lib
 
-        self.names = output_names(haplotype_a_prefix, haplotype_b_prefix, unclassified_prefix, outfile_extension, gzip_output)
+        self.names = output_names(haplotype_a_prefix, haplotype_b_prefix, unclassified_prefix, outfile_extension, gzip_output and bam_header is None)
         h = C.c_void_p()
-        check(lib.tbk_bin_writer_open(*[os.fsencode(n) for n in self.names], int(gzip_output), level, threads, C.byref(h)))
+        if bam_header is not None:
+            check(lib.tbk_bin_writer_open_bam(*[os.fsencode(n) for n in self.names], bam_header, len(bam_header), level, threads, C.byref(h)))
+        else:
+            check(lib.tbk_bin_writer_open(*[os.fsencode(n) for n in self.names], int(gzip_output), level, threads, C.byref(h)))
         self._h = h
         if device is not None:
             check(lib.tbk_bin_writer_use_device(h, device))
@@ -430,6 +467,41 @@ def gzip_members_device(pieces, device: int = 0):
         out.append(C.string_at(C.addressof(buf) + at, out_lens[i]))
         at += out_lens[i]
     return out
+
+
+def _bgzf_members(call, data: bytes, hints):
+    import ctypes as C
+
+    from ._lib import TBK_ERR_NOMEM, check
+
+    hints = list(hints or ())
+    h = (C.c_uint64 * max(1, len(hints)))(*hints)
+    need, n = C.c_uint64(), C.c_uint64()
+    cap = len(data) + 128 * (len(data) // 65280 + 1) + 64
+    buf = C.create_string_buffer(cap)
+    status = call(data, len(data), h, len(hints), buf, cap, C.byref(need), C.byref(n))
+    if status == TBK_ERR_NOMEM and need.value > cap:
+        cap = need.value
+        buf = C.create_string_buffer(cap)
+        status = call(data, len(data), h, len(hints), buf, cap, C.byref(need), C.byref(n))
+    check(status)
+    return C.string_at(C.addressof(buf), need.value), n.value
+
+
+def bgzf_members_device(data: bytes, hints=None, device: int = 0):
+    """``data`` as bgzf blocks of at most 65280 bytes of payload, coded on the GPU (``tbk_bgzf_members_device``: the BAM bin writer's
+    encoder by itself; no BAM header, no end-of-file marker).  ``hints``: non-decreasing offsets into ``data`` where the kind of
+    the bytes changes - a deflate block may end there.  Returns (the blocks back to back, how many)."""
+    from ._lib import lib
+
+    return _bgzf_members(lambda *a: lib.tbk_bgzf_members_device(device, *a), data, hints)
+
+
+def bgzf_members_host(data: bytes, hints=None):
+    """The same by the host's coder (``tbk_bgzf_members``): same contract, same cut rule, no GPU."""
+    from ._lib import lib
+
+    return _bgzf_members(lib.tbk_bgzf_members, data, hints)
 
 
 def bgzf_inflate_device(data: bytes, device: int = 0) -> bytes:
