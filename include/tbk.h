@@ -908,6 +908,29 @@ int tbk_kmerdb_inherited(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kme
                          uint32_t child_min, uint32_t child_max, const char *out_path, uint64_t *n_written);
 int tbk_kmerdb_inherited_table(const tbk_kmerdb *a, const tbk_kmerdb *b, const tbk_kmerdb *child, uint32_t min_count, uint32_t max_count,
                                uint32_t child_min, uint32_t child_max, tbk_table **out);
+/* Two databases held against each other: the joint k-mer spectrum (the matrix `kat comp` and Merqury's read-set comparisons
+ * plot).  spec[cx * 256 + cy] is the number of distinct k-mers whose counter is cx in `x` and cy in `y`; counter 0 means "the
+ * database holds no entry for it".  Either floor is accepted in either position, and what 0 means follows from each database's
+ * floor: for a full database (floor 1) "never seen in its reads" - its once-seen k-mers are entries with counter 1 - and for a
+ * floor-2 database "seen once or never".  By construction spec[0] (the cell 0,0) is 0, row c >= 1 sums to the entries of `x`
+ * with counter c, column c >= 1 to those of `y`, and the whole matrix to the size of the union of the two key sets.  Two
+ * launches, each striding over the tiles of 1024 entries of the database it walks (csrc/tbk_compare.hip): over `x`, where every
+ * entry searches `y` between its tile's bounds there and goes to the cell (cx, cy or 0), and over `y`, where the entries `x`
+ * lacks go to the cell (0, cy).  Blocks tally in LDS and flush once.  Beside the inputs the call holds the matrix (512 KiB).
+ * Both calls: all databases must have one k, one device and one space (plain or homopolymer-compressed); a NULL argument or a
+ * mismatch is TBK_ERR_INVALID with the reason in tbk_last_error().  Empty databases are legal in any position.  The inputs are
+ * only read; TBK_ERR_NOMEM leaves every database as it was and the device usable. */
+int tbk_kmerdb_joint_spectrum(const tbk_kmerdb *x, const tbk_kmerdb *y, uint64_t spec[256 * 256]);
+/* The entries of `base` by counter and by which of two partners hold them: spec[cls * 256 + c] is the number of entries of
+ * `base` with counter c and class cls.  Bit 0 of cls is set when `y` holds the key with a counter in [y_min, y_max], bit 1 is
+ * the same for `z`.  The ranges are taken literally - 1 <= min <= max <= 255, TBK_ERR_INVALID otherwise - and are NOT the
+ * "2 or more" rule of the subtractions above: a full partner is asked with min = 2 to ignore its once-seen k-mers.  Row 0 of
+ * every class is 0, and the four classes of a counter sum to the entries of `base` with that counter.  One launch over `base`;
+ * the call holds 8 KiB beside the inputs.  With base = the child and the parents as partners, class 0 is what the child holds
+ * of neither parent; with base = a parent, partners the other parent and the child, class 0 | 2 is that parent's own k-mers
+ * and class 2 those of them the child inherited. */
+int tbk_kmerdb_origin_spectrum(const tbk_kmerdb *base, const tbk_kmerdb *y, uint32_t y_min, uint32_t y_max,
+                               const tbk_kmerdb *z, uint32_t z_min, uint32_t z_max, uint64_t spec[4 * 256]);
 
 /* ---- counted k-mer dumps: a database from the text other counters print, and back ----------------------------
  * `kmc_dump`, `meryl print` (tab) and `jellyfish dump -c` (space) print one line per k-mer, KMER<sep>COUNT.

@@ -247,6 +247,10 @@ if HAS_KMERDB_FULL:
     _sig("tbk_kmerdb_file_floor", C.c_int, C.c_char_p, C.POINTER(C.c_int))
     _sig("tbk_kmerdb_union", C.c_int, _vp, _vp, C.POINTER(_vp))
     _sig("tbk_kmerdb_solid", C.c_int, _vp, C.POINTER(_vp))
+HAS_DB_COMPARE = hasattr(lib, "tbk_kmerdb_joint_spectrum")  # (variant builds of tools/build_variant.sh may predate the comparisons)
+if HAS_DB_COMPARE:
+    _sig("tbk_kmerdb_joint_spectrum", C.c_int, _vp, _vp, _vp)
+    _sig("tbk_kmerdb_origin_spectrum", C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp)
 HAS_DB_QUERY = hasattr(lib, "tbk_kmerdb_query_create")  # (variant builds of tools/build_variant.sh may predate the database query)
 if HAS_DB_QUERY:
     _sig("tbk_kmerdb_query_create", C.c_int, _vp, C.c_int, C.POINTER(_vp))

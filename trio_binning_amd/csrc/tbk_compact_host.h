@@ -54,6 +54,18 @@ hipError_t tbk_launch_dump_fold(const uint64_t *d_keys, const uint8_t *d_counts,
 hipError_t tbk_launch_kmerdb_union_scatter(const uint64_t *a_keys, const uint8_t *a_counts, uint64_t n_a, const uint64_t *b_keys,
                                            const uint8_t *b_counts, uint64_t n_b, const uint64_t *d_flags, const unsigned long long *d_tile_offsets,
                                            uint64_t *d_out_keys, uint8_t *d_out_counts, uint64_t n_out, hipStream_t stream);
+
+// The comparisons (tbk_compare.hip) compact nothing: they stride over the tiles of the database they walk and tally.  d_spec
+// holds 256 * 256 words (joint: cell cx * 256 + cy) or 4 * 256 (origin: cell class * 256 + c), zeroed by the caller; `keep`
+// has bit `class` set for every class that is tallied (15: all four).
+hipError_t tbk_launch_kmerdb_joint_spectrum(const uint64_t *x_keys, const uint8_t *x_counts, uint64_t n_x, const uint64_t *y_keys,
+                                            const uint8_t *y_counts, uint64_t n_y, unsigned long long *d_spec, hipStream_t stream);
+hipError_t tbk_launch_kmerdb_origin_spectrum(const uint64_t *base_keys, const uint8_t *base_counts, uint64_t n, const uint64_t *y_keys,
+                                             const uint8_t *y_counts, uint64_t n_y, uint32_t y_min, uint32_t y_max, const uint64_t *z_keys,
+                                             const uint8_t *z_counts, uint64_t n_z, uint32_t z_min, uint32_t z_max, uint32_t keep,
+                                             unsigned long long *d_spec, hipStream_t stream);
+// `blocks` under the entry cap of tbk_count_set_grid_caps_ (tbk_count_kernels.hip), for strided launches in other files
+unsigned tbk_count_entry_grid_(uint64_t blocks);
 }
 
 // What a compaction over n entries holds on the device between its flag kernel and its scatter: n / 8 + n / 64 bytes.

@@ -1318,6 +1318,54 @@ extern "C" int tbk_kmerdb_union(const tbk_kmerdb *a, const tbk_kmerdb *b, tbk_km
     return TBK_OK;
 }
 
+// ---- two or three databases held against each other: the joint and the origin spectrum (tbk_compare.hip) ---------------------
+// Either floor in any position and nothing but reads of the inputs; beside them the spectrum itself on the device (512 KiB or
+// 8 KiB), zeroed, tallied into and copied home.
+static int compare_check(const char *who, const tbk_kmerdb *first, const tbk_kmerdb *other, const char *what_other) {
+    if (first->k != other->k) return cfail(TBK_ERR_INVALID, "%s: the databases have different k (%d, and %s %d)", who, first->k, what_other, other->k);
+    if (first->device != other->device) return cfail(TBK_ERR_INVALID, "%s: the databases live on different devices", who);
+    return kmerdb_same_space(first, other, what_other);
+}
+
+// runs `launch` on a zeroed device array of `cells` words and copies it to spec
+template <typename Launch>
+static int compare_run(const char *who, int device, size_t cells, uint64_t *spec, Launch launch) {
+    const int rc = kmerdb_device(device);
+    if (rc) return rc;
+    unsigned long long *d_spec = nullptr;
+    hipError_t e = hipMalloc((void **)&d_spec, cells * sizeof *d_spec);
+    if (e == hipSuccess) e = hipMemset(d_spec, 0, cells * sizeof *d_spec);
+    if (e == hipSuccess) e = launch(d_spec);
+    if (e == hipSuccess) e = hipMemcpy(spec, d_spec, cells * sizeof *d_spec, hipMemcpyDeviceToHost);
+    if (d_spec) (void)hipFree(d_spec);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    return TBK_OK;
+}
+
+extern "C" int tbk_kmerdb_joint_spectrum(const tbk_kmerdb *x, const tbk_kmerdb *y, uint64_t spec[256 * 256]) {
+    if (!x || !y || !spec) return cfail(TBK_ERR_INVALID, "tbk_kmerdb_joint_spectrum: NULL argument");
+    if (compare_check("tbk_kmerdb_joint_spectrum", x, y, "the second")) return TBK_ERR_INVALID;
+    return compare_run("tbk_kmerdb_joint_spectrum", x->device, 256 * 256, spec, [&](unsigned long long *d_spec) {
+        return tbk_launch_kmerdb_joint_spectrum(x->d_keys, x->d_counts, x->n, y->d_keys, y->d_counts, y->n, d_spec, nullptr);
+    });
+}
+
+extern "C" int tbk_kmerdb_origin_spectrum(const tbk_kmerdb *base, const tbk_kmerdb *y, uint32_t y_min, uint32_t y_max, const tbk_kmerdb *z,
+                                          uint32_t z_min, uint32_t z_max, uint64_t spec[4 * 256]) {
+    if (!base || !y || !z || !spec) return cfail(TBK_ERR_INVALID, "tbk_kmerdb_origin_spectrum: NULL argument");
+    if (compare_check("tbk_kmerdb_origin_spectrum", base, y, "the second") || compare_check("tbk_kmerdb_origin_spectrum", base, z, "the third"))
+        return TBK_ERR_INVALID;
+    if (y_min < 1 || y_min > y_max || y_max > 255 || z_min < 1 || z_min > z_max || z_max > 255)
+        return cfail(TBK_ERR_INVALID, "tbk_kmerdb_origin_spectrum: counter ranges [%u, %u] and [%u, %u]: need 1 <= min <= max <= 255", y_min, y_max, z_min, z_max);
+    return compare_run("tbk_kmerdb_origin_spectrum", base->device, 4 * 256, spec, [&](unsigned long long *d_spec) {
+        return tbk_launch_kmerdb_origin_spectrum(base->d_keys, base->d_counts, base->n, y->d_keys, y->d_counts, y->n, y_min, y_max, z->d_keys,
+                                                 z->d_counts, z->n, z_min, z_max, 15u, d_spec, nullptr);
+    });
+}
+
 // (measurement hook, not in tbk.h: tools/measure_union.py makes databases of 1e8 entries where they lie.  Takes over d_keys and
 // d_counts - device memory of hipMalloc, freed with the database - once the pass that checks a loaded file has found them in
 // order, within 2k bits and at or above the floor; the histogram is that pass's tally, row 0 = n.)

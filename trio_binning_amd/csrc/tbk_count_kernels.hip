@@ -23,7 +23,8 @@
 
 // (test hook, not in tbk.h: caps on the grids of this file's strided launches, so that a small input takes the later trips of
 // their loops.  stream_blocks holds the launches that stride over reads, chunks or passes - separate, retain, both count
-// launches - and entry_blocks those that stride over table slots or database entries; 0 = no cap, the state at load.  The
+// launches - and entry_blocks those that stride over table slots, database entries or a database's tiles (tbk_compare.hip,
+// through tbk_count_entry_grid_); 0 = no cap, the state at load.  The
 // tile-per-block launches of tbk_compact.h and the rocPRIM scan and sorts take no cap.  Plain globals, read at every launch of
 // the process: for a single-threaded test that puts (0, 0) back.)
 static uint32_t g_stream_blocks = 0, g_entry_blocks = 0;
@@ -34,6 +35,8 @@ extern "C" int tbk_count_set_grid_caps_(uint32_t stream_blocks, uint32_t entry_b
 }
 static inline unsigned stream_grid(uint64_t blocks) { return (unsigned)(g_stream_blocks && blocks > g_stream_blocks ? g_stream_blocks : blocks); }
 static inline unsigned entry_grid(uint64_t blocks) { return (unsigned)(g_entry_blocks && blocks > g_entry_blocks ? g_entry_blocks : blocks); }
+// (the same cap for the launches of tbk_compare.hip, which stride over a database's tiles)
+extern "C" unsigned tbk_count_entry_grid_(uint64_t blocks) { return entry_grid(blocks); }
 
 // Copy reads that lie back to back into a stream where every read is followed by one 'N', upper-
 // casing on the way (KMC counts lower-case bases like upper-case ones): a window can then never

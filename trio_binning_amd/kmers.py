@@ -1181,6 +1181,28 @@ class KmerDatabase:
         check(lib.tbk_kmerdb_solid(self._h, C.byref(h)))
         return KmerDatabase(h)
 
+    def joint_spectrum(self, other: "KmerDatabase") -> np.ndarray:
+        """The joint k-mer spectrum of two databases (``tbk_kmerdb_joint_spectrum``), shape (256, 256), uint64: cell
+        ``[cx, cy]`` is the number of distinct k-mers with counter ``cx`` here and ``cy`` in ``other``, 0 standing for "holds no
+        entry" (below the floor, or never seen).  Either floor in either place; one k, one device and one space, ``ValueError``
+        otherwise."""
+        spec = np.zeros((256, 256), dtype=np.uint64)
+        check(lib.tbk_kmerdb_joint_spectrum(self._h, other._h, spec.ctypes.data))
+        return spec
+
+    def origin_spectrum(self, y: "KmerDatabase", z: "KmerDatabase", y_range: Tuple[int, int] = (1, 255),
+                        z_range: Tuple[int, int] = (1, 255)) -> np.ndarray:
+        """This database's entries by counter and by which of two partners hold them (``tbk_kmerdb_origin_spectrum``), shape
+        (4, 256), uint64: row ``cls`` has bit 0 set when ``y`` holds the k-mer with a counter in ``y_range`` (inclusive, taken
+        literally: 1 <= min <= max <= 255), bit 1 the same for ``z``.  ``ValueError`` for a range outside that, or databases
+        of different k, device or space."""
+        bounds = [int(v) for v in (*y_range, *z_range)]
+        if any(not 0 <= v <= 0xFFFFFFFF for v in bounds):
+            raise ValueError("counter ranges {} and {}: need 1 <= min <= max <= 255".format(tuple(y_range), tuple(z_range)))
+        spec = np.zeros((4, 256), dtype=np.uint64)
+        check(lib.tbk_kmerdb_origin_spectrum(self._h, y._h, bounds[0], bounds[1], z._h, bounds[2], bounds[3], spec.ctypes.data))
+        return spec
+
     def query(self, copies: bool = False) -> "DatabaseQuery":
         """A session that scores sequences against this database (``DatabaseQuery``); ``copies`` keeps a 32-bit counter
         per entry for the copy spectrum (4 bytes per k-mer more)."""
