@@ -931,6 +931,54 @@ int tbk_kmerdb_joint_spectrum(const tbk_kmerdb *x, const tbk_kmerdb *y, uint64_t
  * and class 2 those of them the child inherited. */
 int tbk_kmerdb_origin_spectrum(const tbk_kmerdb *base, const tbk_kmerdb *y, uint32_t y_min, uint32_t y_max,
                                const tbk_kmerdb *z, uint32_t z_min, uint32_t z_max, uint64_t spec[4 * 256]);
+/* A selection that stays a database: the entries of `base` that up to two partners let pass, with a counter of choice - the
+ * hap-mer databases of Merqury's hapmers.sh ("the parental k-mers the child inherited, with the child's counters"), the k-mers
+ * two lanes share, a library minus a contaminant.  Every other join here ends in text, in keys without counters or in a tally.
+ * WHICH ENTRIES ARE KEPT.  An entry of `base` is kept when its counter lies in [o->min_count, o->max_count] and, for every
+ * partner, "the partner holds the key with a counter in the partner's [min_count, max_count]" is true for TBK_SELECT_REQUIRE
+ * and false for TBK_SELECT_EXCLUDE.  All ranges are taken literally - 1 <= min <= max <= 255, as in
+ * tbk_kmerdb_origin_spectrum - and are NOT the "2 or more" rule of the subtractions: a full partner is asked with min = 2 to
+ * ignore its once-seen k-mers, a floor-2 partner asked with [1, 255] means "holds the key at all".  n_partners is 0, 1 or 2
+ * (`partners` may be NULL for 0); more partners are done by chaining calls.  A database may appear more than once and may be
+ * `base` itself; either floor is accepted in every position.
+ * THE COUNTER OF A KEPT ENTRY.  TBK_SELECT_COUNTER_BASE: the base's.  _MIN: the minimum of the base's counter and every REQUIRE
+ * partner's.  _SUM: min(255, base + the REQUIRE partners'), added in 32 bits.  EXCLUDE partners never contribute; with no
+ * REQUIRE partner all three rules give the base's counter.
+ * THE RESULT is a database in the FULL form (floor 1) whatever the inputs' floors were: its keys are the kept ranks in base's
+ * order, which stays ascending, so nothing is sorted.  Rows 1..255 of its histogram are tallied from its own counters, row 0 is
+ * n, reads and bases are 0 - a selection is no library, as an import without --reads is none; k and the space (plain or
+ * compressed) are base's.  Full is the form that states exactly the multiset held: tbk_kmerdb_union of two selections is exact
+ * multiset addition, the query session takes it as it is, and tbk_kmerdb_solid (load_solid_database) drops its counter-1
+ * entries and nothing else.  A floor-2 header would claim that every k-mer of a library seen twice is here; a selection makes
+ * no such claim.  An empty selection, or an empty base, is TBK_OK and a valid database of n = 0 (its file: 2096 bytes).
+ * REFUSALS are TBK_ERR_INVALID with the reason in tbk_last_error(): a NULL base, o, out or partner's db; n_partners outside
+ * 0..2; a mode, counter rule or range outside the above; a different k, device or space among the databases (the messages of
+ * the spectra above).  *out is NULL after every error; TBK_ERR_NOMEM leaves every input as it was and the device usable.
+ * LAUNCHES (csrc/tbk_select.hip): flag - one block per tile of 1024 entries of base finds the tile's bounds in both partners,
+ * and every entry tests its own counter, then the first partner, then the second only if the first let it pass (EXCLUDE
+ * partners are asked first); the scan of the tile counts; the scatter of keys and counters - for _MIN and _SUM with one more
+ * bounded bisection per kept entry and REQUIRE partner, the kept entries dealt to consecutive threads so that a wave bisects
+ * with all its lanes; the tally of the output's counters.  No block waits for another.  The
+ * output is allocated at its exact size once the number kept is known; beside it the call holds n/8 + n/64 bytes for base's n
+ * entries and 2 KiB, freed before it returns. */
+#define TBK_SELECT_REQUIRE 1
+#define TBK_SELECT_EXCLUDE 2
+#define TBK_SELECT_COUNTER_BASE 0
+#define TBK_SELECT_COUNTER_MIN  1
+#define TBK_SELECT_COUNTER_SUM  2
+typedef struct tbk_select_partner {
+    const tbk_kmerdb *db;
+    uint32_t min_count, max_count;  /* the partner's counter range, 1 <= min <= max <= 255 */
+    int mode;                       /* TBK_SELECT_REQUIRE or TBK_SELECT_EXCLUDE */
+} tbk_select_partner;
+typedef struct tbk_select_options {
+    size_t size;                    /* sizeof(tbk_select_options) of the caller (tbk_select_options_init sets it) */
+    uint32_t min_count, max_count;  /* base's counter range, 1 <= min <= max <= 255 */
+    int counter;                    /* TBK_SELECT_COUNTER_BASE, _MIN or _SUM */
+} tbk_select_options;
+void tbk_select_options_init(tbk_select_options *o);  /* 1, 255, TBK_SELECT_COUNTER_BASE */
+int tbk_kmerdb_select(const tbk_kmerdb *base, const tbk_select_partner *partners, int n_partners, const tbk_select_options *o,
+                      tbk_kmerdb **out);
 
 /* ---- counted k-mer dumps: a database from the text other counters print, and back ----------------------------
  * `kmc_dump`, `meryl print` (tab) and `jellyfish dump -c` (space) print one line per k-mer, KMER<sep>COUNT.

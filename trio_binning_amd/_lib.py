@@ -251,6 +251,22 @@ HAS_DB_COMPARE = hasattr(lib, "tbk_kmerdb_joint_spectrum")  # (variant builds of
 if HAS_DB_COMPARE:
     _sig("tbk_kmerdb_joint_spectrum", C.c_int, _vp, _vp, _vp)
     _sig("tbk_kmerdb_origin_spectrum", C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp)
+class SelectPartner(C.Structure):
+    """tbk_select_partner (include/tbk.h)."""
+    _fields_ = [("db", C.c_void_p), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("mode", C.c_int)]
+
+
+class SelectOptions(C.Structure):
+    """tbk_select_options (include/tbk.h)."""
+    _fields_ = [("size", C.c_size_t), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("counter", C.c_int)]
+
+
+SELECT_REQUIRE, SELECT_EXCLUDE = 1, 2
+SELECT_COUNTERS = {"base": 0, "min": 1, "sum": 2}
+HAS_DB_SELECT = hasattr(lib, "tbk_kmerdb_select")  # (variant builds of tools/build_variant.sh may predate the selection)
+if HAS_DB_SELECT:
+    _sig("tbk_select_options_init", None, C.POINTER(SelectOptions))
+    _sig("tbk_kmerdb_select", C.c_int, _vp, C.POINTER(SelectPartner), C.c_int, C.POINTER(SelectOptions), C.POINTER(_vp))
 HAS_DB_QUERY = hasattr(lib, "tbk_kmerdb_query_create")  # (variant builds of tools/build_variant.sh may predate the database query)
 if HAS_DB_QUERY:
     _sig("tbk_kmerdb_query_create", C.c_int, _vp, C.c_int, C.POINTER(_vp))

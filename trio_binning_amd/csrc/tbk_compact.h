@@ -1,6 +1,6 @@
 // tbk_compact.h — the kernels' side of the tile compaction (tbk_compact_host.h has the tile, the buffers and the launchers):
-// the flag loop, the scatter's prologue and placement, and the bounds of a tile in a second database, each written once for
-// tbk_count_kernels.hip and tbk_dump.hip.  Every helper is for a block of 256 threads that owns tile blockIdx.x, inlines
+// the flag loop, the scatter's prologue and placement, the bounds of a tile in a second database and the questions an entry
+// asks there, each written once for tbk_count_kernels.hip, tbk_dump.hip, tbk_compare.hip and tbk_select.hip.  Every helper is for a block of 256 threads that owns tile blockIdx.x, inlines
 // into its kernel and takes what varies as a lambda.
 #pragma once
 #include "tbk_compact_host.h"
@@ -13,6 +13,16 @@ __device__ __forceinline__ bool db_counter_selected(uint32_t c, uint32_t ci, uin
 __device__ __forceinline__ bool db_absent(const uint64_t *__restrict__ keys, uint64_t lo, uint64_t hi, uint64_t n, uint64_t key) {
     const uint64_t at = db_lower_bound(keys, lo, hi, key);  // (at <= hi <= n)
     return !(at < n && keys[at] == key);
+}
+
+// Does the partner hold `key` with a counter in [c_min, c_max], taken literally?  lo .. hi: the tile's bounds there
+// (tbk_compare.hip, tbk_select.hip).
+__device__ __forceinline__ bool db_held_in_range(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ counts, uint64_t lo, uint64_t hi,
+                                                 uint64_t n, uint64_t key, uint32_t c_min, uint32_t c_max) {
+    const uint64_t at = db_lower_bound(keys, lo, hi, key);  // (at <= hi <= n)
+    if (!(at < n && keys[at] == key)) return false;
+    const uint32_t c = counts[at];
+    return c >= c_min && c <= c_max;
 }
 
 // flag: entry i < n of the tile is kept when pred(i), which is called for no other i.  flags takes the tile's TBK_DBT_WORDS
@@ -91,6 +101,41 @@ __device__ __forceinline__ void compact_scatter_tile(uint64_t n, const uint64_t 
         const uint64_t mask = w.mask[word];
         const uint64_t i = tile * TBK_DBT_TILE + (uint64_t)word * 64 + lane;
         if (((mask >> lane) & 1ull) && i < n) place(i, base + w.before[word] + compact_below(mask, lane));
+    }
+}
+
+// the place of the r-th set bit of mask, counted from bit 0 (r < popcount(mask)): six halvings
+__device__ __forceinline__ uint32_t compact_nth_bit(uint64_t mask, uint32_t r) {
+    uint32_t at = 0;
+    for (uint32_t width = 32; width; width >>= 1) {
+        const uint32_t below = (uint32_t)__popcll(mask & ((1ull << width) - 1ull));
+        if (r >= below) {
+            r -= below;
+            mask >>= width;
+            at += width;
+        }
+    }
+    return at;
+}
+
+// The same scatter with the flagged entries dealt to consecutive threads: thread t takes the t-th, t + 256-th, ... flagged
+// entry of the tile, so a wave whose `place` is expensive (a bisection per entry) works with all its lanes however few
+// entries of the tile are flagged - in compact_scatter_tile a wave pays for its 64 entries when one of them is.  The entry is
+// found from the word table: the word whose `before` covers the place, then the bit within it.
+template <typename Place>
+__device__ __forceinline__ void compact_scatter_tile_dense(uint64_t n, const uint64_t *__restrict__ flags,
+                                                           const unsigned long long *__restrict__ tile_offsets, Place place) {
+    __shared__ CompactWords w;
+    compact_load_words(w, flags, 0);
+    const uint64_t tile = blockIdx.x;
+    const uint64_t base = tile_offsets[tile];
+    const uint32_t total = w.before[TBK_DBT_WORDS - 1] + (uint32_t)__popcll(w.mask[TBK_DBT_WORDS - 1]);  // (<= TBK_DBT_TILE)
+    for (uint32_t j = threadIdx.x; j < total; j += 256) {
+        uint32_t word = 0;
+        for (uint32_t step = TBK_DBT_WORDS / 2; step; step >>= 1)  // the last word whose `before` is <= j: it holds the j-th flagged entry
+            if (w.before[word + step] <= j) word += step;
+        const uint64_t i = tile * TBK_DBT_TILE + (uint64_t)word * 64 + compact_nth_bit(w.mask[word], j - w.before[word]);
+        if (i < n) place(i, base + j);
     }
 }
 

@@ -55,6 +55,26 @@ hipError_t tbk_launch_kmerdb_union_scatter(const uint64_t *a_keys, const uint8_t
                                            const uint8_t *b_counts, uint64_t n_b, const uint64_t *d_flags, const unsigned long long *d_tile_offsets,
                                            uint64_t *d_out_keys, uint8_t *d_out_counts, uint64_t n_out, hipStream_t stream);
 
+// The selection into a database (tbk_select.hip, tbk_kmerdb_select): a partner is the arrays of a database, the literal
+// counter range it is asked with and what the answer must be - `require` 1: it holds the key in that range, 0: it does not.
+// A partner that is not there has n = 0, NULL arrays and require = 0: it never rejects and is never dereferenced.
+struct TbkSelectPartner {
+    const uint64_t *keys;
+    const uint8_t *counts;
+    uint64_t n;
+    uint32_t c_min, c_max;
+    uint32_t require;
+};
+// flag: the entries of base with a counter in [c_min, c_max] that both partners let pass, p0 asked before p1
+hipError_t tbk_launch_kmerdb_select_flag(const uint64_t *base_keys, const uint8_t *base_counts, uint64_t n, uint32_t c_min, uint32_t c_max,
+                                         const TbkSelectPartner *p0, const TbkSelectPartner *p1, uint64_t *d_flags,
+                                         unsigned long long *d_tile_counts, hipStream_t stream);
+// scatter with a counter made of the base's and the partners' (rule: TBK_SELECT_COUNTER_MIN or _SUM; both partners are REQUIRE
+// ones, or not there); the rule that keeps the base's counter is tbk_launch_kmerdb_scatter_pairs
+hipError_t tbk_launch_kmerdb_select_scatter(int rule, const uint64_t *base_keys, const uint8_t *base_counts, uint64_t n, const TbkSelectPartner *r0,
+                                            const TbkSelectPartner *r1, const uint64_t *d_flags, const unsigned long long *d_tile_offsets,
+                                            uint64_t *d_out_keys, uint8_t *d_out_counts, uint64_t n_out, hipStream_t stream);
+
 // The comparisons (tbk_compare.hip) compact nothing: they stride over the tiles of the database they walk and tally.  d_spec
 // holds 256 * 256 words (joint: cell cx * 256 + cy) or 4 * 256 (origin: cell class * 256 + c), zeroed by the caller; `keep`
 // has bit `class` set for every class that is tallied (15: all four).

@@ -16,15 +16,6 @@
 constexpr uint64_t COMPARE_GRID = 2048;                           // 256 CUs x the 8 blocks of 4 waves a CU holds
 constexpr uint64_t COMPARE_MAX_TILES_PER_BLOCK = 1ull << 21;      // x 1024 entries: half of what an LDS cell counts
 
-// Does the partner hold `key` with a counter in [c_min, c_max]?  lo .. hi: the tile's bounds there.
-__device__ __forceinline__ bool db_held_in_range(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ counts, uint64_t lo, uint64_t hi,
-                                                 uint64_t n, uint64_t key, uint32_t c_min, uint32_t c_max) {
-    const uint64_t at = db_lower_bound(keys, lo, hi, key);  // (at <= hi <= n)
-    if (!(at < n && keys[at] == key)) return false;
-    const uint32_t c = counts[at];
-    return c >= c_min && c <= c_max;
-}
-
 // ---- tbk_kmerdb_origin_spectrum: the entries of `base` by counter and by which of two partners hold them -------------------
 // spec[cls * 256 + c] += entries of base with counter c and class cls; bit 0 of cls: y holds the key with a counter in
 // [y_min, y_max], bit 1: the same for z.  Two waves find the tile's two pairs of bounds side by side, as the inherited flag

@@ -1465,6 +1465,110 @@ extern "C" int tbk_kmerdb_solid(const tbk_kmerdb *src, tbk_kmerdb **out) {
     return TBK_OK;
 }
 
+// ---- a selection that stays a database (tbk_kmerdb_select; kernels: tbk_select.hip) -----------------------------------------
+extern "C" void tbk_select_options_init(tbk_select_options *o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->size = sizeof *o;
+    o->min_count = 1;
+    o->max_count = 255;
+    o->counter = TBK_SELECT_COUNTER_BASE;
+}
+
+static bool select_range_ok(uint32_t lo, uint32_t hi) { return lo >= 1 && lo <= hi && hi <= 255; }
+
+// The entries of base in their range that the partners let pass, as a full database: flag (EXCLUDE partners asked first),
+// scan, the output at its exact size, scatter (of base's pairs as they are when no REQUIRE partner's counter goes into the
+// result), tally for the header.  Beside the output: n / 8 + n / 64 bytes and the 2 KiB of the tally, freed before the
+// call returns.
+extern "C" int tbk_kmerdb_select(const tbk_kmerdb *base, const tbk_select_partner *partners, int n_partners, const tbk_select_options *opts,
+                                 tbk_kmerdb **out) {
+    const char *who = "tbk_kmerdb_select";
+    if (out) *out = nullptr;
+    if (!base || !opts || !out) return cfail(TBK_ERR_INVALID, "%s: NULL argument", who);
+    if (n_partners < 0 || n_partners > 2) return cfail(TBK_ERR_INVALID, "%s: %d partners: 0, 1 or 2 (chain calls for more)", who, n_partners);
+    if (n_partners && !partners) return cfail(TBK_ERR_INVALID, "%s: NULL argument", who);
+    tbk_select_options o;
+    tbk_select_options_init(&o);
+    if (opts->size < offsetof(tbk_select_options, counter) + sizeof(int) || opts->size > 4096)
+        return cfail(TBK_ERR_INVALID, "tbk_select_options.size = %zu: set it with tbk_select_options_init", (size_t)opts->size);
+    memcpy(&o, opts, std::min<size_t>(opts->size, sizeof o));
+    if (o.counter != TBK_SELECT_COUNTER_BASE && o.counter != TBK_SELECT_COUNTER_MIN && o.counter != TBK_SELECT_COUNTER_SUM)
+        return cfail(TBK_ERR_INVALID, "%s: counter rule %d: TBK_SELECT_COUNTER_BASE, _MIN or _SUM", who, o.counter);
+    if (!select_range_ok(o.min_count, o.max_count))
+        return cfail(TBK_ERR_INVALID, "%s: counter range [%u, %u] of the base: need 1 <= min <= max <= 255", who, o.min_count, o.max_count);
+    static const char *const place[2] = {"the first partner's", "the second partner's"};
+    for (int i = 0; i < n_partners; i++) {
+        const tbk_select_partner &p = partners[i];
+        if (!p.db) return cfail(TBK_ERR_INVALID, "%s: NULL argument (%s database)", who, place[i]);
+        if (p.mode != TBK_SELECT_REQUIRE && p.mode != TBK_SELECT_EXCLUDE)
+            return cfail(TBK_ERR_INVALID, "%s: mode %d of %s database: TBK_SELECT_REQUIRE or TBK_SELECT_EXCLUDE", who, p.mode, place[i]);
+        if (!select_range_ok(p.min_count, p.max_count))
+            return cfail(TBK_ERR_INVALID, "%s: counter range [%u, %u] of %s database: need 1 <= min <= max <= 255", who, p.min_count, p.max_count, place[i]);
+        if (compare_check(who, base, p.db, place[i])) return TBK_ERR_INVALID;
+    }
+    const int rc = kmerdb_device(base->device);
+    if (rc) return rc;
+    // EXCLUDE partners first, REQUIRE ones behind them: `ask` in the flag kernel's order, `join` the REQUIRE ones alone
+    const TbkSelectPartner none = {nullptr, nullptr, 0, 1, 255, 0};
+    TbkSelectPartner ask[2] = {none, none}, join[2] = {none, none};
+    int n_ask = 0, n_join = 0;
+    for (int mode : {TBK_SELECT_EXCLUDE, TBK_SELECT_REQUIRE})
+        for (int i = 0; i < n_partners; i++) {
+            const tbk_select_partner &p = partners[i];
+            if (p.mode != mode) continue;
+            const TbkSelectPartner t = {p.db->d_keys, p.db->d_counts, p.db->n, p.min_count, p.max_count, mode == TBK_SELECT_REQUIRE ? 1u : 0u};
+            ask[n_ask++] = t;
+            if (mode == TBK_SELECT_REQUIRE) join[n_join++] = t;
+        }
+    tbk_kmerdb *db = new tbk_kmerdb();
+    db->device = base->device; db->k = base->k; db->floor = 1; db->compressed = base->compressed;
+    unsigned long long total = 0, hist[256];
+    memset(hist, 0, sizeof hist);
+    if (base->n) {
+        Compaction sel;
+        unsigned long long *d_hist = nullptr;
+        hipError_t e = sel.reserve(base->n, nullptr);
+        if (e == hipSuccess) e = hipMalloc((void **)&d_hist, sizeof hist);
+        if (e == hipSuccess) e = hipMemset(d_hist, 0, sizeof hist);
+        if (e == hipSuccess)
+            e = tbk_launch_kmerdb_select_flag(base->d_keys, base->d_counts, base->n, o.min_count, o.max_count, &ask[0], &ask[1], sel.d_flags, sel.counts(), nullptr);
+        if (e == hipSuccess) e = sel.total(&total);
+        const bool sane = total <= base->n;  // (nothing is allocated or written by a count that cannot be)
+        const bool some = sane && total;
+        if (e == hipSuccess && some) e = hipMalloc((void **)&db->d_keys, total * sizeof(uint64_t));
+        if (e == hipSuccess && some) e = hipMalloc((void **)&db->d_counts, total);
+        if (e == hipSuccess && some) {
+            if (o.counter == TBK_SELECT_COUNTER_BASE || !n_join)
+                e = tbk_launch_kmerdb_scatter_pairs(base->d_keys, base->d_counts, base->n, sel.d_flags, sel.offsets(), db->d_keys, db->d_counts, total, nullptr);
+            else
+                e = tbk_launch_kmerdb_select_scatter(o.counter, base->d_keys, base->d_counts, base->n, &join[0], &join[1], sel.d_flags, sel.offsets(),
+                                                     db->d_keys, db->d_counts, total, nullptr);
+        }
+        if (e == hipSuccess && some) e = tbk_launch_kmerdb_tally(db->d_counts, total, d_hist, nullptr);
+        if (e == hipSuccess) e = hipMemcpy(hist, d_hist, sizeof hist, hipMemcpyDeviceToHost);
+        sel.release();
+        if (d_hist) (void)hipFree(d_hist);
+        if (e != hipSuccess || !sane) {
+            tbk_kmerdb_destroy(db);
+            (void)hipGetLastError();
+            if (e != hipSuccess)
+                return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "%s (%llu k-mers): %s", who, (unsigned long long)base->n, hipGetErrorString(e));
+            return cfail(TBK_ERR_HIP, "%s: %llu of %llu k-mers flagged", who, total, (unsigned long long)base->n);
+        }
+    }
+    uint64_t tallied = 0;
+    for (int i = 1; i < 256; i++) { db->hist[i] = hist[i]; tallied += hist[i]; }
+    db->hist[0] = total;
+    db->n = total;
+    if (hist[0] || tallied != total) {
+        tbk_kmerdb_destroy(db);
+        return cfail(TBK_ERR_HIP, "%s: %llu of %llu selected counters tallied, %llu of them 0", who, (unsigned long long)tallied, total, hist[0]);
+    }
+    *out = db;
+    return TBK_OK;
+}
+
 // =====================================================================================================================
 // Database query (tbk_kmerdb_query; kernels: tbk_query.hip): the counter the database holds for every window of a
 // batch of sequences - per-sequence totals, a histogram, the entries seen, their copies.  include/tbk.h has the rules.

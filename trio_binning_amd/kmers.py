@@ -1203,6 +1203,37 @@ class KmerDatabase:
         check(lib.tbk_kmerdb_origin_spectrum(self._h, y._h, bounds[0], bounds[1], z._h, bounds[2], bounds[3], spec.ctypes.data))
         return spec
 
+    def select(self, min_count: int = 1, max_count: int = 255, require=(), exclude=(), counter: str = "base") -> "KmerDatabase":
+        """A selection of this database's entries that is a database again (``tbk_kmerdb_select``): those with a counter in
+        [min_count, max_count] that every partner of ``require`` holds with a counter in that partner's range and no partner
+        of ``exclude`` does.  A partner is ``(KmerDatabase, min, max)`` or a bare ``KmerDatabase``, which means
+        ``(db, 1, 255)``; ranges are taken literally, 1 <= min <= max <= 255; at most two partners in all (chain calls for
+        more).  ``counter``: "base" keeps this database's counters, "min" takes the minimum with the ``require`` partners',
+        "sum" adds them, capped at 255.  The result is a full database (``floor == 1``) in this database's order, of its k and
+        space, with ``reads_added == bases_added == 0``; it may be empty.  ``ValueError`` for a range, rule or number of
+        partners outside that, or databases of different k, device or space."""
+        if counter not in _lib.SELECT_COUNTERS:
+            raise ValueError("counter = {!r}: one of 'base', 'min', 'sum'".format(counter))
+        asked = []
+        for mode, group in ((_lib.SELECT_REQUIRE, require), (_lib.SELECT_EXCLUDE, exclude)):
+            for partner in group:
+                db, lo, hi = (partner, 1, 255) if isinstance(partner, KmerDatabase) else partner
+                asked.append((db, int(lo), int(hi), mode))
+        if len(asked) > 2:
+            raise ValueError("{} partners: a selection takes at most two (chain calls for more)".format(len(asked)))
+        bounds = [int(min_count), int(max_count)] + [v for _, lo, hi, _ in asked for v in (lo, hi)]
+        if any(not 0 <= v <= 0xFFFFFFFF for v in bounds):
+            raise ValueError("counter ranges {}: need 1 <= min <= max <= 255".format(list(zip(bounds[::2], bounds[1::2]))))
+        o = _lib.SelectOptions()
+        lib.tbk_select_options_init(C.byref(o))
+        o.min_count, o.max_count, o.counter = bounds[0], bounds[1], _lib.SELECT_COUNTERS[counter]
+        partners = (_lib.SelectPartner * max(1, len(asked)))()
+        for slot, (db, lo, hi, mode) in zip(partners, asked):
+            slot.db, slot.min_count, slot.max_count, slot.mode = (db._h.value if db._h is not None else None), lo, hi, mode
+        h = C.c_void_p()
+        check(lib.tbk_kmerdb_select(self._h, partners, len(asked), C.byref(o), C.byref(h)))
+        return KmerDatabase(h)
+
     def query(self, copies: bool = False) -> "DatabaseQuery":
         """A session that scores sequences against this database (``DatabaseQuery``); ``copies`` keeps a 32-bit counter
         per entry for the copy spectrum (4 bytes per k-mer more)."""
