@@ -979,6 +979,65 @@ typedef struct tbk_select_options {
 void tbk_select_options_init(tbk_select_options *o);  /* 1, 255, TBK_SELECT_COUNTER_BASE */
 int tbk_kmerdb_select(const tbk_kmerdb *base, const tbk_select_partner *partners, int n_partners, const tbk_select_options *o,
                       tbk_kmerdb **out);
+/* The het-mer pairs of ONE database: the look inside a library that the k-mer-pair analysis of Smudgeplot / PloidyPlot takes
+ * from the reads alone - how heterozygous is it, is it diploid at all - and, with the parents' databases beside the child's,
+ * how many of its heterozygous sites the parents' k-mers mark.  All integer, all exact.
+ * PARTNERS.  k is odd and m = (k - 1) / 2: position m is the only one reverse complement maps to itself.  For a canonical k-mer
+ * x (the lexicographic minimum of a k-mer and its reverse complement, as the counter has it), substitute each of the three
+ * other bases at position m, make each result canonical and drop x itself: the distinct canonical k-mers that remain are the
+ * MIDDLE PARTNERS of x.  They are a set: a variant can be x itself (AAT -> ATT, its reverse complement) and two variants can be
+ * one k-mer (whenever the flanks are each other's reverse complement: AAT has the single partner ACT).  A k-mer has 3 partners,
+ * or 1 when its flanks are self-reverse-complementary; the relation is symmetric and transitive, so classes hold 4 or 2 k-mers.
+ * CANDIDATES AND PAIRS.  The candidates are the entries of `db` whose counter lies in [o->min_count, o->max_count], taken
+ * literally, 1 <= min <= max <= 255; either floor is accepted.  A candidate's partners in range are its middle partners that
+ * are candidates too, 0 to 3 of them.  A HET-MER PAIR is a candidate with exactly one partner in range, and that partner
+ * (which then has exactly one, the first).  The MINOR member of a pair has the lower counter, on a tie the lower rank.
+ * THE RESULT.  candidates; partners[j], the candidates with j partners in range (partners[1] == 2 * pairs, partners[2] % 3 == 0,
+ * partners[3] % 4 == 0); pairs; spec[c_minor * 256 + c_major], whose cells with c_minor > c_major and whose row and column 0
+ * are 0 and which sums to pairs; origin[cls_minor * 4 + cls_major], where cls is the class of tbk_kmerdb_origin_spectrum: bit 0
+ * set when o->y holds the key with a counter in [y_min, y_max], bit 1 likewise for o->z.  A partner that is NULL contributes
+ * bit 0; the 16 cells sum to pairs, and with neither partner all pairs are in origin[0].  With o->want_pairs, *out_pairs
+ * takes the pairs themselves, pairs records in memory of tbk_host_alloc that is the caller's to tbk_host_free (NULL when there
+ * is none, and after every error): ranks in the form tbk_kmerdb_read hands out, ascending by the rank of each pair's
+ * lower-ranked member.  out_pairs may be NULL when no pairs are wanted.
+ * REFUSALS, TBK_ERR_INVALID with the reason in tbk_last_error() before any kernel runs: an even k (the middle base must be its
+ * own mirror under reverse complement); a range outside 1 <= min <= max <= 255; a partner of another k, device or space; a
+ * database of more than 2^32 - 1 entries (the directory's offsets are 32-bit words and its last one is n itself; y and z are
+ * bisected with 64-bit offsets and may be larger).  An empty database is legal: everything is zero.  Homopolymer-compressed
+ * databases are accepted when all given are: a variant that puts two equal bases side by side is no compressed k-mer, is in no
+ * such database and is simply never found - no rule is needed.  TBK_ERR_NOMEM leaves every input as it was and the device
+ * usable.
+ * LAUNCHES (csrc/tbk_hetmer.hip): the directory over the top floor(log2 n) - 1 bits of the rank (the query session's kernel);
+ * the tally - blocks stride over tiles of 1024 entries, every candidate makes its three variants canonical, drops the equal
+ * ones and searches the rest side by side through the directory, and only pairs ask y and z; with want_pairs also flag, the
+ * scan of the tile counts and a scatter that finds each pair's partner again.  No block waits for another.  Beside the inputs
+ * and the records the call holds the directory (4 * (2^P + 1) bytes, at most 2 n + 4 and at most 1 GiB), the two result
+ * matrices (512 KiB + 176 bytes) and, with want_pairs, n/8 + n/64 bytes; all freed before it returns. */
+typedef struct tbk_hetmer_pair {
+    uint64_t minor, major;        /* the two ranks */
+    uint8_t c_minor, c_major;     /* their counters, c_minor <= c_major */
+    uint8_t cls_minor, cls_major; /* their origin classes, 0..3 */
+    uint8_t reserved[4];          /* 0 */
+} tbk_hetmer_pair;
+typedef struct tbk_hetmer_options {
+    size_t size;                    /* sizeof(tbk_hetmer_options) of the caller (tbk_hetmer_options_init sets it) */
+    uint32_t min_count, max_count;  /* the candidates' counter range, 1 <= min <= max <= 255 */
+    const tbk_kmerdb *y, *z;        /* partner databases, each may be NULL */
+    uint32_t y_min, y_max;          /* 1 <= min <= max <= 255, checked whether or not y is given */
+    uint32_t z_min, z_max;
+    int want_pairs;                 /* not 0: the records too */
+} tbk_hetmer_options;
+typedef struct tbk_hetmer_result {
+    size_t size;                    /* sizeof(tbk_hetmer_result) of the caller (tbk_hetmer_result_init sets it) */
+    uint64_t candidates;
+    uint64_t partners[4];
+    uint64_t pairs;
+    uint64_t origin[16];
+} tbk_hetmer_result;
+void tbk_hetmer_options_init(tbk_hetmer_options *o);  /* 1, 255, no partners, their ranges 1..255, no pairs */
+void tbk_hetmer_result_init(tbk_hetmer_result *r);    /* the size, everything else 0 */
+int tbk_kmerdb_hetmers(const tbk_kmerdb *db, const tbk_hetmer_options *o, tbk_hetmer_result *result, uint64_t spec[256 * 256],
+                       tbk_hetmer_pair **out_pairs);
 
 /* ---- counted k-mer dumps: a database from the text other counters print, and back ----------------------------
  * `kmc_dump`, `meryl print` (tab) and `jellyfish dump -c` (space) print one line per k-mer, KMER<sep>COUNT.

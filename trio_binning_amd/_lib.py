@@ -267,6 +267,28 @@ HAS_DB_SELECT = hasattr(lib, "tbk_kmerdb_select")  # (variant builds of tools/bu
 if HAS_DB_SELECT:
     _sig("tbk_select_options_init", None, C.POINTER(SelectOptions))
     _sig("tbk_kmerdb_select", C.c_int, _vp, C.POINTER(SelectPartner), C.c_int, C.POINTER(SelectOptions), C.POINTER(_vp))
+class HetmerPair(C.Structure):
+    """tbk_hetmer_pair (include/tbk.h)."""
+    _fields_ = [("minor", C.c_uint64), ("major", C.c_uint64), ("c_minor", C.c_uint8), ("c_major", C.c_uint8), ("cls_minor", C.c_uint8),
+                ("cls_major", C.c_uint8), ("reserved", C.c_uint8 * 4)]
+
+
+class HetmerOptions(C.Structure):
+    """tbk_hetmer_options (include/tbk.h)."""
+    _fields_ = [("size", C.c_size_t), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("y", C.c_void_p), ("z", C.c_void_p),
+                ("y_min", C.c_uint32), ("y_max", C.c_uint32), ("z_min", C.c_uint32), ("z_max", C.c_uint32), ("want_pairs", C.c_int)]
+
+
+class HetmerResult(C.Structure):
+    """tbk_hetmer_result (include/tbk.h)."""
+    _fields_ = [("size", C.c_size_t), ("candidates", C.c_uint64), ("partners", C.c_uint64 * 4), ("pairs", C.c_uint64), ("origin", C.c_uint64 * 16)]
+
+
+HAS_DB_HETMERS = hasattr(lib, "tbk_kmerdb_hetmers")  # (variant builds of tools/build_variant.sh may predate the het-mer pairs)
+if HAS_DB_HETMERS:
+    _sig("tbk_hetmer_options_init", None, C.POINTER(HetmerOptions))
+    _sig("tbk_hetmer_result_init", None, C.POINTER(HetmerResult))
+    _sig("tbk_kmerdb_hetmers", C.c_int, _vp, C.POINTER(HetmerOptions), C.POINTER(HetmerResult), _vp, C.POINTER(_vp))
 HAS_DB_QUERY = hasattr(lib, "tbk_kmerdb_query_create")  # (variant builds of tools/build_variant.sh may predate the database query)
 if HAS_DB_QUERY:
     _sig("tbk_kmerdb_query_create", C.c_int, _vp, C.c_int, C.POINTER(_vp))

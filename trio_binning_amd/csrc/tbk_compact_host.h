@@ -86,6 +86,32 @@ hipError_t tbk_launch_kmerdb_origin_spectrum(const uint64_t *base_keys, const ui
                                              unsigned long long *d_spec, hipStream_t stream);
 // `blocks` under the entry cap of tbk_count_set_grid_caps_ (tbk_count_kernels.hip), for strided launches in other files
 unsigned tbk_count_entry_grid_(uint64_t blocks);
+
+// The directory of a sorted database (tbk_query.hip): d_dir takes 2^prefix_bits + 1 32-bit offsets, d_dir[p] the first entry whose
+// rank has the top prefix_bits bits >= p.  The query session keeps one; the het-mer call builds one per call.
+hipError_t tbk_launch_query_directory(const uint64_t *d_keys, uint64_t n, int k, int prefix_bits, uint32_t *d_dir, hipStream_t stream);
+
+// The het-mer pairs of one database (tbk_hetmer.hip, tbk_kmerdb_hetmers): the database with its directory and the candidates'
+// literal counter range; y and z as the pairs ask them - a partner that is not given has n = 0 and NULL arrays and is never
+// dereferenced.  Nothing is launched for n = 0.
+struct TbkHetmerPartner {
+    const uint64_t *keys;
+    const uint8_t *counts;
+    uint64_t n;
+    uint32_t c_min, c_max;
+};
+struct tbk_hetmer_pair;  // (include/tbk.h)
+// d_sums: 22 words - candidates, candidates with 0, 1, 2, 3 partners in range, pairs, origin[16]; d_spec: 256 * 256 words, cell
+// c_minor * 256 + c_major; both zeroed by the caller.  Strides over tiles under the entry cap of tbk_count_set_grid_caps_.
+hipError_t tbk_launch_hetmer_tally(const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, int k, const uint32_t *d_dir, int prefix_bits,
+                                   uint32_t c_min, uint32_t c_max, const TbkHetmerPartner *y, const TbkHetmerPartner *z, unsigned long long *d_sums,
+                                   unsigned long long *d_spec, hipStream_t stream);
+// flag: the lower-ranked member of every pair; scatter: one record per flagged entry, n_out in all, in the entries' order
+hipError_t tbk_launch_hetmer_flag(const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, int k, const uint32_t *d_dir, int prefix_bits,
+                                  uint32_t c_min, uint32_t c_max, uint64_t *d_flags, unsigned long long *d_tile_counts, hipStream_t stream);
+hipError_t tbk_launch_hetmer_scatter(const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, int k, const uint32_t *d_dir, int prefix_bits,
+                                     uint32_t c_min, uint32_t c_max, const TbkHetmerPartner *y, const TbkHetmerPartner *z, const uint64_t *d_flags,
+                                     const unsigned long long *d_tile_offsets, tbk_hetmer_pair *d_out, uint64_t n_out, hipStream_t stream);
 }
 
 // What a compaction over n entries holds on the device between its flag kernel and its scatter: n / 8 + n / 64 bytes.

@@ -1569,11 +1569,121 @@ extern "C" int tbk_kmerdb_select(const tbk_kmerdb *base, const tbk_select_partne
     return TBK_OK;
 }
 
+// ---- the het-mer pairs of one database (tbk_kmerdb_hetmers; kernels: tbk_hetmer.hip) ---------------------------------------------
+static int query_prefix_bits(uint64_t n, int k);  // (the query session's choice of directory, below)
+
+extern "C" void tbk_hetmer_options_init(tbk_hetmer_options *o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->size = sizeof *o;
+    o->min_count = o->y_min = o->z_min = 1;
+    o->max_count = o->y_max = o->z_max = 255;
+}
+
+extern "C" void tbk_hetmer_result_init(tbk_hetmer_result *r) {
+    if (!r) return;
+    memset(r, 0, sizeof *r);
+    r->size = sizeof *r;
+}
+
+constexpr size_t TBK_HETMER_SUMS = 6 + 16;  // candidates, by partners 0..3, pairs, origin[16] (tbk_launch_hetmer_tally)
+
+// Directory, tally and, for the pairs themselves, flag, scan and scatter at the exact size.  Beside the inputs: the directory,
+// the spectrum and the sums on the device, n / 8 + n / 64 bytes and the records when pairs are asked for; all freed before
+// the call returns.
+extern "C" int tbk_kmerdb_hetmers(const tbk_kmerdb *db, const tbk_hetmer_options *opts, tbk_hetmer_result *result, uint64_t spec[256 * 256],
+                                  tbk_hetmer_pair **out_pairs) {
+    const char *who = "tbk_kmerdb_hetmers";
+    if (out_pairs) *out_pairs = nullptr;
+    if (!db || !opts || !result || !spec) return cfail(TBK_ERR_INVALID, "%s: NULL argument", who);
+    tbk_hetmer_options o;
+    tbk_hetmer_options_init(&o);
+    if (opts->size < offsetof(tbk_hetmer_options, want_pairs) + sizeof(int) || opts->size > 4096)
+        return cfail(TBK_ERR_INVALID, "tbk_hetmer_options.size = %zu: set it with tbk_hetmer_options_init", (size_t)opts->size);
+    memcpy(&o, opts, std::min<size_t>(opts->size, sizeof o));
+    if (result->size < sizeof(tbk_hetmer_result) || result->size > 4096)
+        return cfail(TBK_ERR_INVALID, "tbk_hetmer_result.size = %zu: set it with tbk_hetmer_result_init", (size_t)result->size);
+    if (o.want_pairs && !out_pairs) return cfail(TBK_ERR_INVALID, "%s: pairs are asked for and out_pairs is NULL", who);
+    if (!(db->k & 1))
+        return cfail(TBK_ERR_INVALID, "%s: k = %d is even: the middle base must be its own mirror under reverse complement, and only an odd k has "
+                     "such a position", who, db->k);
+    if (!select_range_ok(o.min_count, o.max_count))
+        return cfail(TBK_ERR_INVALID, "%s: counter range [%u, %u]: need 1 <= min <= max <= 255", who, o.min_count, o.max_count);
+    if (!select_range_ok(o.y_min, o.y_max) || !select_range_ok(o.z_min, o.z_max))
+        return cfail(TBK_ERR_INVALID, "%s: counter ranges [%u, %u] and [%u, %u] of the partners: need 1 <= min <= max <= 255", who, o.y_min, o.y_max,
+                     o.z_min, o.z_max);
+    if (o.y && compare_check(who, db, o.y, "the first partner")) return TBK_ERR_INVALID;
+    if (o.z && compare_check(who, db, o.z, "the second partner")) return TBK_ERR_INVALID;
+    if (db->n > 0xFFFFFFFFull)
+        return cfail(TBK_ERR_INVALID, "%s: the directory holds 32-bit offsets: a database of %llu k-mers (2^32 or more) cannot be searched", who,
+                     (unsigned long long)db->n);
+    const int rc = kmerdb_device(db->device);
+    if (rc) return rc;
+    const size_t size = result->size;
+    memset(result, 0, sizeof(tbk_hetmer_result));
+    result->size = size;
+    memset(spec, 0, 256 * 256 * sizeof(uint64_t));
+    if (!db->n) return TBK_OK;
+    const TbkHetmerPartner y = {o.y ? o.y->d_keys : nullptr, o.y ? o.y->d_counts : nullptr, o.y ? o.y->n : 0, o.y_min, o.y_max};
+    const TbkHetmerPartner z = {o.z ? o.z->d_keys : nullptr, o.z ? o.z->d_counts : nullptr, o.z ? o.z->n : 0, o.z_min, o.z_max};
+    const int prefix_bits = query_prefix_bits(db->n, db->k);
+    uint32_t *d_dir = nullptr;
+    unsigned long long *d_sums = nullptr, sums[TBK_HETMER_SUMS], total = 0;  // d_sums: the sums, then the spectrum
+    tbk_hetmer_pair *d_pairs = nullptr, *home = nullptr;
+    const size_t sums_bytes = TBK_HETMER_SUMS * sizeof(unsigned long long), spec_bytes = 256 * 256 * sizeof(unsigned long long);
+    memset(sums, 0, sizeof sums);
+    Compaction sel;
+    hipError_t e = hipMalloc((void **)&d_dir, (((size_t)1 << prefix_bits) + 1) * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_sums, sums_bytes + spec_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(d_sums, 0, sums_bytes + spec_bytes, nullptr);
+    if (e == hipSuccess && o.want_pairs) e = sel.reserve(db->n, nullptr);
+    if (e == hipSuccess) e = tbk_launch_query_directory(db->d_keys, db->n, db->k, prefix_bits, d_dir, nullptr);
+    if (e == hipSuccess)
+        e = tbk_launch_hetmer_tally(db->d_keys, db->d_counts, db->n, db->k, d_dir, prefix_bits, o.min_count, o.max_count, &y, &z, d_sums,
+                                    d_sums + TBK_HETMER_SUMS, nullptr);
+    if (e == hipSuccess && o.want_pairs)
+        e = tbk_launch_hetmer_flag(db->d_keys, db->d_counts, db->n, db->k, d_dir, prefix_bits, o.min_count, o.max_count, sel.d_flags, sel.counts(), nullptr);
+    if (e == hipSuccess && o.want_pairs) e = sel.total(&total);
+    const bool sane = total <= db->n / 2;  // (nothing is allocated or written by a count that cannot be)
+    const bool some = o.want_pairs && sane && total;
+    bool host_nomem = false;
+    if (e == hipSuccess && some) e = hipMalloc((void **)&d_pairs, total * sizeof(tbk_hetmer_pair));
+    if (e == hipSuccess && some)
+        e = tbk_launch_hetmer_scatter(db->d_keys, db->d_counts, db->n, db->k, d_dir, prefix_bits, o.min_count, o.max_count, &y, &z, sel.d_flags,
+                                      sel.offsets(), d_pairs, total, nullptr);
+    if (e == hipSuccess && some) {
+        home = (tbk_hetmer_pair *)tbk_host_alloc(total * sizeof(tbk_hetmer_pair));
+        host_nomem = !home;
+    }
+    if (e == hipSuccess && some && home) e = hipMemcpy(home, d_pairs, total * sizeof(tbk_hetmer_pair), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(sums, d_sums, sums_bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(spec, d_sums + TBK_HETMER_SUMS, spec_bytes, hipMemcpyDeviceToHost);
+    sel.release();
+    for (void *p : {(void *)d_dir, (void *)d_sums, (void *)d_pairs})
+        if (p) (void)hipFree(p);
+    const bool agree = e != hipSuccess || !sane || host_nomem || !o.want_pairs || total == sums[5];
+    if (e != hipSuccess || !sane || host_nomem || !agree) {
+        tbk_host_free(home);
+        (void)hipGetLastError();
+        memset(spec, 0, 256 * 256 * sizeof(uint64_t));
+        if (host_nomem) return TBK_ERR_NOMEM;  // (tbk_host_alloc has left the reason)
+        if (e != hipSuccess)
+            return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "%s (%llu k-mers): %s", who, (unsigned long long)db->n, hipGetErrorString(e));
+        return cfail(TBK_ERR_HIP, "%s: %llu pairs flagged among %llu k-mers, %llu tallied", who, total, (unsigned long long)db->n, sane ? sums[5] : 0ull);
+    }
+    result->candidates = sums[0];
+    for (int j = 0; j < 4; j++) result->partners[j] = sums[1 + j];
+    result->pairs = sums[5];
+    for (int j = 0; j < 16; j++) result->origin[j] = sums[6 + j];
+    if (out_pairs) *out_pairs = home;
+    return TBK_OK;
+}
+
 // =====================================================================================================================
 // Database query (tbk_kmerdb_query; kernels: tbk_query.hip): the counter the database holds for every window of a
 // batch of sequences - per-sequence totals, a histogram, the entries seen, their copies.  include/tbk.h has the rules.
 // =====================================================================================================================
-extern "C" hipError_t tbk_launch_query_directory(const uint64_t *, uint64_t, int, int, uint32_t *, hipStream_t);
+// (tbk_launch_query_directory: tbk_compact_host.h, shared with the het-mer call)
 extern "C" hipError_t tbk_launch_query_lookup(const uint8_t *, uint64_t, uint64_t, int, const uint64_t *, const uint8_t *, const uint32_t *, uint64_t, int,
                                               uint32_t, uint32_t *, uint32_t *, uint8_t *, unsigned long long *, uint32_t *, uint32_t *, uint64_t,
                                               hipStream_t);

@@ -8,6 +8,7 @@
 
 #include "../../include/tbk.h"
 #include "tbk_common.h"
+#include "tbk_compact_host.h"  // (the one declaration of tbk_launch_query_directory)
 #include "tbk_device.h"
 
 // What the lookup reads of a session: the database's ranks and counters (borrowed) and the directory over the top

@@ -1060,6 +1060,11 @@ def load_solid_database(path: str, device: Optional[int] = None) -> "KmerDatabas
         db.close()
 
 
+# tbk_hetmer_pair (include/tbk.h): 24 bytes
+HETMER_PAIR_DTYPE = np.dtype([("minor", "<u8"), ("major", "<u8"), ("c_minor", "u1"), ("c_major", "u1"), ("cls_minor", "u1"), ("cls_major", "u1"),
+                              ("reserved", "u1", (4,))])
+
+
 class KmerDatabase:
     """What a ``KmerCounter`` leaves behind, kept: the k-mers seen at least twice as ascending lexicographic ranks
     with their counters (2..255) in HBM, and the counter's whole histogram - the ``haplotypeA.*`` database `kmc`
@@ -1233,6 +1238,41 @@ class KmerDatabase:
         h = C.c_void_p()
         check(lib.tbk_kmerdb_select(self._h, partners, len(asked), C.byref(o), C.byref(h)))
         return KmerDatabase(h)
+
+    def hetmers(self, min_count: int, max_count: int, y: Optional["KmerDatabase"] = None, z: Optional["KmerDatabase"] = None,
+                y_range: Tuple[int, int] = (1, 255), z_range: Tuple[int, int] = (1, 255), pairs: bool = False) -> dict:
+        """The het-mer pairs inside this database (``tbk_kmerdb_hetmers``; include/tbk.h has the definitions): among the entries
+        with a counter in [min_count, max_count] - the candidates - those that differ from exactly one other candidate in the
+        middle base alone, which is what the two alleles of a heterozygous SNP leave.  k must be odd.  Returns a dict:
+        ``candidates`` and ``pairs`` (int); ``partners``, shape (4,): candidates by number of middle partners among the
+        candidates; ``spec``, shape (256, 256): pairs by the counter of the minor (row) and the major member (column);
+        ``origin``, shape (4, 4): pairs by the class of the minor (row) and the major member, bit 0 of a class set when ``y``
+        holds that k-mer with a counter in ``y_range``, bit 1 the same for ``z`` (a partner left out contributes 0).  All uint64.
+        With ``pairs=True`` also ``records``: a structured array (``HETMER_PAIR_DTYPE``: minor, major as ranks, c_minor, c_major,
+        cls_minor, cls_major), ascending by the rank of each pair's lower-ranked member.  ``ValueError`` for an even k, a range
+        outside 1 <= min <= max <= 255, or partners of another k, device or space."""
+        bounds = [int(v) for v in (min_count, max_count, *y_range, *z_range)]
+        if any(not 0 <= v <= 0xFFFFFFFF for v in bounds):
+            raise ValueError("counter ranges {}: need 1 <= min <= max <= 255".format(list(zip(bounds[::2], bounds[1::2]))))
+        o, res = _lib.HetmerOptions(), _lib.HetmerResult()
+        lib.tbk_hetmer_options_init(C.byref(o))
+        lib.tbk_hetmer_result_init(C.byref(res))
+        o.min_count, o.max_count, o.y_min, o.y_max, o.z_min, o.z_max = bounds
+        o.y = None if y is None else y._h.value
+        o.z = None if z is None else z._h.value
+        o.want_pairs = int(bool(pairs))
+        spec = np.zeros((256, 256), dtype=np.uint64)
+        ptr = C.c_void_p()
+        check(lib.tbk_kmerdb_hetmers(self._h, C.byref(o), C.byref(res), spec.ctypes.data, C.byref(ptr)))
+        out = {"candidates": int(res.candidates), "pairs": int(res.pairs), "partners": np.array(list(res.partners), dtype=np.uint64),
+               "spec": spec, "origin": np.array(list(res.origin), dtype=np.uint64).reshape(4, 4)}
+        if pairs:
+            records = np.zeros(int(res.pairs), dtype=HETMER_PAIR_DTYPE)
+            if ptr.value:
+                C.memmove(records.ctypes.data, ptr.value, records.nbytes)
+            out["records"] = records
+        lib.tbk_host_free(ptr)
+        return out
 
     def query(self, copies: bool = False) -> "DatabaseQuery":
         """A session that scores sequences against this database (``DatabaseQuery``); ``copies`` keeps a 32-bit counter
