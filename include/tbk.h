@@ -368,7 +368,8 @@ typedef struct tbk_run_stats {
     int32_t gzip_encoder, reserved_;              /* who coded the bins' gzip members: 0 nobody (plain bins), 1 the host, 2 the device */
 } tbk_run_stats;
 /* gzip_output = 2: BAM bins ("BAM output" below) - the input must be BAM (TBK_ERR_INVALID otherwise), out_a/out_b/out_u name BAM
- * files, and tbk_run_stats.gzip_encoder says who coded their bgzf blocks, as for gzip. */
+ * files, and tbk_run_stats.gzip_encoder says who coded their bgzf blocks, as for gzip.
+ * gzip_output = 3: haplotag output ("Haplotag output" below) - BAM input again, out_a names the one BAM file, out_b / out_u are ignored. */
 int tbk_classify_file(tbk_pipeline *p, const char *reads_path, uint64_t num_kmers_a, uint64_t num_kmers_b, const char *out_a,
                       const char *out_b, const char *out_u, int gzip_output, int gzip_level, int tsv_fd, uint64_t batch_bases,
                       uint64_t batch_reads, tbk_run_stats *stats);
@@ -599,6 +600,64 @@ int tbk_bin_writer_open_bam(const char *path_a, const char *path_b, const char *
 int tbk_bin_writer_encoder(const tbk_bin_writer *w);
 int tbk_bin_writer_write(tbk_bin_writer *w, const tbk_fastx_batch *b, const char *bins);
 int tbk_bin_writer_close(tbk_bin_writer *w);
+/* ---- Haplotag output: one BAM file in input order, every read tagged with its haplotype and counts ----------------------------------
+ * With BAM input, ONE BAM file instead of the three bins (the reference has no such mode: an extension, opt-in), in which every read
+ * carries its bin as the HP tag and its two k-mer counts as ka / kb.  The rule is normative.
+ *
+ * Inputs: a record R as the reader keeps it (block_size and the bytes that follow), the bin of its read ('A', 'B' or 'U'; any other
+ * byte counts as 'U') and its counts (a, b).  Offsets count from the block_size field.
+ *   aux area  begins at 36 + l_read_name + 4 * n_cigar_op + (l_seq + 1) / 2 + l_seq and ends at 4 + block_size.
+ *   walk      field by field, tag[2] type[1] value.  The value's size by type: A c C 1 byte; s S 2; i I f 4; Z H up to and including the
+ *             first NUL; B subtype[1] count[int32] count x size, with size 1 for c C, 2 for s S, 4 for i I f.
+ *   output    1. block_size' (int32);  2. every byte of R from +4 up to the aux area, verbatim;  3. every field not named HP, ka or kb,
+ *             verbatim and in order - a field with one of those three names is dropped, whatever its type;  4. HP C 0x01 for bin A,
+ *             HP C 0x02 for bin B, nothing for U;  5. ka I a (uint32);  6. kb I b (uint32).
+ * block_size' = block_size - dropped + added: a record grows by at most 18 bytes.  Flag, seq and qual are untouched; a reverse-strand
+ * record is not complemented, as in the BAM bins.  All integers are little-endian.
+ *
+ * Refused with TBK_ERR_FORMAT, tbk_last_error() naming the first offending record in order (the transcoder's atomic-min rule on the
+ * device) and the reason.  A record is walked front to back and refused at its first offence; of one field these are looked for in
+ * this order:
+ *     fewer than 3 bytes left for a field;  unknown type;  for B: fewer than 5 bytes left for subtype and count (a value that runs past
+ *     the record's end), unknown subtype, negative count;  Z / H without a NUL before the end;  a value that runs past the record's end;
+ *     then, the field being whole: a second field named HP, a second ka, a second kb;
+ * and behind the last field block_size' > TBK_BAM_MAX_RECORD.  An aux area that begins past the record's end, and a block_size above
+ * TBK_BAM_MAX_RECORD, are refused in the words of "BAM input".  A count below 0 is TBK_ERR_INVALID.
+ *
+ * The file: the input's header bytes verbatim (no @PG line is added), the tagged record of every read of the TSV in input order -
+ * records the reader skips (flag & 0x900, l_seq == 0) are absent, as from the bins - and the 28-byte bgzf end-of-file marker; a run
+ * with no reads writes header plus marker.  The container is bgzf as for the BAM bins: the decompressed bytes are specified, the
+ * container bytes are not.
+ *
+ * Rewriter.  tbk_bam_haplotag_device: records / size = a run of whole records in host memory, offsets[n] = where each begins (each
+ * must lie wholly within size: TBK_ERR_INVALID otherwise), bins[n], counts[n][2]; the tagged records are written back to back into
+ * dst (host memory; size + 18 n bytes always suffice), out_off (n + 1 entries, may be NULL) gets where each begins and the total,
+ * *out_len the total - also with TBK_ERR_NOMEM, when cap is too small and nothing is written.  n = 0 is valid and writes nothing.
+ * On `device` (csrc/tbk_bam_tag.hip): a measure kernel that walks the fields of a record per thread, the exclusive scan, a write
+ * kernel tiled by output bytes.  tbk_bam_haplotag: the same by the plain C++ of csrc/tbk_bam_tag.h on the host's threads.
+ * tbk_bam_haplotag_bench_device (tools/measure_haplotag.py): the run resident on the device, one warm-up, then `reps` times
+ * whole_s[i] = measure, scan, the size home and the write kernel (wall clock, the stream idle either side), write_s[i] = the write
+ * kernel alone between HIP events, call_s[i] (may be NULL) = copy in, kernels and the records home with warm buffers.
+ *
+ * Writer.  tbk_bin_writer_open_haplotag opens one file and codes the header into it at once, on the host.
+ * tbk_bin_writer_write_counts appends a batch: its records (TBK_ERR_STATE for a batch that carries none) are rewritten in one call,
+ * and the coder's hints are taken from the tagged records, four per record as for the BAM bins.  Plain tbk_bin_writer_write on such
+ * a writer is TBK_ERR_STATE, as tbk_bin_writer_write_counts is on any other.  Pieces are 65280 bytes; tbk_bin_writer_close codes
+ * the rest and writes the marker.  tbk_bin_writer_use_device switches the coder to the device, and the rewrite as well when
+ * TBK_HAPLOTAG_REWRITE=gpu is set (the default is the host's threads: DESIGN.md section 9 has the measurement); the host functions
+ * stay in place when the device cannot be set up.  tbk_bin_writer_rewriter: 1 when the device rewrites.
+ *
+ * Loop.  tbk_classify_file with gzip_output = 3: out_a names the file, out_b and out_u are ignored (may be NULL); the input must be
+ * BAM (TBK_ERR_INVALID otherwise); the reader keeps records as for mode 2. */
+int tbk_bam_haplotag_device(int device, const uint8_t *records, uint64_t size, const uint64_t *offsets, uint64_t n, const char *bins, const int32_t *counts,
+                            uint8_t *dst, uint64_t cap, uint64_t *out_off, uint64_t *out_len);
+int tbk_bam_haplotag(const uint8_t *records, uint64_t size, const uint64_t *offsets, uint64_t n, const char *bins, const int32_t *counts, uint8_t *dst, uint64_t cap,
+                     uint64_t *out_off, uint64_t *out_len);
+int tbk_bam_haplotag_bench_device(int device, const uint8_t *records, uint64_t size, const uint64_t *offsets, uint64_t n, const char *bins, const int32_t *counts,
+                                  int reps, double *whole_s, double *write_s, double *call_s, uint64_t *out_len);
+int tbk_bin_writer_open_haplotag(const char *path, const uint8_t *header, uint64_t header_len, int level, int threads, tbk_bin_writer **out);
+int tbk_bin_writer_write_counts(tbk_bin_writer *w, const tbk_fastx_batch *b, const char *bins, const int32_t *counts);
+int tbk_bin_writer_rewriter(const tbk_bin_writer *w);
 /* The writer's own encoder for gzip members whose bytes do not come in runs (FASTQ of long reads:
  * nothing for LZ77 to match, so entropy coding only - dynamic-Huffman DEFLATE blocks cut at line ends,
  * so that bases and qualities get codes of their own).  One complete gzip member for src[0..n);

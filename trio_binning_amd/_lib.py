@@ -360,6 +360,13 @@ if hasattr(lib, "tbk_gzip_members_device"):
         _sig("tbk_bgzf_members_threads_", C.c_int, C.c_char_p, _u64, _u64p, _u64, C.c_char_p, _u64, _u64p, _u64p, C.c_int)
         _sig("tbk_bgzf_members_bench_device", C.c_int, C.c_int, _vp, _u64, _u64p, _u64, C.c_int, _dp, _dp, _u64p)
         _sig("tbk_bin_writer_open_bam", C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _u64, C.c_int, C.c_int, C.POINTER(_vp))
+    if hasattr(lib, "tbk_bam_haplotag_device"):  # haplotag output (include/tbk.h "Haplotag output")
+        _sig("tbk_bam_haplotag_device", C.c_int, C.c_int, C.c_char_p, _u64, _u64p, _u64, C.c_char_p, _i32p, C.c_char_p, _u64, _u64p, _u64p)
+        _sig("tbk_bam_haplotag", C.c_int, C.c_char_p, _u64, _u64p, _u64, C.c_char_p, _i32p, C.c_char_p, _u64, _u64p, _u64p)
+        _sig("tbk_bam_haplotag_bench_device", C.c_int, C.c_int, C.c_char_p, _u64, _u64p, _u64, C.c_char_p, _i32p, C.c_int, _dp, _dp, _dp, _u64p)
+        _sig("tbk_bin_writer_open_haplotag", C.c_int, C.c_char_p, C.c_char_p, _u64, C.c_int, C.c_int, C.POINTER(_vp))
+        _sig("tbk_bin_writer_write_counts", C.c_int, _vp, _vp, C.c_char_p, _vp)
+        _sig("tbk_bin_writer_rewriter", C.c_int, _vp)
     if hasattr(lib, "tbk_bgzf_bench_device"):
         _sig("tbk_bgzf_bench_device", C.c_int, C.c_int, C.c_char_p, _u64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _u64p)
     if hasattr(lib, "tbk_gzip_inflate_device"):

@@ -115,6 +115,12 @@ def _parser(kmer_list_type) -> argparse.ArgumentParser:
              "and the header as they came - instead of FASTQ text",
     )
     parser.add_argument(
+        "--haplotag-output", default=None, metavar="PATH",
+        help="BAM input only: instead of the three bins write ONE BAM file, PATH, in input order, in which every read carries its bin "
+             "as the tag HP (1: haplotype A, 2: haplotype B, none: unclassified) and its two k-mer counts as the tags ka and kb; the "
+             "records are otherwise as they came",
+    )
+    parser.add_argument(
         "--compress", action="store_true", default=False,
         help="k-mer lists made by find-unique-kmers --compress: every run of equal bases of a read is written once before it is "
              "probed (the bins still hold the reads as they came). Count databases say by themselves which space they are in",
@@ -251,6 +257,13 @@ def _check_kmer_arguments(parser, args, prog: str = "classify-by-kmers") -> bool
             parser.error("--bam-output keeps BAM records whole: the reads must be a .bam file, not {}".format(args.reads))
         if args.no_gzip_output:
             parser.error("--bam-output and --no-gzip-output exclude each other: BAM bins are bgzf-compressed")
+    if getattr(args, "haplotag_output", None) is not None:
+        if not args.reads.endswith(".bam"):
+            parser.error("--haplotag-output tags BAM records: the reads must be a .bam file, not {}".format(args.reads))
+        if args.bam_output:
+            parser.error("--haplotag-output and --bam-output exclude each other: one tagged BAM file, or three BAM bins")
+        if args.no_gzip_output:
+            parser.error("--haplotag-output and --no-gzip-output exclude each other: a BAM file is bgzf-compressed")
     is_db = [fu.is_database_path(args.haplotype_a_kmers), fu.is_database_path(args.haplotype_b_kmers)]
     if is_db[0] != is_db[1]:
         sys.exit(prog + ": {} is a {} and {} is a {}: give two k-mer lists or two count databases (*{})".format(
@@ -331,11 +344,12 @@ def classify_compressed(args, num_a: int, num_b: int) -> dict:
     print("Classifying in homopolymer-compressed space: the reads are compressed on device {} before they are probed.".format(device), file=sys.stderr)
     gzip_output = not args.no_gzip_output
     reader = None
-    if args.bam_output:  # (BAM bins begin with the input's header: the reader comes first)
+    if args.bam_output or args.haplotag_output is not None:  # (BAM output begins with the input's header: the reader comes first)
         reader = seq.BatchReader(args.reads, keep_records=True)
         try:
             writer = seq.BinWriter(args.haplotype_a_out_prefix, args.haplotype_b_out_prefix, args.unclassified_out_prefix, ".bam", True,
-                                   int(os.environ.get("TBK_GZIP_LEVEL", "-1")), device=device, bam_header=reader.bam_header())
+                                   int(os.environ.get("TBK_GZIP_LEVEL", "-1")), device=device, bam_header=reader.bam_header(),
+                                   haplotag_path=args.haplotag_output)
         except BaseException:
             reader.close()
             classifier.close()
@@ -353,7 +367,10 @@ def classify_compressed(args, num_a: int, num_b: int) -> dict:
         t1 = time.perf_counter()
         score_a, score_b, bins = kmers.score_and_bin(counts, num_a, num_b)
         out.write(seq.format_tsv(batch, bins, score_a, score_b))
-        writer.write(batch, bins)
+        if args.haplotag_output is not None:
+            writer.write_counts(batch, bins, counts)  # (the counts of compressed space, as the TSV's scores are)
+        else:
+            writer.write(batch, bins)
         spent["probe_wait_s"] += t1 - t0
         spent["write_s"] += time.perf_counter() - t1
 
@@ -421,7 +438,10 @@ def main():
     # packed for the link on the way), this thread feeding the device(s) and taking the batches back in
     # input order, a writer scoring, binning, writing the three bins and the TSV.  Python only names the
     # files; the TSV goes to the process's stdout descriptor.
-    if args.bam_output:
+    mode = 2 if args.bam_output else not args.no_gzip_output
+    if args.haplotag_output is not None:
+        names, mode = (args.haplotag_output, "", ""), 3  # one tagged BAM file; the three bins are not written
+    elif args.bam_output:
         names = seq.output_names(args.haplotype_a_out_prefix, args.haplotype_b_out_prefix, args.unclassified_out_prefix, ".bam", False)
     else:
         names = seq.output_names(args.haplotype_a_out_prefix, args.haplotype_b_out_prefix, args.unclassified_out_prefix,
@@ -439,7 +459,7 @@ def main():
         spool = tempfile.TemporaryFile()
         tsv_fd = spool.fileno()
     try:
-        stats = classifier.classify_file(args.reads, num_a, num_b, names, 2 if args.bam_output else not args.no_gzip_output, level, tsv_fd, _BATCH_BASES, _BATCH_READS)
+        stats = classifier.classify_file(args.reads, num_a, num_b, names, mode, level, tsv_fd, _BATCH_BASES, _BATCH_READS)
     finally:
         if spool is not None:
             spool.seek(0)

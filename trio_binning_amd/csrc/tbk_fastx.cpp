@@ -48,6 +48,7 @@
 #include "tbk_gdeflate.h"
 #include "tbk_gzplan.h"
 #include "tbk_bam.h"
+#include "tbk_bam_tag.h"
 
 uint32_t tbk_crc32(uint32_t crc, const uint8_t *p, size_t n);  // tbk_crc.cpp: zlib's crc32() by carry-less multiplication
 
@@ -2271,6 +2272,8 @@ struct IoLane {
     void end() { { std::lock_guard<std::mutex> lk(mu); stop = true; } cv.notify_all(); if (th.joinable()) th.join(); }
 };
 
+#define TBK_HAPLOTAG_REWRITE_ON_DEVICE 0   /* the haplotag rewrite's default place: 1 the device, 0 the host's threads */
+
 struct tbk_bin_writer {
     BinFile bin[3];  // A, B, U
     bool gz = false;
@@ -2287,6 +2290,12 @@ struct tbk_bin_writer {
     // blocks of 65280 bytes; hints[b]: the cut hints of bin b's pending bytes (four per record, offsets into bin[b].text)
     bool bam = false, bam_zlib = false;
     std::vector<uint64_t> hints[3];
+    // haplotag output (tbk_bin_writer_open_haplotag; include/tbk.h "Haplotag output"): one BAM file, bin[0], of every read's record
+    // with its tags rewritten - by the host's threads (tbk_bam_tag.h), or by `tagger` on the device once tbk_bin_writer_use_device set it up
+    bool tag = false;
+    tbk_bamtag *tagger = nullptr;
+    uint64_t tag_records = 0;   // records written so far: a refused record is named by its number in the output
+    std::vector<uint64_t> tag_off;
 };
 
 static bool write_all(int fd, const char *p, size_t n, std::string &err) {
@@ -2617,6 +2626,75 @@ extern "C" int tbk_bin_writer_open_bam(const char *path_a, const char *path_b, c
     return rc;
 }
 
+// Haplotag output (include/tbk.h "Haplotag output"): ONE BAM file that gets the input's header at once, coded here on the host;
+// the tagged records follow with tbk_bin_writer_write_counts, the end-of-file marker with tbk_bin_writer_close.  The file is the
+// writer's bin 0; its other two bins have no file and stay empty.
+extern "C" int tbk_bin_writer_open_haplotag(const char *path, const uint8_t *header, uint64_t header_len, int level, int threads, tbk_bin_writer **out) {
+    if (!out || !path || !header || header_len < 12 || memcmp(header, "BAM\1", 4) != 0) return ffail(TBK_ERR_INVALID, "tbk_bin_writer_open_haplotag: no path or no BAM header");
+    *out = nullptr;
+    const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) return ffail(TBK_ERR_IO, "cannot create %s: %s", path, strerror(errno));
+    tbk_bin_writer *w = new tbk_bin_writer();
+    w->gz = w->bam = w->tag = true;
+    w->bam_zlib = getenv("TBK_GZIP_ENCODER") && strcmp(getenv("TBK_GZIP_ENCODER"), "zlib") == 0;
+    w->level = level < 0 ? 6 : std::min(level, 9);
+    w->threads = std::min(threads <= 0 ? tbk_host_threads() : threads, 512);
+    w->chunk = 65280;
+    w->bin[0].fd = fd;
+    struct stat st;
+    w->bin[0].positional = ::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && ::lseek(fd, 0, SEEK_CUR) >= 0;
+    int rc = TBK_OK;
+    std::vector<char> coded;
+    for (uint64_t at = 0; at < header_len; at += 65280)
+        if (!tbk_bgzf_member_(header, at, (size_t)std::min<uint64_t>(65280, header_len - at), nullptr, 0, w->level, w->bam_zlib, coded)) rc = ffail(TBK_ERR_IO, "deflate failed");
+    if (!rc && !write_all(fd, coded.data(), coded.size(), w->err)) rc = ffail(TBK_ERR_IO, "%s", w->err.c_str());
+    w->bin[0].file_off += coded.size();
+    if (rc) { (void)tbk_bin_writer_close(w); return rc; }
+    *out = w;
+    return TBK_OK;
+}
+
+// append the batch's records, each rewritten with its bin and counts as tags, in input order: one call rewrites the whole batch
+// into the pending bytes of bin 0, the coder's hints are taken from the tagged records (four per record, as for the BAM bins)
+extern "C" int tbk_bin_writer_write_counts(tbk_bin_writer *w, const tbk_fastx_batch *b, const char *bins, const int32_t *counts) {
+    if (!w || !b || (b->n_reads() && (!bins || !counts))) return ffail(TBK_ERR_INVALID, "NULL argument");
+    if (!w->tag) return ffail(TBK_ERR_STATE, "tbk_bin_writer_write_counts: not a haplotag writer (tbk_bin_writer_open_haplotag)");
+    if (!b->has_records) return ffail(TBK_ERR_STATE, "tbk_bin_writer_write_counts: the batch carries no records (tbk_fastx_set_keep_records)");
+    const uint64_t n = b->n_reads();
+    if (!n) return TBK_OK;
+    for (uint64_t i = 0; i < 2 * n; i++)
+        if (counts[i] < 0) return ffail(TBK_ERR_INVALID, "tbk_bin_writer_write_counts: read %llu of the batch has a count below 0", (unsigned long long)(i / 2));
+    BinFile &f = w->bin[0];
+    const size_t at0 = f.text.size();
+    const uint64_t size = b->rec_off[(size_t)n], room = size + (uint64_t)TBK_TAG_GROWTH * n;
+    if (!f.text.grow_to(at0 + (size_t)room)) return ffail(TBK_ERR_NOMEM, "out of memory buffering the tagged records");
+    w->tag_off.resize((size_t)n + 1);
+    uint8_t *dst = (uint8_t *)f.text.data() + at0;
+    uint64_t len = 0, bad = TBK_BAM_NO_BAD;
+    const double t0 = wall_now();
+    if (w->tagger) {
+        const int rc = tbk_bamtag_run(w->tagger, b->records.data(), size, b->rec_off.data(), n, bins, counts, dst, room, w->tag_off.data(), &len, &bad);
+        if (rc) return rc;
+    } else {
+        bool fits = true;
+        bad = tbk_bam_haplotag_host(b->records.data(), b->rec_off.data(), n, bins, counts, dst, room, w->tag_off.data(), &len, &fits, w->threads);
+        if (bad == TBK_BAM_NO_BAD && !fits) return ffail(TBK_ERR_INTERNAL, "tbk_bin_writer_write_counts: the tagged records outgrew their bound");
+    }
+    if (bad != TBK_BAM_NO_BAD)
+        return ffail(TBK_ERR_FORMAT, "haplotag output: BAM record %llu: %s", (unsigned long long)(w->tag_records + (bad >> 8)), tbk_tag_reason((uint32_t)(bad & 0xFFu)));
+    w->fill_s += wall_now() - t0;
+    w->tag_records += n;
+    f.text.n = at0 + (size_t)len;
+    std::vector<uint64_t> &hints = w->hints[0];
+    hints.reserve(hints.size() + 4 * (size_t)n);
+    for (uint64_t i = 0; i < n; i++) {
+        uint64_t h[4];
+        tbk_bam_hints(dst + w->tag_off[(size_t)i], (uint32_t)(w->tag_off[(size_t)i + 1] - w->tag_off[(size_t)i]), at0 + w->tag_off[(size_t)i], h);
+        hints.insert(hints.end(), h, h + 4);
+    }
+    return flush_bins(w, false);
+}
+
 // The bytes Read.print writes for record i (seq.py:27-31: FASTQ when the record has a non-empty quality string, else
 // FASTA; name = header up to the first space, bare '+' line), as up to 7 pieces of memory.  A record copied into the
 // batch's arrays is gathered from them and from constants.  A borrowed record lies in the mapped input as
@@ -2662,6 +2740,7 @@ static inline int record_pieces(const tbk_fastx_batch *b, size_t i, struct iovec
 extern "C" int tbk_bin_writer_write(tbk_bin_writer *w, const tbk_fastx_batch *b, const char *bins) {
     if (!w || !b || (b->n_reads() && !bins)) return ffail(TBK_ERR_INVALID, "NULL argument");
     const uint64_t n = b->n_reads();
+    if (w->tag) return ffail(TBK_ERR_STATE, "tbk_bin_writer_write: a haplotag writer takes its batches with their counts (tbk_bin_writer_write_counts)");
     if (w->bam && !b->has_records) return ffail(TBK_ERR_STATE, "tbk_bin_writer_write: BAM bins, and the batch carries no records (tbk_fastx_set_keep_records)");
     // where every record goes: its bin and its offset in that bin's pending text (one serial pass
     // over the records' lengths), then the bytes are put there by several threads
@@ -2777,11 +2856,25 @@ extern "C" int tbk_bin_writer_write(tbk_bin_writer *w, const tbk_fastx_batch *b,
     return flush_bins(w, false);
 }
 
+// Who rewrites a haplotag writer's records once a device is there: TBK_HAPLOTAG_REWRITE=gpu / cpu, else the default the
+// measurement set.
+static bool tag_rewrites_on_device() {
+    const char *e = getenv("TBK_HAPLOTAG_REWRITE");
+    if (e && strcmp(e, "gpu") == 0) return true;
+    if (e && strcmp(e, "cpu") == 0) return false;
+    return TBK_HAPLOTAG_REWRITE_ON_DEVICE != 0;
+}
+
 // The gzip members from here on are coded on `device` (tbk_gdeflate.hip) instead of on the host's threads: call it right after
 // tbk_bin_writer_open (gzip output; before the first write).  TBK_GZIP_ENCODER=cpu / zlib keeps the host encoders.
 extern "C" int tbk_bin_writer_use_device(tbk_bin_writer *w, int device) {
     if (!w) return ffail(TBK_ERR_INVALID, "NULL argument");
     if (!w->gz || w->gpu) return TBK_OK;
+    if (w->tag && w->bin[0].text.size()) return ffail(TBK_ERR_STATE, "tbk_bin_writer_use_device after the first write");
+    if (w->tag && !w->tagger && tag_rewrites_on_device()) {
+        // (the host's rewriter stays when the device's cannot be set up, as its coder does)
+        if (tbk_bamtag_create(device, &w->tagger)) w->tagger = nullptr;
+    }
     const char *enc = getenv("TBK_GZIP_ENCODER");
     if ((enc && (strcmp(enc, "cpu") == 0 || strcmp(enc, "zlib") == 0)) || getenv("TBK_GZIP_STRATEGY") || w->level == 0) return TBK_OK;
     for (int b = 0; b < 3; b++) if (w->bin[b].text.size()) return ffail(TBK_ERR_STATE, "tbk_bin_writer_use_device after the first write");
@@ -2797,6 +2890,7 @@ extern "C" int tbk_bin_writer_use_device(tbk_bin_writer *w, int device) {
 }
 
 extern "C" int tbk_bin_writer_encoder(const tbk_bin_writer *w) { return w && w->gpu ? 1 : 0; }
+extern "C" int tbk_bin_writer_rewriter(const tbk_bin_writer *w) { return w && w->tagger ? 1 : 0; }
 
 extern "C" int tbk_bin_writer_close(tbk_bin_writer *w) {
     if (!w) return TBK_OK;
@@ -2816,9 +2910,10 @@ extern "C" int tbk_bin_writer_close(tbk_bin_writer *w) {
         tbk_gdeflate_destroy(w->gpu);
         w->gpu = nullptr;
     }
+    if (w->tagger) { tbk_bamtag_destroy(w->tagger); w->tagger = nullptr; }
     if (w->bam) {
         for (int b = 0; b < 3; b++)
-            if (!write_all(w->bin[b].fd, (const char *)BGZF_EOF_MARKER, sizeof BGZF_EOF_MARKER, w->err) && !rc) rc = ffail(TBK_ERR_IO, "%s", w->err.c_str());
+            if (w->bin[b].fd >= 0 && !write_all(w->bin[b].fd, (const char *)BGZF_EOF_MARKER, sizeof BGZF_EOF_MARKER, w->err) && !rc) rc = ffail(TBK_ERR_IO, "%s", w->err.c_str());
     } else if (w->gz) {
         // an empty bin is still a valid (empty) gzip file, as gzip.open(...).close() leaves it
         for (int b = 0; b < 3; b++) {

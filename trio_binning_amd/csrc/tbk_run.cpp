@@ -83,7 +83,8 @@ bool write_fd(int fd, const char *p, size_t n) {
 extern "C" int tbk_classify_file(tbk_pipeline *p, const char *reads_path, uint64_t num_kmers_a, uint64_t num_kmers_b, const char *out_a,
                                  const char *out_b, const char *out_u, int gzip_output, int gzip_level, int tsv_fd, uint64_t batch_bases,
                                  uint64_t batch_reads, tbk_run_stats *stats) {
-    if (!p || !reads_path || !out_a || !out_b || !out_u) { tbk_set_error_(TBK_ERR_INVALID, "NULL argument"); return TBK_ERR_INVALID; }
+    const bool haplotag = gzip_output == 3;   // one BAM file, out_a, of every read's record with its bin and counts as tags
+    if (!p || !reads_path || !out_a || (!haplotag && (!out_b || !out_u))) { tbk_set_error_(TBK_ERR_INVALID, "NULL argument"); return TBK_ERR_INVALID; }
     const auto t_start = Clock::now();
     tbk_run_stats st;
     memset(&st, 0, sizeof st);
@@ -110,6 +111,14 @@ extern "C" int tbk_classify_file(tbk_pipeline *p, const char *reads_path, uint64
         if (!rc) rc = tbk_fastx_set_keep_records(reader, 1);
         if (!rc) rc = tbk_fastx_bam_header(reader, &header, &header_len);
         if (!rc) rc = tbk_bin_writer_open_bam(out_a, out_b, out_u, header, header_len, gzip_level, 0, &writer);
+    } else if (haplotag) {
+        // haplotag output (include/tbk.h "Haplotag output"): the batches carry their records, the file begins with the input's header
+        const uint8_t *header = nullptr;
+        uint64_t header_len = 0;
+        if (!tbk_fastx_bam_counts(reader, nullptr)) { tbk_set_error_(TBK_ERR_INVALID, "haplotag output needs BAM input"); rc = TBK_ERR_INVALID; }
+        if (!rc) rc = tbk_fastx_set_keep_records(reader, 1);
+        if (!rc) rc = tbk_fastx_bam_header(reader, &header, &header_len);
+        if (!rc) rc = tbk_bin_writer_open_haplotag(out_a, header, header_len, gzip_level, 0, &writer);
     } else {
         rc = tbk_bin_writer_open(out_a, out_b, out_u, gzip_output, gzip_level, 0, &writer);
     }
@@ -188,7 +197,7 @@ extern "C" int tbk_classify_file(tbk_pipeline *p, const char *reads_path, uint64
                     const uint64_t n = it->n_reads;
                     sa.resize(n); sb.resize(n); bins.resize(n);
                     int r = tbk_score_and_bin(it->counts, n, num_kmers_a, num_kmers_b, sa.data(), sb.data(), bins.data());
-                    if (!r) r = tbk_bin_writer_write(writer, it->batch, bins.data());
+                    if (!r) r = haplotag ? tbk_bin_writer_write_counts(writer, it->batch, bins.data(), it->counts) : tbk_bin_writer_write(writer, it->batch, bins.data());
                     size_t len = 0;
                     if (!r && tsv_fd >= 0) {
                         r = tbk_format_tsv(it->batch, bins.data(), sa.data(), sb.data(), nullptr, 0, &len);

@@ -837,7 +837,8 @@ class MultiClassifier:
     def classify_file(self, reads_path: str, num_kmers_a: int, num_kmers_b: int, out_names: Sequence[str], gzip_output: bool,
                       gzip_level: int = -1, tsv_fd: int = 1, batch_bases: int = 0, batch_reads: int = 0) -> dict:
         """The whole read / classify / write loop of classify-by-kmers on native threads (``tbk_classify_file``);
-        the TSV goes to ``tsv_fd``.  ``gzip_output`` 2: BAM bins from BAM input (``classify-by-kmers --bam-output``).  Returns the run's statistics."""
+        the TSV goes to ``tsv_fd``.  ``gzip_output`` 2: BAM bins from BAM input (``classify-by-kmers --bam-output``); 3: one BAM file,
+        ``out_names[0]``, of every read's record tagged with its bin and counts (``--haplotag-output``).  Returns the run's statistics."""
 
         class Stats(C.Structure):
             _fields_ = [("reads", C.c_uint64), ("bases", C.c_uint64), ("batches", C.c_uint64), ("read_s", C.c_double),
@@ -845,7 +846,7 @@ class MultiClassifier:
 
         st = Stats()
         a, b, u = [os.fsencode(n) for n in out_names]
-        check(lib.tbk_classify_file(self._h, os.fsencode(reads_path), num_kmers_a, num_kmers_b, a, b, u, 2 if gzip_output == 2 else int(bool(gzip_output)), gzip_level,
+        check(lib.tbk_classify_file(self._h, os.fsencode(reads_path), num_kmers_a, num_kmers_b, a, b, u, int(gzip_output) if gzip_output in (2, 3) else int(bool(gzip_output)), gzip_level,
                                     tsv_fd, batch_bases, batch_reads, C.byref(st)))
         out = {name: getattr(st, name) for name, _ in Stats._fields_ if name != "_pad"}
         out["gzip_encoder"] = {0: None, 1: "host", 2: "device"}.get(st.gzip_encoder)   # who coded the bins' gzip members

@@ -394,8 +394,10 @@ class BinWriter:
 
     def __init__(self, haplotype_a_prefix: str, haplotype_b_prefix: str, unclassified_prefix: str,
                  outfile_extension: str, gzip_output: bool, level: int = -1, threads: int = 0, device: Optional[int] = None,
-                 bam_header: Optional[bytes] = None):
-        """``bam_header``: BAM bins (include/tbk.h "BAM output") - the files are ``prefix + outfile_extension`` as given (``.bam``), begin
+                 bam_header: Optional[bytes] = None, haplotag_path: Optional[str] = None):
+        """``haplotag_path`` (with ``bam_header``): the haplotag form (include/tbk.h "Haplotag output") - ONE BAM file of that name and
+        no bins; the prefixes and the extension are not used, and batches are written with ``write_counts``.
+        ``bam_header``: BAM bins (include/tbk.h "BAM output") - the files are ``prefix + outfile_extension`` as given (``.bam``), begin
         with these header bytes, and ``write`` takes batches that carry their records (``BatchReader(..., keep_records=True)``).
         ``device``: code the gzip members on that GPU (``tbk_bin_writer_use_device``: what ``classify-by-kmers`` does by itself);
         None: on the host's threads.  ``gpu_encoder`` says which it is."""
@@ -406,7 +408,12 @@ class BinWriter:
 
         self.names = output_names(haplotype_a_prefix, haplotype_b_prefix, unclassified_prefix, outfile_extension, gzip_output and bam_header is None)
         h = C.c_void_p()
-        if bam_header is not None:
+        if haplotag_path is not None:
+            if bam_header is None:
+                raise ValueError("BinWriter: the haplotag form needs the input's BAM header (bam_header)")
+            self.names = [haplotag_path]
+            check(lib.tbk_bin_writer_open_haplotag(os.fsencode(haplotag_path), bam_header, len(bam_header), level, threads, C.byref(h)))
+        elif bam_header is not None:
             check(lib.tbk_bin_writer_open_bam(*[os.fsencode(n) for n in self.names], bam_header, len(bam_header), level, threads, C.byref(h)))
         else:
             check(lib.tbk_bin_writer_open(*[os.fsencode(n) for n in self.names], int(gzip_output), level, threads, C.byref(h)))
@@ -414,11 +421,23 @@ class BinWriter:
         if device is not None:
             check(lib.tbk_bin_writer_use_device(h, device))
         self.gpu_encoder = bool(lib.tbk_bin_writer_encoder(h)) if hasattr(lib, "tbk_bin_writer_encoder") else False
+        self.gpu_rewriter = bool(lib.tbk_bin_writer_rewriter(h)) if hasattr(lib, "tbk_bin_writer_rewriter") else False
 
     def write(self, batch: Batch, bins: bytes) -> None:
         from ._lib import check, lib
 
         check(lib.tbk_bin_writer_write(self._h, batch._h, bins))
+
+    def write_counts(self, batch: Batch, bins: bytes, counts) -> None:
+        """The haplotag form's ``write``: ``counts`` is the batch's (n_reads, 2) int32 array, as ``Classifier.wait`` returns it."""
+        import numpy as np
+
+        from ._lib import check, lib
+
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        if counts.shape != (batch.n_reads, 2):
+            raise ValueError("write_counts: counts must have shape ({}, 2), not {}".format(batch.n_reads, counts.shape))
+        check(lib.tbk_bin_writer_write_counts(self._h, batch._h, bins, counts.ctypes.data))
 
     def close(self) -> None:
         if self._h is not None and self._h.value:
@@ -543,6 +562,48 @@ def bam_fastq_device(records: bytes, offsets, skip_flags: int = 0x900, device: i
     from ._lib import lib
 
     return _bam_fastq(lambda *a: lib.tbk_bam_fastq_device(device, *a), records, offsets, skip_flags)
+
+
+def bam_haplotag_status(records: bytes, offsets, bins: bytes, counts, device: Optional[int] = 0, cap: Optional[int] = None):
+    """``tbk_bam_haplotag_device`` on ``device`` (None: ``tbk_bam_haplotag``, the host's rewriter) without an exception raised:
+    (status, the bytes written, out_off, out_len).  ``cap``: the room given (None: ``len(records) + 18 n``, which always suffices)."""
+    import ctypes as C
+
+    import numpy as np
+
+    from ._lib import lib
+
+    n = len(offsets)
+    offs = (C.c_uint64 * max(1, n))(*offsets)
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(n, 2)
+    if cap is None:
+        cap = len(records) + 18 * n
+    buf = C.create_string_buffer(max(cap, 1))
+    out_off = (C.c_uint64 * (n + 1))()
+    out_len = C.c_uint64()
+    args = (records, len(records), offs, n, bins, counts.ctypes.data_as(C.POINTER(C.c_int32)), buf, cap, out_off, C.byref(out_len))
+    status = lib.tbk_bam_haplotag(*args) if device is None else lib.tbk_bam_haplotag_device(device, *args)
+    return status, C.string_at(C.addressof(buf), min(out_len.value, cap) if status == 0 else 0), list(out_off), out_len.value
+
+
+def bam_haplotag_device(records: bytes, offsets, bins: bytes, counts, device: int = 0):
+    """(the tagged records back to back, where each begins with the total last) of a run of whole BAM records (bytes; ``offsets``:
+    where each begins), every record rewritten with its bin (``bins``: one of b"ABU" per record) and its counts (n x 2 int32) as the
+    tags HP, ka and kb on the GPU (``tbk_bam_haplotag_device``; include/tbk.h "Haplotag output")."""
+    from ._lib import check
+
+    status, data, out_off, _ = bam_haplotag_status(records, offsets, bins, counts, device)
+    check(status)
+    return data, out_off
+
+
+def bam_haplotag_host(records: bytes, offsets, bins: bytes, counts):
+    """The same by the host's rewriter (``tbk_bam_haplotag``)."""
+    from ._lib import check
+
+    status, data, out_off, _ = bam_haplotag_status(records, offsets, bins, counts, None)
+    check(status)
+    return data, out_off
 
 
 def bam_fastq_host(records: bytes, offsets, skip_flags: int = 0x900):
