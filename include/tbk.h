@@ -1280,6 +1280,43 @@ int tbk_kmerdb_query_copy_spectrum(tbk_kmerdb_query *q, uint64_t spec[6][256]);
 /* Clears seen, copies, the histogram and the window total: the next assembly against the same database. */
 int tbk_kmerdb_query_reset(tbk_kmerdb_query *q);
 
+/* ---- copy-number track: where do the reads' depth and the sequences' copies disagree? ---- */
+/* A second pass over sequences (usually the ones the session was fed with tbk_kmerdb_query_add): per bin of `window`
+ * window starts, the read depth, the copies the session has counted, and how many k-mers say "collapsed" or "duplicated".
+ * q is a session made with copies != 0, k its database's k, peak >= 1 the read depth of a k-mer that the sequences
+ * should hold once, window = W >= 1.
+ * WINDOWS.  A sequence of length L has nw = max(L - k + 1, 0) window starts.  Clean windows, canonical k-mers and the
+ * counter c (0 when absent) are exactly those of tbk_kmerdb_query_add.  For a present window (c >= 1), a is the entry's
+ * copy counter in the session at the time of the call, a 32-bit value; it may be 0 when the sequence was never added.
+ * BINS.  A sequence has ceil(nw / W) bins; bin b holds the window starts [b W, min((b + 1) W, nw)).  A sequence shorter
+ * than k has no bins.
+ * PER BIN:
+ *   clean      clean windows in the bin;
+ *   absent     clean windows with c == 0 (present = clean - absent);
+ *   saturated  present windows with c == 255: the counter is capped there and no verdict is drawn from it;
+ *   collapsed  present, c < 255 and 2c > (2a + 1) peak: the reads hold the k-mer more often than the sequences do;
+ *   expanded   present, c < 255, a >= 1 and 2c < (2a - 1) peak: the sequences hold it more often than the reads do;
+ *   depth      the lower median of c over the present windows - the lower median of m sorted values v is v[(m - 1) / 2] -
+ *              and 0 when nothing is present;
+ *   copies     the lower median of min(a, 255) over the present windows, 0 when there are none.
+ * The verdicts are drawn in 64-bit integers, and a tie is consistent: with peak 10 and a = 1, c = 15 and c = 5 are
+ * neither collapsed nor expanded.  (2c <= 508, so every peak above 508 draws the verdicts of 509: no collapse, and an
+ * expansion wherever a >= 1.)
+ * The call only reads the session: the histogram, the seen bits, the copies and the window total are as they were, and
+ * the batch does not count towards the limit of 2^32 - 1 window starts.
+ * bins is host memory: the bins of sequence 0 first, each sequence's in order; pad is written as 0.  n_bins must be
+ * the sum of ceil(nw_r / window) over the sequences.  TBK_ERR_INVALID, with a message, for a session made without
+ * copies, for window == 0 or peak == 0, and for an n_bins that is not that sum; nothing is written then and the session
+ * stays usable.  n_reads == 0 or n_bins == 0 (with a matching sum) is valid and writes nothing.  An empty database is
+ * valid: every clean window is absent.
+ * The call uses the session's batch buffers and grows them as needed.  On the device it takes, per base of the batch
+ * (rounded up to passes of 2048 stream positions, one position more per sequence): the bases and their separated copy
+ * (2 bytes), c and min(a, 255) per stream position (2 bytes) and five bitmaps (5 bits) - 4.625 bytes, of which
+ * tbk_kmerdb_query_add's own buffers already hold up to 3.25 - and 16 bytes per sequence and 24 per bin beside them. */
+typedef struct tbk_depth_bin { uint32_t clean, absent, saturated, collapsed, expanded; uint8_t depth, copies, pad[2]; } tbk_depth_bin; /* 24 bytes */
+int tbk_kmerdb_query_track(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
+                           uint32_t window, uint32_t peak, tbk_depth_bin *bins, uint64_t n_bins);
+
 /* Host threads the library starts for its own host-side work (list parsing, gzip members,
  * scoring): hardware threads limited by the CPU affinity mask and the cgroup CPU quota, divided by the
  * number of ranks the launcher started on this node (LOCAL_WORLD_SIZE, or TBK_LOCAL_RANKS): one process per GPU

@@ -300,6 +300,9 @@ if HAS_DB_QUERY:
     _sig("tbk_kmerdb_query_reset", C.c_int, _vp)
     _sig("tbk_kmerdb_query_set_windows_", C.c_int, _vp, _u64)  # (test hook: the running total of window starts)
     _sig("tbk_kmerdb_query_set_wave_slots_", C.c_int, _vp, _u64)  # (test hook: the grid of the launches that stride over passes or reads)
+HAS_DB_TRACK = hasattr(lib, "tbk_kmerdb_query_track")  # (variant builds may predate the copy-number track)
+if HAS_DB_TRACK:
+    _sig("tbk_kmerdb_query_track", C.c_int, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, _vp, _u64)
 
 class DumpOptions(C.Structure):
     """tbk_dump_options (include/tbk.h)."""

@@ -1691,6 +1691,12 @@ extern "C" hipError_t tbk_launch_query_totals(const uint32_t *, const uint32_t *
 extern "C" hipError_t tbk_launch_query_counts(const uint8_t *, const uint64_t *, uint64_t, uint8_t *, uint64_t, hipStream_t);
 extern "C" hipError_t tbk_launch_query_completeness(const uint8_t *, const uint32_t *, uint64_t, uint32_t, uint32_t, unsigned long long *, hipStream_t);
 extern "C" hipError_t tbk_launch_query_spectrum(const uint8_t *, const uint32_t *, uint64_t, unsigned long long *, hipStream_t);
+// (the copy-number track's two kernels: tbk_depth.hip)
+extern "C" hipError_t tbk_launch_depth_lookup(const uint8_t *, uint64_t, uint64_t, int, const uint64_t *, const uint8_t *, const uint32_t *, const uint32_t *,
+                                              uint64_t, int, uint32_t, uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint8_t *, uint8_t *, uint64_t,
+                                              hipStream_t);
+extern "C" hipError_t tbk_launch_depth_bins(uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint8_t *, uint8_t *, const uint64_t *, const uint64_t *,
+                                            uint64_t, uint64_t, int, uint32_t, tbk_depth_bin *, uint64_t, hipStream_t);
 
 constexpr uint64_t TBK_QUERY_MAX_WINDOWS = 0xFFFFFFFFull;  // window starts of a session: a 32-bit copy counter cannot wrap
 constexpr int TBK_QUERY_MAX_PREFIX_BITS = 28;              // a directory of at most 1 GiB + 4 bytes
@@ -1712,6 +1718,7 @@ struct tbk_kmerdb_query {
     unsigned long long *d_sums = nullptr;  // 256 histogram rows, then 2 + 6 x 256 for the per-entry tallies
     void *d_pad = nullptr;                 // one zero entry that stands for the arrays of an empty database
     QueryBuf bases, offsets, sep, clean_bits, found_bits, bytes, totals, counts;
+    QueryBuf copy_bytes, saturated_bits, collapsed_bits, expanded_bits, bin_prefix, bins;  // (the copy-number track's own)
     size_t seen_bytes() const { return (size_t)((db->n + 31) / 32 + 1) * 4; }
 };
 
@@ -1742,7 +1749,8 @@ extern "C" void tbk_kmerdb_query_destroy(tbk_kmerdb_query *q) {
     if (hipSetDevice(q->device) == hipSuccess) {
         for (void *p : {(void *)q->d_dir, (void *)q->d_seen, (void *)q->d_copies, (void *)q->d_sums, q->d_pad})
             if (p) (void)hipFree(p);
-        for (QueryBuf *b : {&q->bases, &q->offsets, &q->sep, &q->clean_bits, &q->found_bits, &q->bytes, &q->totals, &q->counts})
+        for (QueryBuf *b : {&q->bases, &q->offsets, &q->sep, &q->clean_bits, &q->found_bits, &q->bytes, &q->totals, &q->counts, &q->copy_bytes,
+                            &q->saturated_bits, &q->collapsed_bits, &q->expanded_bits, &q->bin_prefix, &q->bins})
             if (b->p) (void)hipFree(b->p);
     }
     delete q;
@@ -1893,5 +1901,56 @@ extern "C" int tbk_kmerdb_query_copy_spectrum(tbk_kmerdb_query *q, uint64_t spec
     CHIP(hipMemsetAsync(d_spec, 0, 6 * 256 * sizeof(unsigned long long), nullptr));
     CHIP(tbk_launch_query_spectrum(q->db->d_counts, q->d_copies, q->db->n, d_spec, nullptr));
     CHIP(hipMemcpy(spec, d_spec, 6 * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return TBK_OK;
+}
+
+// The copy-number track (include/tbk.h has the rule; kernels: tbk_depth.hip): the batch is separated and looked up
+// again, this time without a write to the session, and reduced per bin.  The lookup's bitmaps and counter bytes reuse the
+// buffers of tbk_kmerdb_query_add; the copy bytes, three more bitmaps, the bin prefix and the bins are the call's own.
+extern "C" int tbk_kmerdb_query_track(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t window,
+                                      uint32_t peak, tbk_depth_bin *bins, uint64_t n_bins) {
+    if (!q) return cfail(TBK_ERR_INVALID, "query is NULL");
+    if (!q->with_copies) return cfail(TBK_ERR_INVALID, "the query session was made without copies: it has no copy-number track");
+    if (!window) return cfail(TBK_ERR_INVALID, "a track's window is 0: need 1 or more window starts per bin");
+    if (!peak) return cfail(TBK_ERR_INVALID, "a track's peak is 0: need the one-copy read depth, 1 or more");
+    int rc = n_reads ? tbk_check_offsets_(offsets, n_reads) : TBK_OK;
+    if (rc) return rc;
+    std::vector<uint64_t> prefix(n_reads + 1, 0);
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t len = offsets[r + 1] - offsets[r];
+        const uint64_t nw = len >= (uint64_t)q->k ? len - (uint64_t)q->k + 1 : 0;
+        prefix[r + 1] = prefix[r] + nw / window + (nw % window != 0);
+    }
+    if (prefix[n_reads] != n_bins)
+        return cfail(TBK_ERR_INVALID, "a track of these %llu sequences at window %u has %llu bins, not %llu", (unsigned long long)n_reads, window,
+                     (unsigned long long)prefix[n_reads], (unsigned long long)n_bins);
+    if (!n_bins) return TBK_OK;
+    if (!bins) return cfail(TBK_ERR_INVALID, "bins is NULL");
+    const uint64_t total = offsets[n_reads];
+    if (!bases) return cfail(TBK_ERR_INVALID, "bases is NULL");
+    if ((rc = kmerdb_device(q->device))) return rc;
+    const uint64_t sep_total = total + n_reads;  // one 'N' behind every read
+    const uint64_t passes = tbk_probe_passes(sep_total);
+    if ((rc = query_reserve(q->bases, total + 16)) || (rc = query_reserve(q->offsets, (n_reads + 1) * 8)) || (rc = query_reserve(q->sep, sep_total + 16)) ||
+        (rc = query_reserve(q->clean_bits, passes * 64 * 4)) || (rc = query_reserve(q->found_bits, passes * 64 * 4)) ||
+        (rc = query_reserve(q->saturated_bits, passes * 64 * 4)) || (rc = query_reserve(q->collapsed_bits, passes * 64 * 4)) ||
+        (rc = query_reserve(q->expanded_bits, passes * 64 * 4)) || (rc = query_reserve(q->bytes, passes * 2048)) ||
+        (rc = query_reserve(q->copy_bytes, passes * 2048)) || (rc = query_reserve(q->bin_prefix, (n_reads + 1) * 8)) ||
+        (rc = query_reserve(q->bins, n_bins * sizeof(tbk_depth_bin))))
+        return rc;
+    CHIP(hipMemcpyAsync(q->bases.p, bases, total, hipMemcpyHostToDevice, nullptr));
+    CHIP(hipMemcpyAsync(q->offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, nullptr));
+    CHIP(hipMemcpy(q->bin_prefix.p, prefix.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice));  // (prefix is pageable and local: a copy that has left it on return)
+    CHIP(tbk_launch_separate(q->bases.as<uint8_t>(), q->offsets.as<uint64_t>(), n_reads, q->sep.as<uint8_t>(), nullptr));
+    const tbk_kmerdb *db = q->db;
+    CHIP(tbk_launch_depth_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, db->n ? db->d_keys : (const uint64_t *)q->d_pad,
+                                 db->n ? db->d_counts : (const uint8_t *)q->d_pad, q->d_copies, q->d_dir, db->n, q->prefix_bits,
+                                 std::min<uint32_t>(peak, 509), q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(),
+                                 q->saturated_bits.as<uint32_t>(), q->collapsed_bits.as<uint32_t>(), q->expanded_bits.as<uint32_t>(), q->bytes.as<uint8_t>(),
+                                 q->copy_bytes.as<uint8_t>(), q->wave_slots, nullptr));
+    CHIP(tbk_launch_depth_bins(q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(), q->saturated_bits.as<uint32_t>(), q->collapsed_bits.as<uint32_t>(),
+                               q->expanded_bits.as<uint32_t>(), q->bytes.as<uint8_t>(), q->copy_bytes.as<uint8_t>(), q->offsets.as<uint64_t>(),
+                               q->bin_prefix.as<uint64_t>(), n_reads, n_bins, q->k, window, q->bins.as<tbk_depth_bin>(), q->wave_slots, nullptr));
+    CHIP(hipMemcpy(bins, q->bins.p, n_bins * sizeof(tbk_depth_bin), hipMemcpyDeviceToHost));
     return TBK_OK;
 }

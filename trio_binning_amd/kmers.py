@@ -1384,6 +1384,12 @@ class HomopolymerCompressor:
             pass
 
 
+# one bin of a copy-number track (``tbk_depth_bin``, 24 bytes)
+DEPTH_BIN = np.dtype([("clean", "<u4"), ("absent", "<u4"), ("saturated", "<u4"), ("collapsed", "<u4"), ("expanded", "<u4"),
+                      ("depth", "u1"), ("copies", "u1"), ("pad", "u1", (2,))])
+assert DEPTH_BIN.itemsize == 24
+
+
 class DatabaseQuery:
     """How often did the reads see the k-mers of these sequences?  (``tbk_kmerdb_query``, include/tbk.h.)
 
@@ -1436,6 +1442,30 @@ class DatabaseQuery:
         spec = np.zeros((6, 256), dtype=np.uint64)
         check(lib.tbk_kmerdb_query_copy_spectrum(self._h, spec.ctypes.data))
         return spec
+
+    def track(self, bases: np.ndarray, offsets: np.ndarray, window: int, peak: int) -> Tuple[np.ndarray, np.ndarray]:
+        """The copy-number track of a batch (``tbk_kmerdb_query_track``, include/tbk.h): per bin of ``window`` window starts
+        the clean, absent and saturated windows, the lower medians ``depth`` (of ``c``) and ``copies`` (of the session's
+        copy counter, capped at 255) over the present ones, and the windows that read as ``collapsed`` -
+        ``2c > (2a + 1) peak`` - or ``expanded`` - ``a >= 1`` and ``2c < (2a - 1) peak``; ``peak`` is the read depth of a
+        k-mer the sequences should hold once.  Returns (bins as a ``DEPTH_BIN`` array, uint64 prefix of ``n + 1`` entries):
+        the bins of sequence ``r`` are ``bins[prefix[r]:prefix[r + 1]]``.  The session is only read.  ``ValueError`` for a
+        session made without ``copies`` and for a ``window`` or ``peak`` below 1."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.size - 1, 0)
+        window, peak = int(window), int(peak)
+        if not self.copies or not 1 <= window < 1 << 32 or not 1 <= peak < 1 << 32:
+            # the library's own refusal and message, for the values a C uint32_t can carry
+            check(lib.tbk_kmerdb_query_track(self._h, None, None, 0, min(max(window, 0), 0xFFFFFFFF), min(max(peak, 0), 0xFFFFFFFF), None, 0))
+            raise ValueError("track: window {} and peak {} must lie in 1 .. 2^32 - 1".format(window, peak))
+        lengths = np.diff(offsets.astype(np.int64)) if n else np.zeros(0, dtype=np.int64)
+        starts = np.maximum(lengths - self.k + 1, 0)
+        prefix = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum((starts + window - 1) // window, out=prefix[1:])
+        bins = np.zeros(int(prefix[-1]), dtype=DEPTH_BIN)
+        check(lib.tbk_kmerdb_query_track(self._h, bases.ctypes.data, offsets.ctypes.data, n, window, peak, bins.ctypes.data, bins.size))
+        return bins, prefix
 
     def reset(self) -> None:
         """Forget every batch: the next assembly against the same database."""
