@@ -1317,6 +1317,48 @@ typedef struct tbk_depth_bin { uint32_t clean, absent, saturated, collapsed, exp
 int tbk_kmerdb_query_track(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
                            uint32_t window, uint32_t peak, tbk_depth_bin *bins, uint64_t n_bins);
 
+/* ---- repair candidates: which one-base edit mends each stretch of broken windows? ---------- */
+/* A third pass over sequences: every maximal stretch of windows the database does not hold, and the one-base edits that
+ * make every window over the edited position a k-mer the database holds.  q is a session with or without copies, k its
+ * database's k, min_count in 1..255, min_support in 1..32.  The threshold is m = max(floor, min_count), floor 2 for a solid
+ * database and 1 for a full one, as tbk_kmerdb_query_add has it.
+ * WINDOWS AND STRETCHES.  Clean windows, case folding, canonical k-mers and the counter c are exactly those of
+ * tbk_kmerdb_query_add.  A window is BROKEN when it is clean and c < m.  A STRETCH is a maximal run [f, l] of consecutive
+ * broken window starts of one sequence, r = l - f + 1; its neighbours are found, not clean, or the sequence's ends.
+ * Stretches never join across sequences.
+ * CANDIDATES.  A stretch with r > k is LONG and is not attempted.  Otherwise every window of the stretch holds the
+ * positions P = [l, f + k - 1] - k - r + 1 of them, all ACGT - and the gaps Q = [l + 1, f + k - 1], gap q in front of
+ * base q.  With s the sequence, case folded:
+ *   SUB(p, b)  p in P, b each of the three bases that differ from s[p];
+ *   DEL(p)     p in P, unless p - 1 is in P and s[p-1] == s[p]: deleting any base of a run is one edit, left-aligned;
+ *   INS(q, b)  q in Q, b in ACGT, unless q - 1 is in Q and s[q-1] == b: the same left alignment.
+ * At most 8k - 4 candidates.
+ * THE WINDOWS THAT COUNT, of the edited sequence s' of a sequence of length L:
+ *   SUB  window starts max(0, p-k+1) .. min(p, L-k);
+ *   DEL  those that hold both s'[p-1] and s'[p]: max(0, p-k+1) .. min(p-1, L-1-k); none for p = 0 or p = L-1;
+ *   INS  those that hold s'[q]: max(0, q-k+1) .. min(q, L+1-k).
+ * ACCEPTANCE.  Windows of s' that are not clean are skipped; support is the number of clean ones among them, depth the
+ * smallest c among the clean ones.  A candidate is ACCEPTED when support >= min_support and every clean window has c >= m.
+ * RESULT.  One record per stretch, ordered by (read, first), in memory of tbk_host_alloc: *repairs is the caller's to
+ * tbk_host_free (NULL when there is no stretch).  first = f, windows = r, accepted = the number of accepted candidates;
+ * kind is 0 NONE (attempted, nothing accepted), 1 SUB, 2 DEL, 3 INS or 4 LONG.  For kinds 1 to 3, pos (p, or q for an
+ * insertion), base (the new base as upper-case ASCII, 0 for DEL), support and depth describe the accepted candidate that
+ * is smallest by (kind, pos, base); for kinds 0 and 4 they are 0.  pad is 0.
+ * The call only reads the session: the histogram, the seen bits, the copies and the window total are as they were, and
+ * the batch does not count towards the limit of 2^32 - 1 window starts.  An empty database is valid: every clean window is
+ * broken and nothing is accepted.  TBK_ERR_INVALID, with a message, for min_count outside 1..255 or min_support outside
+ * 1..32 - nothing is written then and the session stays usable - and for a sequence of 2^32 or more bases.
+ * The call uses the session's batch buffers and grows them as needed.  On the device it takes, per base of the batch
+ * (rounded up to passes of 2048 stream positions, one position more per sequence): the bases and their separated copy
+ * (2 bytes), the clean and the broken bitmap (2 bits) and, until the call returns, the compaction's flags (1 bit and 16
+ * bytes per 1024 positions) - 2.39 bytes, of which tbk_kmerdb_query_add's own buffers already hold 2.25 - and 8 bytes per
+ * sequence and 40 per stretch beside them. */
+enum { TBK_REPAIR_NONE = 0, TBK_REPAIR_SUB = 1, TBK_REPAIR_DEL = 2, TBK_REPAIR_INS = 3, TBK_REPAIR_LONG = 4 };
+typedef struct tbk_repair { uint64_t read, first, pos; uint32_t windows; uint16_t accepted;
+                            uint8_t kind, base, support, depth, pad[6]; } tbk_repair;  /* 40 bytes, pad 0 */
+int tbk_kmerdb_query_repairs(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
+                             uint32_t min_count, uint32_t min_support, tbk_repair **repairs, uint64_t *n_repairs);
+
 /* Host threads the library starts for its own host-side work (list parsing, gzip members,
  * scoring): hardware threads limited by the CPU affinity mask and the cgroup CPU quota, divided by the
  * number of ranks the launcher started on this node (LOCAL_WORLD_SIZE, or TBK_LOCAL_RANKS): one process per GPU

@@ -303,6 +303,10 @@ if HAS_DB_QUERY:
 HAS_DB_TRACK = hasattr(lib, "tbk_kmerdb_query_track")  # (variant builds may predate the copy-number track)
 if HAS_DB_TRACK:
     _sig("tbk_kmerdb_query_track", C.c_int, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, _vp, _u64)
+HAS_DB_REPAIRS = hasattr(lib, "tbk_kmerdb_query_repairs")  # (variant builds may predate the repair candidates)
+if HAS_DB_REPAIRS:
+    _sig("tbk_kmerdb_query_repairs", C.c_int, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, C.POINTER(_vp), _u64p)
+    _sig("tbk_kmerdb_query_repair_times_", C.c_int, _vp, _vp)  # (measuring hook: the last call's two host-clock times, ms)
 
 class DumpOptions(C.Structure):
     """tbk_dump_options (include/tbk.h)."""

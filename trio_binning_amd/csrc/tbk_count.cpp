@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
+#include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1697,6 +1698,14 @@ extern "C" hipError_t tbk_launch_depth_lookup(const uint8_t *, uint64_t, uint64_
                                               hipStream_t);
 extern "C" hipError_t tbk_launch_depth_bins(uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint8_t *, uint8_t *, const uint64_t *, const uint64_t *,
                                             uint64_t, uint64_t, int, uint32_t, tbk_depth_bin *, uint64_t, hipStream_t);
+// (the repair candidates' four kernels: tbk_repair.hip)
+extern "C" hipError_t tbk_launch_repair_lookup(const uint8_t *, uint64_t, uint64_t, int, const uint64_t *, const uint8_t *, const uint32_t *, uint64_t, int,
+                                               uint32_t, uint32_t *, uint32_t *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_repair_heads(const uint32_t *, uint64_t, uint64_t *, unsigned long long *, hipStream_t);
+extern "C" hipError_t tbk_launch_repair_stretches(const uint32_t *, uint64_t, const uint64_t *, uint64_t, const uint64_t *, const unsigned long long *,
+                                                  tbk_repair *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_repair(const uint8_t *, const uint64_t *, int, const uint64_t *, const uint8_t *, const uint32_t *, uint64_t, int, uint32_t,
+                                        uint32_t, tbk_repair *, uint64_t, uint64_t, hipStream_t);
 
 constexpr uint64_t TBK_QUERY_MAX_WINDOWS = 0xFFFFFFFFull;  // window starts of a session: a 32-bit copy counter cannot wrap
 constexpr int TBK_QUERY_MAX_PREFIX_BITS = 28;              // a directory of at most 1 GiB + 4 bytes
@@ -1719,6 +1728,8 @@ struct tbk_kmerdb_query {
     void *d_pad = nullptr;                 // one zero entry that stands for the arrays of an empty database
     QueryBuf bases, offsets, sep, clean_bits, found_bits, bytes, totals, counts;
     QueryBuf copy_bytes, saturated_bits, collapsed_bits, expanded_bits, bin_prefix, bins;  // (the copy-number track's own)
+    QueryBuf repairs;                                                                      // (the repair candidates' records)
+    double repair_ms[2] = {0, 0};  // (tbk_kmerdb_query_repair_times_)
     size_t seen_bytes() const { return (size_t)((db->n + 31) / 32 + 1) * 4; }
 };
 
@@ -1750,7 +1761,7 @@ extern "C" void tbk_kmerdb_query_destroy(tbk_kmerdb_query *q) {
         for (void *p : {(void *)q->d_dir, (void *)q->d_seen, (void *)q->d_copies, (void *)q->d_sums, q->d_pad})
             if (p) (void)hipFree(p);
         for (QueryBuf *b : {&q->bases, &q->offsets, &q->sep, &q->clean_bits, &q->found_bits, &q->bytes, &q->totals, &q->counts, &q->copy_bytes,
-                            &q->saturated_bits, &q->collapsed_bits, &q->expanded_bits, &q->bin_prefix, &q->bins})
+                            &q->saturated_bits, &q->collapsed_bits, &q->expanded_bits, &q->bin_prefix, &q->bins, &q->repairs})
             if (b->p) (void)hipFree(b->p);
     }
     delete q;
@@ -1952,5 +1963,90 @@ extern "C" int tbk_kmerdb_query_track(tbk_kmerdb_query *q, const uint8_t *bases,
                                q->expanded_bits.as<uint32_t>(), q->bytes.as<uint8_t>(), q->copy_bytes.as<uint8_t>(), q->offsets.as<uint64_t>(),
                                q->bin_prefix.as<uint64_t>(), n_reads, n_bins, q->k, window, q->bins.as<tbk_depth_bin>(), q->wave_slots, nullptr));
     CHIP(hipMemcpy(bins, q->bins.p, n_bins * sizeof(tbk_depth_bin), hipMemcpyDeviceToHost));
+    return TBK_OK;
+}
+
+// The repair candidates (include/tbk.h has the rule; kernels: tbk_repair.hip): the batch is separated and looked up
+// again without a write to the session, the heads of the broken stretches are compacted into records at their exact
+// number, and the repair kernel completes the records in place.  The two bitmaps reuse the buffers of
+// tbk_kmerdb_query_add; the compaction's flags are the call's own and freed on return, the records stay with the session.
+extern "C" int tbk_kmerdb_query_repairs(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t min_count,
+                                        uint32_t min_support, tbk_repair **repairs, uint64_t *n_repairs) {
+    if (!q || !repairs || !n_repairs) return cfail(TBK_ERR_INVALID, "tbk_kmerdb_query_repairs: NULL argument");
+    if (min_count < 1 || min_count > 255) return cfail(TBK_ERR_INVALID, "repairs: min_count %u: need 1 <= min_count <= 255", min_count);
+    if (min_support < 1 || min_support > 32) return cfail(TBK_ERR_INVALID, "repairs: min_support %u: need 1 <= min_support <= 32", min_support);
+    *repairs = nullptr;
+    *n_repairs = 0;
+    if (!n_reads) return TBK_OK;
+    int rc = tbk_check_offsets_(offsets, n_reads);
+    if (rc) return rc;
+    const uint64_t total = offsets[n_reads];
+    if (total && !bases) return cfail(TBK_ERR_INVALID, "bases is NULL");
+    uint64_t windows = 0;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t len = offsets[r + 1] - offsets[r];
+        if (len >= (uint64_t)q->k) windows += len - (uint64_t)q->k + 1;
+        if (len >= (1ull << 32))
+            return cfail(TBK_ERR_INVALID, "repairs: sequence %llu has %llu bases: a record counts a stretch's windows in 32 bits", (unsigned long long)r,
+                         (unsigned long long)len);
+    }
+    if (!windows) return TBK_OK;
+    if ((rc = kmerdb_device(q->device))) return rc;
+    const uint64_t sep_total = total + n_reads;  // one 'N' behind every read
+    const uint64_t passes = tbk_probe_passes(sep_total);
+    if ((rc = query_reserve(q->bases, total + 16)) || (rc = query_reserve(q->offsets, (n_reads + 1) * 8)) || (rc = query_reserve(q->sep, sep_total + 16)) ||
+        (rc = query_reserve(q->clean_bits, passes * 64 * 4)) || (rc = query_reserve(q->found_bits, passes * 64 * 4)))
+        return rc;
+    const tbk_kmerdb *db = q->db;
+    const uint64_t *d_keys = db->n ? db->d_keys : (const uint64_t *)q->d_pad;
+    const uint8_t *d_counts = db->n ? db->d_counts : (const uint8_t *)q->d_pad;
+    const uint32_t m = std::max<uint32_t>(db->floor, min_count);
+    uint32_t *d_broken = q->found_bits.as<uint32_t>();
+    const auto t0 = std::chrono::steady_clock::now();
+    CHIP(hipMemcpyAsync(q->bases.p, bases, total, hipMemcpyHostToDevice, nullptr));
+    CHIP(hipMemcpyAsync(q->offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, nullptr));
+    CHIP(tbk_launch_separate(q->bases.as<uint8_t>(), q->offsets.as<uint64_t>(), n_reads, q->sep.as<uint8_t>(), nullptr));
+    CHIP(tbk_launch_repair_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, d_keys, d_counts, q->d_dir, db->n, q->prefix_bits, m,
+                                  q->clean_bits.as<uint32_t>(), d_broken, q->wave_slots, nullptr));
+    Compaction sel;
+    unsigned long long found = 0;
+    hipError_t e = sel.reserve(passes * 2048, nullptr);
+    if (e == hipSuccess) e = tbk_launch_repair_heads(d_broken, passes, sel.d_flags, sel.counts(), nullptr);
+    if (e == hipSuccess) e = sel.total(&found);
+    const auto t1 = std::chrono::steady_clock::now();
+    const bool sane = found <= windows;  // (nothing is allocated or written by a count that cannot be)
+    tbk_repair *home = nullptr;
+    if (e == hipSuccess && sane && found) {
+        if ((rc = query_reserve(q->repairs, found * sizeof(tbk_repair)))) return rc;
+        e = tbk_launch_repair_stretches(d_broken, passes, q->offsets.as<uint64_t>(), n_reads, sel.d_flags, sel.offsets(), q->repairs.as<tbk_repair>(),
+                                        found, nullptr);
+        if (e == hipSuccess)
+            e = tbk_launch_repair(q->sep.as<uint8_t>(), q->offsets.as<uint64_t>(), q->k, d_keys, d_counts, q->d_dir, db->n, q->prefix_bits, m, min_support,
+                                  q->repairs.as<tbk_repair>(), found, q->wave_slots, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        q->repair_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+        q->repair_ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+        if (e == hipSuccess && !(home = (tbk_repair *)tbk_host_alloc(found * sizeof(tbk_repair)))) return TBK_ERR_NOMEM;  // (tbk_host_alloc has left the reason)
+        if (e == hipSuccess) e = hipMemcpy(home, q->repairs.p, found * sizeof(tbk_repair), hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess || !sane) {
+        tbk_host_free(home);
+        (void)hipGetLastError();
+        if (e != hipSuccess)
+            return cfail(e == hipErrorOutOfMemory ? TBK_ERR_NOMEM : TBK_ERR_HIP, "tbk_kmerdb_query_repairs (%llu bases): %s", (unsigned long long)total,
+                         hipGetErrorString(e));
+        return cfail(TBK_ERR_HIP, "tbk_kmerdb_query_repairs: %llu stretches among %llu windows", found, (unsigned long long)windows);
+    }
+    *repairs = home;
+    *n_repairs = found;
+    return TBK_OK;
+}
+
+// (measuring hook, not in tbk.h: the host's clock over the last call that found a stretch - the copy in, the lookup and the
+// compaction up to the stretch count, then the records and the repair kernel up to the stream's end; tools/measure_repairs.py)
+extern "C" int tbk_kmerdb_query_repair_times_(tbk_kmerdb_query *q, double ms[2]) {
+    if (!q || !ms) return cfail(TBK_ERR_INVALID, "NULL argument");
+    ms[0] = q->repair_ms[0];
+    ms[1] = q->repair_ms[1];
     return TBK_OK;
 }

@@ -1389,6 +1389,12 @@ DEPTH_BIN = np.dtype([("clean", "<u4"), ("absent", "<u4"), ("saturated", "<u4"),
                       ("depth", "u1"), ("copies", "u1"), ("pad", "u1", (2,))])
 assert DEPTH_BIN.itemsize == 24
 
+# one stretch of broken windows and its repair candidates (``tbk_repair``, 40 bytes)
+REPAIR = np.dtype([("read", "<u8"), ("first", "<u8"), ("pos", "<u8"), ("windows", "<u4"), ("accepted", "<u2"), ("kind", "u1"), ("base", "u1"),
+                   ("support", "u1"), ("depth", "u1"), ("pad", "u1", (6,))])
+assert REPAIR.itemsize == 40
+REPAIR_NONE, REPAIR_SUB, REPAIR_DEL, REPAIR_INS, REPAIR_LONG = range(5)
+
 
 class DatabaseQuery:
     """How often did the reads see the k-mers of these sequences?  (``tbk_kmerdb_query``, include/tbk.h.)
@@ -1466,6 +1472,33 @@ class DatabaseQuery:
         bins = np.zeros(int(prefix[-1]), dtype=DEPTH_BIN)
         check(lib.tbk_kmerdb_query_track(self._h, bases.ctypes.data, offsets.ctypes.data, n, window, peak, bins.ctypes.data, bins.size))
         return bins, prefix
+
+    def repairs(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 2, min_support: int = 1) -> np.ndarray:
+        """The repair candidates of a batch (``tbk_kmerdb_query_repairs``, include/tbk.h): one ``REPAIR`` record per maximal
+        stretch of broken windows - clean, with ``c`` below ``max(floor, min_count)`` - ordered by (read, first).  ``windows`` is
+        the stretch's length, ``accepted`` the number of one-base edits at the positions all its windows share that leave
+        every window over the edit held by the database, with at least ``min_support`` clean windows to say so; ``kind``
+        (``REPAIR_NONE``, ``_SUB``, ``_DEL``, ``_INS``, or ``_LONG`` for a stretch of more than k windows, which is not attempted),
+        ``pos``, ``base``, ``support`` and ``depth`` describe the smallest accepted edit by (kind, pos, base).  The session is
+        only read.  ``ValueError`` for a ``min_count`` outside 1..255 or a ``min_support`` outside 1..32."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.size - 1, 0)
+        min_count, min_support = int(min_count), int(min_support)
+        ptr, count = C.c_void_p(), C.c_uint64()
+        if not 0 <= min_count < 1 << 32 or not 0 <= min_support < 1 << 32:
+            # the library's own refusal and message, for the values a C uint32_t can carry
+            check(lib.tbk_kmerdb_query_repairs(self._h, None, None, 0, min(max(min_count, 0), 0xFFFFFFFF), min(max(min_support, 0), 0xFFFFFFFF),
+                                               C.byref(ptr), C.byref(count)))
+            raise ValueError("repairs: min_count {} must lie in 1 .. 255 and min_support {} in 1 .. 32".format(min_count, min_support))
+        check(lib.tbk_kmerdb_query_repairs(self._h, bases.ctypes.data, offsets.ctypes.data, n, min_count, min_support, C.byref(ptr), C.byref(count)))
+        try:
+            records = np.zeros(count.value, dtype=REPAIR)
+            if count.value:
+                C.memmove(records.ctypes.data, ptr, count.value * REPAIR.itemsize)
+        finally:
+            lib.tbk_host_free(ptr)
+        return records
 
     def reset(self) -> None:
         """Forget every batch: the next assembly against the same database."""
