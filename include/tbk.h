@@ -990,6 +990,18 @@ int tbk_kmerdb_joint_spectrum(const tbk_kmerdb *x, const tbk_kmerdb *y, uint64_t
  * and class 2 those of them the child inherited. */
 int tbk_kmerdb_origin_spectrum(const tbk_kmerdb *base, const tbk_kmerdb *y, uint32_t y_min, uint32_t y_max,
                                const tbk_kmerdb *z, uint32_t z_min, uint32_t z_max, uint64_t spec[4 * 256]);
+/* ONE database by the GC content of its k-mers: k-mer multiplicity against GC, the matrix `kat gcp` plots - a contaminant of
+ * another GC and depth is a second cloud in it, and a library that under-covers AT-rich or GC-rich sequence shows in its rows.
+ * spec[g * 256 + c] is the number of entries whose key has g G-or-C bases and whose counter is c.  THE GC OF A KEY: a key is a
+ * rank, 2 bits a base with A, C, G, T = 0, 1, 2, 3, and a base is G or C exactly when its two bits differ, so
+ * g = popcount((key ^ (key >> 1)) & 0x5555555555555555), 0..k; a k-mer and its reverse complement have one g, so the canonical
+ * choice does not matter, and in a homopolymer-compressed database g is the GC of the compressed k-mer.  Rows above k are 0 and
+ * column 0 is 0; column c >= 1 sums over g to row c of the database's own counters (tbk_kmerdb_histogram, from the floor on),
+ * and the whole matrix to n.  Either floor and either space are accepted; an empty database gives a zero matrix and TBK_OK.
+ * One launch striding over the tiles of 1024 entries (csrc/tbk_compare.hip); blocks tally the (k + 1) x 256 cells in LDS and
+ * flush once.  Beside the input the call holds the matrix (66 KiB).  A NULL argument is TBK_ERR_INVALID with the reason in
+ * tbk_last_error(); the database is only read; TBK_ERR_NOMEM leaves it as it was and the device usable. */
+int tbk_kmerdb_gc_spectrum(const tbk_kmerdb *db, uint64_t spec[33 * 256]);
 /* A selection that stays a database: the entries of `base` that up to two partners let pass, with a counter of choice - the
  * hap-mer databases of Merqury's hapmers.sh ("the parental k-mers the child inherited, with the child's counters"), the k-mers
  * two lanes share, a library minus a contaminant.  Every other join here ends in text, in keys without counters or in a tally.
@@ -999,7 +1011,11 @@ int tbk_kmerdb_origin_spectrum(const tbk_kmerdb *base, const tbk_kmerdb *y, uint
  * tbk_kmerdb_origin_spectrum - and are NOT the "2 or more" rule of the subtractions: a full partner is asked with min = 2 to
  * ignore its once-seen k-mers, a floor-2 partner asked with [1, 255] means "holds the key at all".  n_partners is 0, 1 or 2
  * (`partners` may be NULL for 0); more partners are done by chaining calls.  A database may appear more than once and may be
- * `base` itself; either floor is accepted in every position.
+ * `base` itself; either floor is accepted in every position.  On top of all that an entry is kept only when the G-or-C bases
+ * of its key (tbk_kmerdb_gc_spectrum has the rule) lie in [o->min_gc, o->max_gc]: a cloud of that matrix carved out as a
+ * database.  The bounds are bases, not per cent; 0 and 32, which tbk_select_options_init sets, never bind, nor does any bound
+ * above k.  The two fields were added behind `counter`: a caller whose `size` is the struct's of before them (24 bytes) is
+ * accepted as it was and gets no GC bound.
  * THE COUNTER OF A KEPT ENTRY.  TBK_SELECT_COUNTER_BASE: the base's.  _MIN: the minimum of the base's counter and every REQUIRE
  * partner's.  _SUM: min(255, base + the REQUIRE partners'), added in 32 bits.  EXCLUDE partners never contribute; with no
  * REQUIRE partner all three rules give the base's counter.
@@ -1011,10 +1027,10 @@ int tbk_kmerdb_origin_spectrum(const tbk_kmerdb *base, const tbk_kmerdb *y, uint
  * entries and nothing else.  A floor-2 header would claim that every k-mer of a library seen twice is here; a selection makes
  * no such claim.  An empty selection, or an empty base, is TBK_OK and a valid database of n = 0 (its file: 2096 bytes).
  * REFUSALS are TBK_ERR_INVALID with the reason in tbk_last_error(): a NULL base, o, out or partner's db; n_partners outside
- * 0..2; a mode, counter rule or range outside the above; a different k, device or space among the databases (the messages of
+ * 0..2; a mode, counter rule or range outside the above (min_gc > max_gc or max_gc > 32 among them); a different k, device or space among the databases (the messages of
  * the spectra above).  *out is NULL after every error; TBK_ERR_NOMEM leaves every input as it was and the device usable.
  * LAUNCHES (csrc/tbk_select.hip): flag - one block per tile of 1024 entries of base finds the tile's bounds in both partners,
- * and every entry tests its own counter, then the first partner, then the second only if the first let it pass (EXCLUDE
+ * and every entry tests its own counter and GC, then the first partner, then the second only if the first let it pass (EXCLUDE
  * partners are asked first); the scan of the tile counts; the scatter of keys and counters - for _MIN and _SUM with one more
  * bounded bisection per kept entry and REQUIRE partner, the kept entries dealt to consecutive threads so that a wave bisects
  * with all its lanes; the tally of the output's counters.  No block waits for another.  The
@@ -1034,8 +1050,9 @@ typedef struct tbk_select_options {
     size_t size;                    /* sizeof(tbk_select_options) of the caller (tbk_select_options_init sets it) */
     uint32_t min_count, max_count;  /* base's counter range, 1 <= min <= max <= 255 */
     int counter;                    /* TBK_SELECT_COUNTER_BASE, _MIN or _SUM */
+    uint32_t min_gc, max_gc;        /* base's GC range in bases, 0 <= min <= max <= 32; read only from a `size` that reaches them */
 } tbk_select_options;
-void tbk_select_options_init(tbk_select_options *o);  /* 1, 255, TBK_SELECT_COUNTER_BASE */
+void tbk_select_options_init(tbk_select_options *o);  /* 1, 255, TBK_SELECT_COUNTER_BASE, 0, 32 */
 int tbk_kmerdb_select(const tbk_kmerdb *base, const tbk_select_partner *partners, int n_partners, const tbk_select_options *o,
                       tbk_kmerdb **out);
 /* The het-mer pairs of ONE database: the look inside a library that the k-mer-pair analysis of Smudgeplot / PloidyPlot takes

@@ -251,6 +251,9 @@ HAS_DB_COMPARE = hasattr(lib, "tbk_kmerdb_joint_spectrum")  # (variant builds of
 if HAS_DB_COMPARE:
     _sig("tbk_kmerdb_joint_spectrum", C.c_int, _vp, _vp, _vp)
     _sig("tbk_kmerdb_origin_spectrum", C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp)
+HAS_DB_GC = hasattr(lib, "tbk_kmerdb_gc_spectrum")  # (variant builds of tools/build_variant.sh may predate the GC matrix)
+if HAS_DB_GC:
+    _sig("tbk_kmerdb_gc_spectrum", C.c_int, _vp, _vp)
 class SelectPartner(C.Structure):
     """tbk_select_partner (include/tbk.h)."""
     _fields_ = [("db", C.c_void_p), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("mode", C.c_int)]
@@ -258,7 +261,8 @@ class SelectPartner(C.Structure):
 
 class SelectOptions(C.Structure):
     """tbk_select_options (include/tbk.h)."""
-    _fields_ = [("size", C.c_size_t), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("counter", C.c_int)]
+    _fields_ = [("size", C.c_size_t), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("counter", C.c_int), ("min_gc", C.c_uint32),
+                ("max_gc", C.c_uint32)]
 
 
 SELECT_REQUIRE, SELECT_EXCLUDE = 1, 2

@@ -202,6 +202,14 @@ TBK_HD uint64_t tbk_revcomp64(uint64_t x, int m) {
     return y >> (64 - 2 * m);
 }
 
+// The G-or-C bases of a count database's key (tbk_kmerdb_gc_spectrum, tbk_kmerdb_select; 0..32).  A key there is a
+// lexicographic rank: 2 bits a base with A, C, G, T = 0, 1, 2, 3, and a base is G or C exactly when its two bits differ.
+// Bits above 2k are zero and add nothing, so k is not asked for; k = 32 uses the top bit.  A k-mer and its reverse complement
+// have one GC, so it does not matter which of the two the counter kept.
+TBK_HD uint32_t tbk_rank_gc(uint64_t rank) {
+    return (uint32_t)__builtin_popcountll((rank ^ (rank >> 1)) & 0x5555555555555555ull);
+}
+
 // (m, w, o) for a given k, wanted w and table size.  m_need = shortest m-mer with at most
 // ~0.9 keys per distinct canonical m-mer (the 300 M-key / m = 16 / w = 6 operating point that
 // was measured); the preferred m is max(16, m_need), then one shorter (never below m_need or

@@ -65,9 +65,10 @@ struct TbkSelectPartner {
     uint32_t c_min, c_max;
     uint32_t require;
 };
-// flag: the entries of base with a counter in [c_min, c_max] that both partners let pass, p0 asked before p1
+// flag: the entries of base with a counter in [c_min, c_max] and tbk_rank_gc(key) in [g_min, g_max] that both partners let
+// pass, p0 asked before p1
 hipError_t tbk_launch_kmerdb_select_flag(const uint64_t *base_keys, const uint8_t *base_counts, uint64_t n, uint32_t c_min, uint32_t c_max,
-                                         const TbkSelectPartner *p0, const TbkSelectPartner *p1, uint64_t *d_flags,
+                                         uint32_t g_min, uint32_t g_max, const TbkSelectPartner *p0, const TbkSelectPartner *p1, uint64_t *d_flags,
                                          unsigned long long *d_tile_counts, hipStream_t stream);
 // scatter with a counter made of the base's and the partners' (rule: TBK_SELECT_COUNTER_MIN or _SUM; both partners are REQUIRE
 // ones, or not there); the rule that keeps the base's counter is tbk_launch_kmerdb_scatter_pairs
@@ -84,6 +85,11 @@ hipError_t tbk_launch_kmerdb_origin_spectrum(const uint64_t *base_keys, const ui
                                              const uint8_t *y_counts, uint64_t n_y, uint32_t y_min, uint32_t y_max, const uint64_t *z_keys,
                                              const uint8_t *z_counts, uint64_t n_z, uint32_t z_min, uint32_t z_max, uint32_t keep,
                                              unsigned long long *d_spec, hipStream_t stream);
+// One database by the G-or-C bases of its keys and by counter: d_spec holds 33 * 256 words (cell gc * 256 + c), zeroed by the
+// caller.  layout 0 is the build's choice of what a block keeps in LDS; 1 (the whole matrix) and 2 (the counters below 64)
+// name the two for the measurement.
+hipError_t tbk_launch_kmerdb_gc_spectrum(const uint64_t *d_keys, const uint8_t *d_counts, uint64_t n, int k, int layout, unsigned long long *d_spec,
+                                         hipStream_t stream);
 // `blocks` under the entry cap of tbk_count_set_grid_caps_ (tbk_count_kernels.hip), for strided launches in other files
 unsigned tbk_count_entry_grid_(uint64_t blocks);
 

@@ -1367,6 +1367,14 @@ extern "C" int tbk_kmerdb_origin_spectrum(const tbk_kmerdb *base, const tbk_kmer
     });
 }
 
+// One database by the GC content of its keys (tbk_compare.hip): 33 x 256 words on the device (66 KiB) beside the input.
+extern "C" int tbk_kmerdb_gc_spectrum(const tbk_kmerdb *db, uint64_t spec[33 * 256]) {
+    if (!db || !spec) return cfail(TBK_ERR_INVALID, "tbk_kmerdb_gc_spectrum: NULL argument");
+    return compare_run("tbk_kmerdb_gc_spectrum", db->device, 33 * 256, spec, [&](unsigned long long *d_spec) {
+        return tbk_launch_kmerdb_gc_spectrum(db->d_keys, db->d_counts, db->n, db->k, 0, d_spec, nullptr);
+    });
+}
+
 // (measurement hook, not in tbk.h: tools/measure_union.py makes databases of 1e8 entries where they lie.  Takes over d_keys and
 // d_counts - device memory of hipMalloc, freed with the database - once the pass that checks a loaded file has found them in
 // order, within 2k bits and at or above the floor; the histogram is that pass's tally, row 0 = n.)
@@ -1474,6 +1482,8 @@ extern "C" void tbk_select_options_init(tbk_select_options *o) {
     o->min_count = 1;
     o->max_count = 255;
     o->counter = TBK_SELECT_COUNTER_BASE;
+    o->min_gc = 0;
+    o->max_gc = 32;
 }
 
 static bool select_range_ok(uint32_t lo, uint32_t hi) { return lo >= 1 && lo <= hi && hi <= 255; }
@@ -1491,13 +1501,18 @@ extern "C" int tbk_kmerdb_select(const tbk_kmerdb *base, const tbk_select_partne
     if (n_partners && !partners) return cfail(TBK_ERR_INVALID, "%s: NULL argument", who);
     tbk_select_options o;
     tbk_select_options_init(&o);
-    if (opts->size < offsetof(tbk_select_options, counter) + sizeof(int) || opts->size > 4096)
+    // the struct as it was before the GC bounds ended with `counter` (20 bytes, 24 with its padding): a caller of that size,
+    // or of any size that does not reach max_gc, states no GC bound, and what follows `counter` in its memory is not read
+    const size_t without_gc = offsetof(tbk_select_options, counter) + sizeof(int), with_gc = offsetof(tbk_select_options, max_gc) + sizeof(uint32_t);
+    if (opts->size < without_gc || opts->size > 4096)
         return cfail(TBK_ERR_INVALID, "tbk_select_options.size = %zu: set it with tbk_select_options_init", (size_t)opts->size);
-    memcpy(&o, opts, std::min<size_t>(opts->size, sizeof o));
+    memcpy(&o, opts, opts->size < with_gc ? without_gc : std::min<size_t>(opts->size, sizeof o));
     if (o.counter != TBK_SELECT_COUNTER_BASE && o.counter != TBK_SELECT_COUNTER_MIN && o.counter != TBK_SELECT_COUNTER_SUM)
         return cfail(TBK_ERR_INVALID, "%s: counter rule %d: TBK_SELECT_COUNTER_BASE, _MIN or _SUM", who, o.counter);
     if (!select_range_ok(o.min_count, o.max_count))
         return cfail(TBK_ERR_INVALID, "%s: counter range [%u, %u] of the base: need 1 <= min <= max <= 255", who, o.min_count, o.max_count);
+    if (o.min_gc > o.max_gc || o.max_gc > 32)
+        return cfail(TBK_ERR_INVALID, "%s: GC range [%u, %u] of the base, in bases: need 0 <= min <= max <= 32", who, o.min_gc, o.max_gc);
     static const char *const place[2] = {"the first partner's", "the second partner's"};
     for (int i = 0; i < n_partners; i++) {
         const tbk_select_partner &p = partners[i];
@@ -1533,7 +1548,8 @@ extern "C" int tbk_kmerdb_select(const tbk_kmerdb *base, const tbk_select_partne
         if (e == hipSuccess) e = hipMalloc((void **)&d_hist, sizeof hist);
         if (e == hipSuccess) e = hipMemset(d_hist, 0, sizeof hist);
         if (e == hipSuccess)
-            e = tbk_launch_kmerdb_select_flag(base->d_keys, base->d_counts, base->n, o.min_count, o.max_count, &ask[0], &ask[1], sel.d_flags, sel.counts(), nullptr);
+            e = tbk_launch_kmerdb_select_flag(base->d_keys, base->d_counts, base->n, o.min_count, o.max_count, o.min_gc, o.max_gc, &ask[0], &ask[1],
+                                              sel.d_flags, sel.counts(), nullptr);
         if (e == hipSuccess) e = sel.total(&total);
         const bool sane = total <= base->n;  // (nothing is allocated or written by a count that cannot be)
         const bool some = sane && total;

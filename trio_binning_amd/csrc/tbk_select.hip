@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/tbk.h"
+#include "tbk_common.h"
 #include "tbk_compact.h"
 #include "tbk_device.h"
 
@@ -19,13 +20,13 @@ __device__ __forceinline__ bool select_passes(const TbkSelectPartner &p, uint64_
 
 // ---- flag: one bit per entry of base, one count per tile -------------------------------------------------------------------
 // Two threads of wave 0 and two of wave 1 find the tile's bounds in p0 and in p1 side by side; behind the barrier of
-// compact_flag_tile every entry tests its own counter first - an entry outside the base range loads nothing of a partner -
-// then asks p0, and p1 only for what p0 left (the host puts EXCLUDE partners first: the cheaper rejection).  Equal bounds
+// compact_flag_tile every entry tests its own counter first, then the G-or-C bases of its own key (tbk_rank_gc against
+// [g_min, g_max]; 0 and 32 never bind) - an entry outside either range loads nothing of a partner - then asks p0, and p1 only for what p0 left (the host puts EXCLUDE partners first: the cheaper rejection).  Equal bounds
 // are no load at all.  32 bytes of LDS for the bounds and the tile's sum: occupancy is bounded by registers alone.
 __global__ void __launch_bounds__(256)
 tbk_kmerdb_select_flag_kernel(const uint64_t *__restrict__ base_keys, const uint8_t *__restrict__ base_counts, uint64_t n, uint32_t c_min,
-                              uint32_t c_max, TbkSelectPartner p0, TbkSelectPartner p1, uint64_t *__restrict__ flags,
-                              unsigned long long *__restrict__ tile_counts) {
+                              uint32_t c_max, uint32_t g_min, uint32_t g_max, TbkSelectPartner p0, TbkSelectPartner p1,
+                              uint64_t *__restrict__ flags, unsigned long long *__restrict__ tile_counts) {
     __shared__ uint64_t bound[4];  // p0: first, last; p1: first, last
     const uint64_t first = (uint64_t)blockIdx.x * TBK_DBT_TILE;  // (< n: one block per tile of base)
     compact_tile_bounds(base_keys, n, first, p0.keys, p0.n, bound, 0);
@@ -34,6 +35,8 @@ tbk_kmerdb_select_flag_kernel(const uint64_t *__restrict__ base_keys, const uint
         const uint32_t c = base_counts[i];
         if (c < c_min || c > c_max) return false;
         const uint64_t key = base_keys[i];
+        const uint32_t g = tbk_rank_gc(key);
+        if (g < g_min || g > g_max) return false;
         return select_passes(p0, bound[0], bound[1], key) && select_passes(p1, bound[2], bound[3], key);
     });
 }
@@ -85,9 +88,10 @@ tbk_kmerdb_select_scatter_kernel(const uint64_t *__restrict__ base_keys, const u
 // launchers (called from tbk_count.cpp)
 // =======================================================================================
 extern "C" hipError_t tbk_launch_kmerdb_select_flag(const uint64_t *base_keys, const uint8_t *base_counts, uint64_t n, uint32_t c_min, uint32_t c_max,
-                                                    const TbkSelectPartner *p0, const TbkSelectPartner *p1, uint64_t *d_flags,
-                                                    unsigned long long *d_tile_counts, hipStream_t stream) {
-    return compact_launch_tiles(n, stream, tbk_kmerdb_select_flag_kernel, base_keys, base_counts, n, c_min, c_max, *p0, *p1, d_flags, d_tile_counts);
+                                                    uint32_t g_min, uint32_t g_max, const TbkSelectPartner *p0, const TbkSelectPartner *p1,
+                                                    uint64_t *d_flags, unsigned long long *d_tile_counts, hipStream_t stream) {
+    return compact_launch_tiles(n, stream, tbk_kmerdb_select_flag_kernel, base_keys, base_counts, n, c_min, c_max, g_min, g_max, *p0, *p1, d_flags,
+                                d_tile_counts);
 }
 
 extern "C" hipError_t tbk_launch_kmerdb_select_scatter(int rule, const uint64_t *base_keys, const uint8_t *base_counts, uint64_t n,

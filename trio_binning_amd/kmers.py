@@ -1209,13 +1209,25 @@ class KmerDatabase:
         check(lib.tbk_kmerdb_origin_spectrum(self._h, y._h, bounds[0], bounds[1], z._h, bounds[2], bounds[3], spec.ctypes.data))
         return spec
 
-    def select(self, min_count: int = 1, max_count: int = 255, require=(), exclude=(), counter: str = "base") -> "KmerDatabase":
+    def gc_spectrum(self) -> np.ndarray:
+        """This database's entries by GC content and by counter (``tbk_kmerdb_gc_spectrum``), shape (k + 1, 256), uint64: cell
+        ``[g, c]`` is the number of k-mers with ``g`` G-or-C bases and counter ``c`` - k-mer multiplicity against GC, the matrix
+        ``kat gcp`` plots.  Column 0 is 0, column ``c >= 1`` sums to ``histogram()[c]`` from the floor on, and the whole matrix
+        to ``len(self)``.  Either floor, either space; an empty database gives zeros."""
+        spec = np.zeros((33, 256), dtype=np.uint64)
+        check(lib.tbk_kmerdb_gc_spectrum(self._h, spec.ctypes.data))
+        return spec[:self.k + 1].copy()
+
+    def select(self, min_count: int = 1, max_count: int = 255, require=(), exclude=(), counter: str = "base",
+               gc: Optional[Tuple[Optional[int], Optional[int]]] = None) -> "KmerDatabase":
         """A selection of this database's entries that is a database again (``tbk_kmerdb_select``): those with a counter in
         [min_count, max_count] that every partner of ``require`` holds with a counter in that partner's range and no partner
         of ``exclude`` does.  A partner is ``(KmerDatabase, min, max)`` or a bare ``KmerDatabase``, which means
         ``(db, 1, 255)``; ranges are taken literally, 1 <= min <= max <= 255; at most two partners in all (chain calls for
         more).  ``counter``: "base" keeps this database's counters, "min" takes the minimum with the ``require`` partners',
-        "sum" adds them, capped at 255.  The result is a full database (``floor == 1``) in this database's order, of its k and
+        "sum" adds them, capped at 255.  ``gc``: ``(lo, hi)`` keeps only the k-mers with lo..hi G-or-C bases (bases, not per
+        cent; 0 <= lo <= hi <= 32, a bound above k never binds, and either may be None for "no bound"); the default is no
+        bound.  The result is a full database (``floor == 1``) in this database's order, of its k and
         space, with ``reads_added == bases_added == 0``; it may be empty.  ``ValueError`` for a range, rule or number of
         partners outside that, or databases of different k, device or space."""
         if counter not in _lib.SELECT_COUNTERS:
@@ -1233,6 +1245,11 @@ class KmerDatabase:
         o = _lib.SelectOptions()
         lib.tbk_select_options_init(C.byref(o))
         o.min_count, o.max_count, o.counter = bounds[0], bounds[1], _lib.SELECT_COUNTERS[counter]
+        if gc is not None:
+            lo, hi = (0 if gc[0] is None else int(gc[0])), (32 if gc[1] is None else int(gc[1]))
+            if not (0 <= lo <= 0xFFFFFFFF and 0 <= hi <= 0xFFFFFFFF):
+                raise ValueError("GC range {}: need 0 <= min <= max <= 32".format((lo, hi)))
+            o.min_gc, o.max_gc = lo, hi
         partners = (_lib.SelectPartner * max(1, len(asked)))()
         for slot, (db, lo, hi, mode) in zip(partners, asked):
             slot.db, slot.min_count, slot.max_count, slot.mode = (db._h.value if db._h is not None else None), lo, hi, mode

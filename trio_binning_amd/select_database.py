@@ -1,6 +1,6 @@
 """Select from k-mer count databases into a database.
 
-    python -m trio_binning_amd.select_database -o out.tbkdb [--min-count N] [--max-count N] \\
+    python -m trio_binning_amd.select_database -o out.tbkdb [--min-count N] [--max-count N] [--min-gc N] [--max-gc N] \\
         [--require DB[:MIN[:MAX]]]... [--exclude DB[:MIN[:MAX]]]... [--counter base|min|sum] base.tbkdb
 
 The k-mers of base.tbkdb with a counter in [--min-count, --max-count] (default 1..255) that every --require database holds with
@@ -10,7 +10,8 @@ hap-mer database (the ``hapmers`` command does that for a trio).  All ranges are
 full database (kept with --keep-singletons) with MIN 2 to ignore its k-mers seen once.  At most two partners in all; chain runs
 for more.  --counter: the counters written are base's ("base", the default), the minimum of base's and the --require
 databases' ("min"), or their sum capped at 255 ("sum").  The files are loaded as they are, full ones included, and may be of
-either space as long as all are of one.
+either space as long as all are of one.  --min-gc and --max-gc keep only the k-mers with that many G-or-C bases (integers in
+0..k, counted in bases, not per cent; either may be given alone): a cloud of the ``gc_spectrum`` matrix carved out as a database.
 
 The result is a FULL database (its header states exactly the k-mers and counters it holds; reads and bases are 0): it merges
 exactly with merge_databases, dumps with dump_database and scores with assembly_qv.  An empty selection is written too.
@@ -57,6 +58,8 @@ def parse_args(argv=None):
     parser.add_argument("-o", "--output", required=True, metavar="out.tbkdb", help="the database to write")
     parser.add_argument("--min-count", type=int, default=1, metavar="N", help="lowest counter of base.tbkdb that is kept (default 1)")
     parser.add_argument("--max-count", type=int, default=255, metavar="N", help="highest counter of base.tbkdb that is kept (default 255)")
+    parser.add_argument("--min-gc", type=int, default=None, metavar="N", help="fewest G-or-C bases of a k-mer that is kept (0..k; default: no bound)")
+    parser.add_argument("--max-gc", type=int, default=None, metavar="N", help="most G-or-C bases of a k-mer that is kept (0..k; default: no bound)")
     parser.add_argument("--require", action="append", default=[], type=partner_spec, metavar="DB[:MIN[:MAX]]",
                         help="keep only k-mers this database holds with a counter in MIN..MAX (default 1..255)")
     parser.add_argument("--exclude", action="append", default=[], type=partner_spec, metavar="DB[:MIN[:MAX]]",
@@ -75,6 +78,11 @@ def parse_args(argv=None):
     for path, lo, hi, mode in args.partners:
         if not 1 <= lo <= hi <= 255:
             parser.error("--{} {}: counter range {}..{}: need 1 <= MIN <= MAX <= 255".format(mode, path, lo, hi))
+    for name, value in (("--min-gc", args.min_gc), ("--max-gc", args.max_gc)):
+        if value is not None and not 0 <= value <= 32:
+            parser.error("{} {}: a number of G-or-C bases, 0..k".format(name, value))
+    if args.min_gc is not None and args.max_gc is not None and args.min_gc > args.max_gc:
+        parser.error("--min-gc {} --max-gc {}: need min <= max".format(args.min_gc, args.max_gc))
     inputs = [args.base] + [p[0] for p in args.partners]
     for path in inputs:
         if _same_file(args.output, path):
@@ -95,7 +103,18 @@ def parse_args(argv=None):
                 PROG, path, SPACES[info["compressed"]], args.base, SPACES[first["compressed"]]))
         infos.append(info)
     args.info = infos[0]
+    for name, value in (("--min-gc", args.min_gc), ("--max-gc", args.max_gc)):
+        if value is not None and value > args.info["k"]:
+            parser.error("{} {}: {} holds {}-mers: a number of G-or-C bases, 0..{}".format(name, value, args.base, args.info["k"], args.info["k"]))
+    args.gc = None if args.min_gc is None and args.max_gc is None else (args.min_gc, args.max_gc)
     return args
+
+
+def gc_words(gc, k: int) -> str:
+    """what the stderr line says of a GC range: nothing when none was given"""
+    if gc is None:
+        return ""
+    return " with {}..{} G-or-C bases".format(0 if gc[0] is None else gc[0], k if gc[1] is None else gc[1])
 
 
 def main(argv=None):
@@ -112,16 +131,18 @@ def main(argv=None):
         groups = {"require": [], "exclude": []}
         for path, lo, hi, mode in args.partners:
             groups[mode].append((database(path), lo, hi))
-        with base.select(args.min_count, args.max_count, require=groups["require"], exclude=groups["exclude"], counter=args.counter) as picked:
+        with base.select(args.min_count, args.max_count, require=groups["require"], exclude=groups["exclude"], counter=args.counter,
+                         gc=args.gc) as picked:
             picked.save(args.output)
             kept, of = len(picked), len(base)
     finally:
         for db in loaded.values():
             db.close()
+    gc = gc_words(args.gc, args.info["k"])
     if kept:
-        print("{}: {} of the {} k-mers of {} kept and written to {}".format(PROG, kept, of, args.base, args.output), file=sys.stderr)
+        print("{}: {} of the {} k-mers of {} kept{} and written to {}".format(PROG, kept, of, args.base, gc, args.output), file=sys.stderr)
     else:
-        print("{}: none of the {} k-mers of {} kept: {} is an empty database".format(PROG, of, args.base, args.output), file=sys.stderr)
+        print("{}: none of the {} k-mers of {} kept{}: {} is an empty database".format(PROG, of, args.base, gc, args.output), file=sys.stderr)
 
 
 if __name__ == "__main__":
