@@ -1376,6 +1376,39 @@ typedef struct tbk_repair { uint64_t read, first, pos; uint32_t windows; uint16_
 int tbk_kmerdb_query_repairs(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
                              uint32_t min_count, uint32_t min_support, tbk_repair **repairs, uint64_t *n_repairs);
 
+/* ---- read evidence: how many of a read's k-mers does the database hold, and how much of it do they cover? ---------- */
+/* A pass over reads that carries a database's k-mers back to them: per sequence, the windows the database holds with a
+ * counter in a range, and the bases those windows cover.  q is a session with or without copies, k its database's k,
+ * min_count in 1..255 and max_count in min_count..255.  The lower bound is m = max(floor, min_count), floor 2 for a solid
+ * database and 1 for a full one, as the repair candidates have it.
+ * WINDOWS.  A sequence of length L has nw = max(L - k + 1, 0) window starts.  Clean windows (ACGT only, either case),
+ * canonical k-mers and the counter c are exactly those of tbk_kmerdb_query_add; c is 0 when the k-mer is absent.  A window
+ * is HELD when it is clean and m <= c <= max_count.
+ * COVERAGE.  A base position p in [0, L) is COVERED when some held window w has w <= p <= w + k - 1.  A held window starts
+ * at L - k at most, so the last position any window covers is L - 1: coverage never reaches past a sequence's end, and
+ * nothing joins across sequences.  (The evidence kernel relies on this: it dilates the held bits by k - 1 positions upward
+ * and neither masks the result nor looks at the position behind the sequence.)
+ * PER SEQUENCE:
+ *   clean      clean windows;
+ *   held       held windows;
+ *   covered    covered positions;
+ *   longest    the length of the longest run of consecutive covered positions, 0 when there is none;
+ *   stretches  the number of maximal runs of consecutive covered positions.
+ * A sequence shorter than k, or an empty one, gets five zeros.
+ * out is host memory, one record per sequence in the batch's order.  TBK_ERR_INVALID, with a message, for min_count outside
+ * 1..255 and for max_count outside min_count..255, before anything runs: nothing is written then and the session stays
+ * usable.  A range that is empty after the floor - (1, 1) on a solid database - is valid and holds nothing.  n_reads == 0 is
+ * valid and writes nothing.  An empty database is valid: no window is held.
+ * The call only reads the session: the histogram, the seen bits, the copies and the window total are as they were, and
+ * the batch does not count towards the limit of 2^32 - 1 window starts.
+ * The call uses the session's batch buffers and grows them as needed.  On the device it takes, per base of the batch
+ * (rounded up to passes of 2048 stream positions, one position more per sequence): the bases and their separated copy
+ * (2 bytes) and the clean and the held bitmap (2 bits) - 2.25 bytes, all of which tbk_kmerdb_query_add's own buffers
+ * already hold - and 8 bytes per sequence for the offsets and 40 for its record beside them.  No byte per base comes home. */
+typedef struct tbk_read_evidence { uint64_t clean, held, covered, longest, stretches; } tbk_read_evidence; /* 40 bytes */
+int tbk_kmerdb_query_evidence(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
+                              uint32_t min_count, uint32_t max_count, tbk_read_evidence *out /* n_reads */);
+
 /* Host threads the library starts for its own host-side work (list parsing, gzip members,
  * scoring): hardware threads limited by the CPU affinity mask and the cgroup CPU quota, divided by the
  * number of ranks the launcher started on this node (LOCAL_WORLD_SIZE, or TBK_LOCAL_RANKS): one process per GPU

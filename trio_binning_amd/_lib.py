@@ -311,6 +311,10 @@ HAS_DB_REPAIRS = hasattr(lib, "tbk_kmerdb_query_repairs")  # (variant builds may
 if HAS_DB_REPAIRS:
     _sig("tbk_kmerdb_query_repairs", C.c_int, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, C.POINTER(_vp), _u64p)
     _sig("tbk_kmerdb_query_repair_times_", C.c_int, _vp, _vp)  # (measuring hook: the last call's two host-clock times, ms)
+HAS_DB_EVIDENCE = hasattr(lib, "tbk_kmerdb_query_evidence")  # (variant builds may predate the read evidence)
+if HAS_DB_EVIDENCE:
+    _sig("tbk_kmerdb_query_evidence", C.c_int, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, _vp)
+    _sig("tbk_kmerdb_query_evidence_times_", C.c_int, _vp, _vp)  # (measuring hook: the last call's two kernel times, ms)
 
 class DumpOptions(C.Structure):
     """tbk_dump_options (include/tbk.h)."""

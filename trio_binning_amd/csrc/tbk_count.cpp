@@ -1722,6 +1722,11 @@ extern "C" hipError_t tbk_launch_repair_stretches(const uint32_t *, uint64_t, co
                                                   tbk_repair *, uint64_t, hipStream_t);
 extern "C" hipError_t tbk_launch_repair(const uint8_t *, const uint64_t *, int, const uint64_t *, const uint8_t *, const uint32_t *, uint64_t, int, uint32_t,
                                         uint32_t, tbk_repair *, uint64_t, uint64_t, hipStream_t);
+// (the read evidence's two kernels: tbk_screen.hip)
+extern "C" hipError_t tbk_launch_screen_lookup(const uint8_t *, uint64_t, uint64_t, int, const uint64_t *, const uint8_t *, const uint32_t *, uint64_t, int,
+                                               uint32_t, uint32_t, uint32_t *, uint32_t *, uint64_t, hipStream_t);
+extern "C" hipError_t tbk_launch_screen_evidence(const uint32_t *, const uint32_t *, const uint64_t *, uint64_t, int, tbk_read_evidence *, uint64_t,
+                                                 hipStream_t);
 
 constexpr uint64_t TBK_QUERY_MAX_WINDOWS = 0xFFFFFFFFull;  // window starts of a session: a 32-bit copy counter cannot wrap
 constexpr int TBK_QUERY_MAX_PREFIX_BITS = 28;              // a directory of at most 1 GiB + 4 bytes
@@ -1746,6 +1751,9 @@ struct tbk_kmerdb_query {
     QueryBuf copy_bytes, saturated_bits, collapsed_bits, expanded_bits, bin_prefix, bins;  // (the copy-number track's own)
     QueryBuf repairs;                                                                      // (the repair candidates' records)
     double repair_ms[2] = {0, 0};  // (tbk_kmerdb_query_repair_times_)
+    QueryBuf evidence;                                                                     // (the read evidence's records)
+    hipEvent_t evidence_marks[3] = {nullptr, nullptr, nullptr};  // around the evidence's two kernels, made by its first call
+    double evidence_ms[2] = {0, 0};                              // (tbk_kmerdb_query_evidence_times_)
     size_t seen_bytes() const { return (size_t)((db->n + 31) / 32 + 1) * 4; }
 };
 
@@ -1777,8 +1785,10 @@ extern "C" void tbk_kmerdb_query_destroy(tbk_kmerdb_query *q) {
         for (void *p : {(void *)q->d_dir, (void *)q->d_seen, (void *)q->d_copies, (void *)q->d_sums, q->d_pad})
             if (p) (void)hipFree(p);
         for (QueryBuf *b : {&q->bases, &q->offsets, &q->sep, &q->clean_bits, &q->found_bits, &q->bytes, &q->totals, &q->counts, &q->copy_bytes,
-                            &q->saturated_bits, &q->collapsed_bits, &q->expanded_bits, &q->bin_prefix, &q->bins, &q->repairs})
+                            &q->saturated_bits, &q->collapsed_bits, &q->expanded_bits, &q->bin_prefix, &q->bins, &q->repairs, &q->evidence})
             if (b->p) (void)hipFree(b->p);
+        for (hipEvent_t mark : q->evidence_marks)
+            if (mark) (void)hipEventDestroy(mark);
     }
     delete q;
 }
@@ -2064,5 +2074,66 @@ extern "C" int tbk_kmerdb_query_repair_times_(tbk_kmerdb_query *q, double ms[2])
     if (!q || !ms) return cfail(TBK_ERR_INVALID, "NULL argument");
     ms[0] = q->repair_ms[0];
     ms[1] = q->repair_ms[1];
+    return TBK_OK;
+}
+
+// The read evidence (include/tbk.h has the rule; kernels: tbk_screen.hip): the batch is separated and looked up again
+// without a write to the session, and the two bitmaps are reduced to one record per sequence.  The bitmaps reuse the buffers
+// of tbk_kmerdb_query_add; the records are the call's own and stay with the session.
+extern "C" int tbk_kmerdb_query_evidence(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t min_count,
+                                         uint32_t max_count, tbk_read_evidence *out) {
+    if (!q) return cfail(TBK_ERR_INVALID, "tbk_kmerdb_query_evidence: query is NULL");
+    if (min_count < 1 || min_count > 255) return cfail(TBK_ERR_INVALID, "evidence: min_count %u: need 1 <= min_count <= 255", min_count);
+    if (max_count < min_count || max_count > 255)
+        return cfail(TBK_ERR_INVALID, "evidence: max_count %u: need min_count (%u) <= max_count <= 255", max_count, min_count);
+    if (!n_reads) return TBK_OK;
+    if (!out) return cfail(TBK_ERR_INVALID, "tbk_kmerdb_query_evidence: out is NULL");
+    int rc = tbk_check_offsets_(offsets, n_reads);
+    if (rc) return rc;
+    const uint64_t total = offsets[n_reads];
+    if (total && !bases) return cfail(TBK_ERR_INVALID, "bases is NULL");
+    memset(out, 0, n_reads * sizeof(tbk_read_evidence));
+    uint64_t windows = 0;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t len = offsets[r + 1] - offsets[r];
+        if (len >= (uint64_t)q->k) windows += len - (uint64_t)q->k + 1;
+    }
+    if (!windows) return TBK_OK;
+    if ((rc = kmerdb_device(q->device))) return rc;
+    const uint64_t sep_total = total + n_reads;  // one 'N' behind every read
+    const uint64_t passes = tbk_probe_passes(sep_total);
+    if ((rc = query_reserve(q->bases, total + 16)) || (rc = query_reserve(q->offsets, (n_reads + 1) * 8)) || (rc = query_reserve(q->sep, sep_total + 16)) ||
+        (rc = query_reserve(q->clean_bits, passes * 64 * 4)) || (rc = query_reserve(q->found_bits, passes * 64 * 4)) ||
+        (rc = query_reserve(q->evidence, n_reads * sizeof(tbk_read_evidence))))
+        return rc;
+    for (hipEvent_t &mark : q->evidence_marks)
+        if (!mark) CHIP(hipEventCreate(&mark));
+    const tbk_kmerdb *db = q->db;
+    CHIP(hipMemcpyAsync(q->bases.p, bases, total, hipMemcpyHostToDevice, nullptr));
+    CHIP(hipMemcpyAsync(q->offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, nullptr));
+    CHIP(tbk_launch_separate(q->bases.as<uint8_t>(), q->offsets.as<uint64_t>(), n_reads, q->sep.as<uint8_t>(), nullptr));
+    CHIP(hipEventRecord(q->evidence_marks[0], nullptr));
+    CHIP(tbk_launch_screen_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, db->n ? db->d_keys : (const uint64_t *)q->d_pad,
+                                  db->n ? db->d_counts : (const uint8_t *)q->d_pad, q->d_dir, db->n, q->prefix_bits, std::max<uint32_t>(db->floor, min_count),
+                                  max_count, q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(), q->wave_slots, nullptr));
+    CHIP(hipEventRecord(q->evidence_marks[1], nullptr));
+    CHIP(tbk_launch_screen_evidence(q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(), q->offsets.as<uint64_t>(), n_reads, q->k,
+                                    q->evidence.as<tbk_read_evidence>(), q->wave_slots, nullptr));
+    CHIP(hipEventRecord(q->evidence_marks[2], nullptr));
+    CHIP(hipMemcpy(out, q->evidence.p, n_reads * sizeof(tbk_read_evidence), hipMemcpyDeviceToHost));
+    float ms[2] = {0, 0};
+    CHIP(hipEventElapsedTime(&ms[0], q->evidence_marks[0], q->evidence_marks[1]));
+    CHIP(hipEventElapsedTime(&ms[1], q->evidence_marks[1], q->evidence_marks[2]));
+    q->evidence_ms[0] = ms[0];
+    q->evidence_ms[1] = ms[1];
+    return TBK_OK;
+}
+
+// (measuring hook, not in tbk.h: the device's clock over the two kernels of the last call that had a window - the lookup pass,
+// then the evidence kernel; tools/measure_screen.py)
+extern "C" int tbk_kmerdb_query_evidence_times_(tbk_kmerdb_query *q, double ms[2]) {
+    if (!q || !ms) return cfail(TBK_ERR_INVALID, "NULL argument");
+    ms[0] = q->evidence_ms[0];
+    ms[1] = q->evidence_ms[1];
     return TBK_OK;
 }

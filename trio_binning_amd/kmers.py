@@ -1412,6 +1412,10 @@ REPAIR = np.dtype([("read", "<u8"), ("first", "<u8"), ("pos", "<u8"), ("windows"
 assert REPAIR.itemsize == 40
 REPAIR_NONE, REPAIR_SUB, REPAIR_DEL, REPAIR_INS, REPAIR_LONG = range(5)
 
+# one sequence's k-mer evidence (``tbk_read_evidence``, 40 bytes)
+READ_EVIDENCE = np.dtype([("clean", "<u8"), ("held", "<u8"), ("covered", "<u8"), ("longest", "<u8"), ("stretches", "<u8")])
+assert READ_EVIDENCE.itemsize == 40
+
 
 class DatabaseQuery:
     """How often did the reads see the k-mers of these sequences?  (``tbk_kmerdb_query``, include/tbk.h.)
@@ -1515,6 +1519,24 @@ class DatabaseQuery:
                 C.memmove(records.ctypes.data, ptr, count.value * REPAIR.itemsize)
         finally:
             lib.tbk_host_free(ptr)
+        return records
+
+    def evidence(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 1, max_count: int = 255) -> np.ndarray:
+        """The k-mer evidence of a batch of reads (``tbk_kmerdb_query_evidence``, include/tbk.h): one ``READ_EVIDENCE`` record per
+        sequence.  ``clean`` counts its clean windows and ``held`` those of them whose counter lies in
+        ``[max(floor, min_count), max_count]``; ``covered`` counts the bases that lie in a held window, ``stretches`` the maximal
+        runs of such bases and ``longest`` the longest of them.  A sequence shorter than k gets five zeros.  The session is only
+        read.  ``ValueError`` for a ``min_count`` outside 1..255 or a ``max_count`` outside ``min_count``..255."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.size - 1, 0)
+        min_count, max_count = int(min_count), int(max_count)
+        if not 0 <= min_count < 1 << 32 or not 0 <= max_count < 1 << 32:
+            # the library's own refusal and message, for the values a C uint32_t can carry
+            check(lib.tbk_kmerdb_query_evidence(self._h, None, None, 0, min(max(min_count, 0), 0xFFFFFFFF), min(max(max_count, 0), 0xFFFFFFFF), None))
+            raise ValueError("evidence: min_count {} must lie in 1 .. 255 and max_count {} in min_count .. 255".format(min_count, max_count))
+        records = np.zeros(n, dtype=READ_EVIDENCE)
+        check(lib.tbk_kmerdb_query_evidence(self._h, bases.ctypes.data, offsets.ctypes.data, n, min_count, max_count, records.ctypes.data))
         return records
 
     def reset(self) -> None:
