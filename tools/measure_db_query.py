@@ -14,7 +14,7 @@ timed) before each call; each leg is warmed up once and the median of --runs run
   add_copies   add() of a session made with copies (a 32-bit atomic add per found window more)
 
 --no-directory-library names a variant of the library whose lookup bisects the whole database for every window
-(VARIANT_SRC=tbk_query tools/build_variant.sh query_nodir -DTBK_QUERY_NO_DIRECTORY): the `add` leg is repeated with it
+(VARIANT_SRC=tbk_query tools/build_variant.sh query_nodir -DTBK_LOOKUP_NO_DIRECTORY): the `add` leg is repeated with it
 in a fresh process, after this one's database is closed, and joins the record as "no_directory".  One JSON line on
 stdout; --out writes it to a file too.
 

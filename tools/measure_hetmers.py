@@ -2,7 +2,7 @@
 tools/measure_db_handoff.py --inherited (tools/measure_select.py's construction), and the query session's lookup beside it.
 
     python tools/measure_hetmers.py [--n 100000000] [-k 21] [--runs 7] [--tmp /dev/shm] [--out-dir profiles/r21]
-    python tools/measure_hetmers.py --name measure_hetmers_nodir.json   # under TBK_LIBRARY: the variant -DTBK_HETMER_NO_DIRECTORY
+    python tools/measure_hetmers.py --name measure_hetmers_nodir.json   # under TBK_LIBRARY: the variant -DTBK_LOOKUP_NO_DIRECTORY
     python tools/measure_hetmers.py --render-only [--regs FILE] [--bench-parent FILE... --bench-change FILE...]
 
 Three databases of about --n k-mers: A (ascending random ranks made canonical - a database of anything else has no class

@@ -30,6 +30,7 @@
 #include "../../include/tbk.h"
 #include "tbk_common.h"
 #include "tbk_compact_host.h"
+#include "tbk_lookup_host.h"
 
 extern "C" void tbk_set_error_(int code, const char *msg);
 extern "C" hipError_t tbk_launch_separate(const uint8_t *, const uint64_t *, uint64_t, uint8_t *, hipStream_t);
@@ -1700,34 +1701,7 @@ extern "C" int tbk_kmerdb_hetmers(const tbk_kmerdb *db, const tbk_hetmer_options
 // Database query (tbk_kmerdb_query; kernels: tbk_query.hip): the counter the database holds for every window of a
 // batch of sequences - per-sequence totals, a histogram, the entries seen, their copies.  include/tbk.h has the rules.
 // =====================================================================================================================
-// (tbk_launch_query_directory: tbk_compact_host.h, shared with the het-mer call)
-extern "C" hipError_t tbk_launch_query_lookup(const uint8_t *, uint64_t, uint64_t, int, const uint64_t *, const uint8_t *, const uint32_t *, uint64_t, int,
-                                              uint32_t, uint32_t *, uint32_t *, uint8_t *, unsigned long long *, uint32_t *, uint32_t *, uint64_t,
-                                              hipStream_t);
-extern "C" hipError_t tbk_launch_query_totals(const uint32_t *, const uint32_t *, const uint64_t *, uint64_t, unsigned long long *, uint64_t, hipStream_t);
-extern "C" hipError_t tbk_launch_query_counts(const uint8_t *, const uint64_t *, uint64_t, uint8_t *, uint64_t, hipStream_t);
-extern "C" hipError_t tbk_launch_query_completeness(const uint8_t *, const uint32_t *, uint64_t, uint32_t, uint32_t, unsigned long long *, hipStream_t);
-extern "C" hipError_t tbk_launch_query_spectrum(const uint8_t *, const uint32_t *, uint64_t, unsigned long long *, hipStream_t);
-// (the copy-number track's two kernels: tbk_depth.hip)
-extern "C" hipError_t tbk_launch_depth_lookup(const uint8_t *, uint64_t, uint64_t, int, const uint64_t *, const uint8_t *, const uint32_t *, const uint32_t *,
-                                              uint64_t, int, uint32_t, uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint8_t *, uint8_t *, uint64_t,
-                                              hipStream_t);
-extern "C" hipError_t tbk_launch_depth_bins(uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint8_t *, uint8_t *, const uint64_t *, const uint64_t *,
-                                            uint64_t, uint64_t, int, uint32_t, tbk_depth_bin *, uint64_t, hipStream_t);
-// (the repair candidates' four kernels: tbk_repair.hip)
-extern "C" hipError_t tbk_launch_repair_lookup(const uint8_t *, uint64_t, uint64_t, int, const uint64_t *, const uint8_t *, const uint32_t *, uint64_t, int,
-                                               uint32_t, uint32_t *, uint32_t *, uint64_t, hipStream_t);
-extern "C" hipError_t tbk_launch_repair_heads(const uint32_t *, uint64_t, uint64_t *, unsigned long long *, hipStream_t);
-extern "C" hipError_t tbk_launch_repair_stretches(const uint32_t *, uint64_t, const uint64_t *, uint64_t, const uint64_t *, const unsigned long long *,
-                                                  tbk_repair *, uint64_t, hipStream_t);
-extern "C" hipError_t tbk_launch_repair(const uint8_t *, const uint64_t *, int, const uint64_t *, const uint8_t *, const uint32_t *, uint64_t, int, uint32_t,
-                                        uint32_t, tbk_repair *, uint64_t, uint64_t, hipStream_t);
-// (the read evidence's two kernels: tbk_screen.hip)
-extern "C" hipError_t tbk_launch_screen_lookup(const uint8_t *, uint64_t, uint64_t, int, const uint64_t *, const uint8_t *, const uint32_t *, uint64_t, int,
-                                               uint32_t, uint32_t, uint32_t *, uint32_t *, uint64_t, hipStream_t);
-extern "C" hipError_t tbk_launch_screen_evidence(const uint32_t *, const uint32_t *, const uint64_t *, uint64_t, int, tbk_read_evidence *, uint64_t,
-                                                 hipStream_t);
-
+// (the launchers of its kernel files - tbk_query.hip, tbk_depth.hip, tbk_repair.hip, tbk_screen.hip: tbk_lookup_host.h)
 constexpr uint64_t TBK_QUERY_MAX_WINDOWS = 0xFFFFFFFFull;  // window starts of a session: a 32-bit copy counter cannot wrap
 constexpr int TBK_QUERY_MAX_PREFIX_BITS = 28;              // a directory of at most 1 GiB + 4 bytes
 
@@ -1755,6 +1729,10 @@ struct tbk_kmerdb_query {
     hipEvent_t evidence_marks[3] = {nullptr, nullptr, nullptr};  // around the evidence's two kernels, made by its first call
     double evidence_ms[2] = {0, 0};                              // (tbk_kmerdb_query_evidence_times_)
     size_t seen_bytes() const { return (size_t)((db->n + 31) / 32 + 1) * 4; }
+    // what the kernels search; an empty database's arrays are the one entry of padding
+    TbkDbView view() const {
+        return TbkDbView{db->n ? db->d_keys : (const uint64_t *)d_pad, db->n ? db->d_counts : (const uint8_t *)d_pad, d_dir, (uint32_t)db->n, prefix_bits};
+    }
 };
 
 static int query_reserve(QueryBuf &b, size_t need) {
@@ -1857,6 +1835,34 @@ extern "C" int tbk_kmerdb_query_set_wave_slots_(tbk_kmerdb_query *q, uint64_t wa
     return TBK_OK;
 }
 
+// the window starts of a batch: every sequence of k bases or more has len - k + 1
+static uint64_t query_count_windows(const uint64_t *offsets, uint64_t n_reads, int k) {
+    uint64_t windows = 0;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t len = offsets[r + 1] - offsets[r];
+        if (len >= (uint64_t)k) windows += len - (uint64_t)k + 1;
+    }
+    return windows;
+}
+
+// What the four calls that look a batch up begin with, on the session's device: the buffers of the batch, of its separated
+// stream (one 'N' behind every read: sep_total bytes, `passes` wave passes) and of the two bitmaps every lookup kernel
+// leaves, 64 words per pass each; the batch copied in and separated.  All of it in the stream when this returns.
+static int query_stage_batch(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint64_t *sep_total_out,
+                             uint64_t *passes_out) {
+    const uint64_t total = offsets[n_reads], sep_total = total + n_reads, passes = tbk_probe_passes(sep_total);
+    int rc;
+    if ((rc = query_reserve(q->bases, total + 16)) || (rc = query_reserve(q->offsets, (n_reads + 1) * 8)) || (rc = query_reserve(q->sep, sep_total + 16)) ||
+        (rc = query_reserve(q->clean_bits, passes * 64 * 4)) || (rc = query_reserve(q->found_bits, passes * 64 * 4)))
+        return rc;
+    CHIP(hipMemcpyAsync(q->bases.p, bases, total, hipMemcpyHostToDevice, nullptr));
+    CHIP(hipMemcpyAsync(q->offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, nullptr));
+    CHIP(tbk_launch_separate(q->bases.as<uint8_t>(), q->offsets.as<uint64_t>(), n_reads, q->sep.as<uint8_t>(), nullptr));
+    *sep_total_out = sep_total;
+    *passes_out = passes;
+    return TBK_OK;
+}
+
 extern "C" int tbk_kmerdb_query_add(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t min_count,
                                     uint64_t *per_read, uint8_t *counts) {
     if (!q) return cfail(TBK_ERR_INVALID, "query is NULL");
@@ -1865,11 +1871,7 @@ extern "C" int tbk_kmerdb_query_add(tbk_kmerdb_query *q, const uint8_t *bases, c
     if (rc) return rc;
     const uint64_t total = offsets[n_reads];
     if (total && !bases) return cfail(TBK_ERR_INVALID, "bases is NULL");
-    uint64_t windows = 0;
-    for (uint64_t r = 0; r < n_reads; r++) {
-        const uint64_t len = offsets[r + 1] - offsets[r];
-        if (len >= (uint64_t)q->k) windows += len - (uint64_t)q->k + 1;
-    }
+    const uint64_t windows = query_count_windows(offsets, n_reads, q->k);
     if (windows > TBK_QUERY_MAX_WINDOWS || q->windows > TBK_QUERY_MAX_WINDOWS - windows)
         return cfail(TBK_ERR_INVALID, "a query session takes at most 2^32 - 1 window starts: %llu so far, %llu in this batch (reset the session, or make another)",
                      (unsigned long long)q->windows, (unsigned long long)windows);
@@ -1877,19 +1879,10 @@ extern "C" int tbk_kmerdb_query_add(tbk_kmerdb_query *q, const uint8_t *bases, c
     if (counts && total) memset(counts, 0, total);
     if (!windows) return TBK_OK;
     if ((rc = kmerdb_device(q->device))) return rc;
-    const uint64_t sep_total = total + n_reads;  // one 'N' behind every read
-    const uint64_t passes = tbk_probe_passes(sep_total);
-    if ((rc = query_reserve(q->bases, total + 16)) || (rc = query_reserve(q->offsets, (n_reads + 1) * 8)) || (rc = query_reserve(q->sep, sep_total + 16)) ||
-        (rc = query_reserve(q->clean_bits, passes * 64 * 4)) || (rc = query_reserve(q->found_bits, passes * 64 * 4)) ||
-        (rc = query_reserve(q->totals, n_reads * 2 * 8)))
-        return rc;
+    uint64_t sep_total, passes;
+    if ((rc = query_stage_batch(q, bases, offsets, n_reads, &sep_total, &passes)) || (rc = query_reserve(q->totals, n_reads * 2 * 8))) return rc;
     if (counts && ((rc = query_reserve(q->bytes, passes * 2048)) || (rc = query_reserve(q->counts, total)))) return rc;
-    CHIP(hipMemcpyAsync(q->bases.p, bases, total, hipMemcpyHostToDevice, nullptr));
-    CHIP(hipMemcpyAsync(q->offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, nullptr));
-    CHIP(tbk_launch_separate(q->bases.as<uint8_t>(), q->offsets.as<uint64_t>(), n_reads, q->sep.as<uint8_t>(), nullptr));
-    const tbk_kmerdb *db = q->db;
-    CHIP(tbk_launch_query_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, db->n ? db->d_keys : (const uint64_t *)q->d_pad,
-                                 db->n ? db->d_counts : (const uint8_t *)q->d_pad, q->d_dir, db->n, q->prefix_bits, std::max<uint32_t>(db->floor, min_count),
+    CHIP(tbk_launch_query_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, q->view(), std::max<uint32_t>(q->db->floor, min_count),
                                  q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(), counts ? q->bytes.as<uint8_t>() : nullptr, q->d_sums, q->d_seen,
                                  q->with_copies ? q->d_copies : nullptr, q->wave_slots, nullptr));
     q->windows += windows;  // (the launch is in the stream: what follows can only fail to bring the answers home)
@@ -1963,26 +1956,17 @@ extern "C" int tbk_kmerdb_query_track(tbk_kmerdb_query *q, const uint8_t *bases,
                      (unsigned long long)prefix[n_reads], (unsigned long long)n_bins);
     if (!n_bins) return TBK_OK;
     if (!bins) return cfail(TBK_ERR_INVALID, "bins is NULL");
-    const uint64_t total = offsets[n_reads];
     if (!bases) return cfail(TBK_ERR_INVALID, "bases is NULL");
     if ((rc = kmerdb_device(q->device))) return rc;
-    const uint64_t sep_total = total + n_reads;  // one 'N' behind every read
-    const uint64_t passes = tbk_probe_passes(sep_total);
-    if ((rc = query_reserve(q->bases, total + 16)) || (rc = query_reserve(q->offsets, (n_reads + 1) * 8)) || (rc = query_reserve(q->sep, sep_total + 16)) ||
-        (rc = query_reserve(q->clean_bits, passes * 64 * 4)) || (rc = query_reserve(q->found_bits, passes * 64 * 4)) ||
-        (rc = query_reserve(q->saturated_bits, passes * 64 * 4)) || (rc = query_reserve(q->collapsed_bits, passes * 64 * 4)) ||
-        (rc = query_reserve(q->expanded_bits, passes * 64 * 4)) || (rc = query_reserve(q->bytes, passes * 2048)) ||
-        (rc = query_reserve(q->copy_bytes, passes * 2048)) || (rc = query_reserve(q->bin_prefix, (n_reads + 1) * 8)) ||
-        (rc = query_reserve(q->bins, n_bins * sizeof(tbk_depth_bin))))
+    uint64_t sep_total, passes;
+    if ((rc = query_stage_batch(q, bases, offsets, n_reads, &sep_total, &passes)) || (rc = query_reserve(q->saturated_bits, passes * 64 * 4)) ||
+        (rc = query_reserve(q->collapsed_bits, passes * 64 * 4)) || (rc = query_reserve(q->expanded_bits, passes * 64 * 4)) ||
+        (rc = query_reserve(q->bytes, passes * 2048)) || (rc = query_reserve(q->copy_bytes, passes * 2048)) ||
+        (rc = query_reserve(q->bin_prefix, (n_reads + 1) * 8)) || (rc = query_reserve(q->bins, n_bins * sizeof(tbk_depth_bin))))
         return rc;
-    CHIP(hipMemcpyAsync(q->bases.p, bases, total, hipMemcpyHostToDevice, nullptr));
-    CHIP(hipMemcpyAsync(q->offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, nullptr));
     CHIP(hipMemcpy(q->bin_prefix.p, prefix.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice));  // (prefix is pageable and local: a copy that has left it on return)
-    CHIP(tbk_launch_separate(q->bases.as<uint8_t>(), q->offsets.as<uint64_t>(), n_reads, q->sep.as<uint8_t>(), nullptr));
-    const tbk_kmerdb *db = q->db;
-    CHIP(tbk_launch_depth_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, db->n ? db->d_keys : (const uint64_t *)q->d_pad,
-                                 db->n ? db->d_counts : (const uint8_t *)q->d_pad, q->d_copies, q->d_dir, db->n, q->prefix_bits,
-                                 std::min<uint32_t>(peak, 509), q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(),
+    CHIP(tbk_launch_depth_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, q->view(), q->d_copies, std::min<uint32_t>(peak, 509),
+                                 q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(),
                                  q->saturated_bits.as<uint32_t>(), q->collapsed_bits.as<uint32_t>(), q->expanded_bits.as<uint32_t>(), q->bytes.as<uint8_t>(),
                                  q->copy_bytes.as<uint8_t>(), q->wave_slots, nullptr));
     CHIP(tbk_launch_depth_bins(q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(), q->saturated_bits.as<uint32_t>(), q->collapsed_bits.as<uint32_t>(),
@@ -2008,32 +1992,22 @@ extern "C" int tbk_kmerdb_query_repairs(tbk_kmerdb_query *q, const uint8_t *base
     if (rc) return rc;
     const uint64_t total = offsets[n_reads];
     if (total && !bases) return cfail(TBK_ERR_INVALID, "bases is NULL");
-    uint64_t windows = 0;
     for (uint64_t r = 0; r < n_reads; r++) {
         const uint64_t len = offsets[r + 1] - offsets[r];
-        if (len >= (uint64_t)q->k) windows += len - (uint64_t)q->k + 1;
         if (len >= (1ull << 32))
             return cfail(TBK_ERR_INVALID, "repairs: sequence %llu has %llu bases: a record counts a stretch's windows in 32 bits", (unsigned long long)r,
                          (unsigned long long)len);
     }
+    const uint64_t windows = query_count_windows(offsets, n_reads, q->k);
     if (!windows) return TBK_OK;
     if ((rc = kmerdb_device(q->device))) return rc;
-    const uint64_t sep_total = total + n_reads;  // one 'N' behind every read
-    const uint64_t passes = tbk_probe_passes(sep_total);
-    if ((rc = query_reserve(q->bases, total + 16)) || (rc = query_reserve(q->offsets, (n_reads + 1) * 8)) || (rc = query_reserve(q->sep, sep_total + 16)) ||
-        (rc = query_reserve(q->clean_bits, passes * 64 * 4)) || (rc = query_reserve(q->found_bits, passes * 64 * 4)))
-        return rc;
-    const tbk_kmerdb *db = q->db;
-    const uint64_t *d_keys = db->n ? db->d_keys : (const uint64_t *)q->d_pad;
-    const uint8_t *d_counts = db->n ? db->d_counts : (const uint8_t *)q->d_pad;
-    const uint32_t m = std::max<uint32_t>(db->floor, min_count);
+    const TbkDbView db = q->view();
+    const uint32_t m = std::max<uint32_t>(q->db->floor, min_count);
+    uint64_t sep_total, passes;
+    const auto t0 = std::chrono::steady_clock::now();  // (the buffers are there after the first call: the clock runs over the copy in)
+    if ((rc = query_stage_batch(q, bases, offsets, n_reads, &sep_total, &passes))) return rc;
     uint32_t *d_broken = q->found_bits.as<uint32_t>();
-    const auto t0 = std::chrono::steady_clock::now();
-    CHIP(hipMemcpyAsync(q->bases.p, bases, total, hipMemcpyHostToDevice, nullptr));
-    CHIP(hipMemcpyAsync(q->offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, nullptr));
-    CHIP(tbk_launch_separate(q->bases.as<uint8_t>(), q->offsets.as<uint64_t>(), n_reads, q->sep.as<uint8_t>(), nullptr));
-    CHIP(tbk_launch_repair_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, d_keys, d_counts, q->d_dir, db->n, q->prefix_bits, m,
-                                  q->clean_bits.as<uint32_t>(), d_broken, q->wave_slots, nullptr));
+    CHIP(tbk_launch_repair_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, db, m, q->clean_bits.as<uint32_t>(), d_broken, q->wave_slots, nullptr));
     Compaction sel;
     unsigned long long found = 0;
     hipError_t e = sel.reserve(passes * 2048, nullptr);
@@ -2047,8 +2021,8 @@ extern "C" int tbk_kmerdb_query_repairs(tbk_kmerdb_query *q, const uint8_t *base
         e = tbk_launch_repair_stretches(d_broken, passes, q->offsets.as<uint64_t>(), n_reads, sel.d_flags, sel.offsets(), q->repairs.as<tbk_repair>(),
                                         found, nullptr);
         if (e == hipSuccess)
-            e = tbk_launch_repair(q->sep.as<uint8_t>(), q->offsets.as<uint64_t>(), q->k, d_keys, d_counts, q->d_dir, db->n, q->prefix_bits, m, min_support,
-                                  q->repairs.as<tbk_repair>(), found, q->wave_slots, nullptr);
+            e = tbk_launch_repair(q->sep.as<uint8_t>(), q->offsets.as<uint64_t>(), q->k, db, m, min_support, q->repairs.as<tbk_repair>(), found,
+                                  q->wave_slots, nullptr);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
         q->repair_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
         q->repair_ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
@@ -2093,29 +2067,16 @@ extern "C" int tbk_kmerdb_query_evidence(tbk_kmerdb_query *q, const uint8_t *bas
     const uint64_t total = offsets[n_reads];
     if (total && !bases) return cfail(TBK_ERR_INVALID, "bases is NULL");
     memset(out, 0, n_reads * sizeof(tbk_read_evidence));
-    uint64_t windows = 0;
-    for (uint64_t r = 0; r < n_reads; r++) {
-        const uint64_t len = offsets[r + 1] - offsets[r];
-        if (len >= (uint64_t)q->k) windows += len - (uint64_t)q->k + 1;
-    }
-    if (!windows) return TBK_OK;
+    if (!query_count_windows(offsets, n_reads, q->k)) return TBK_OK;
     if ((rc = kmerdb_device(q->device))) return rc;
-    const uint64_t sep_total = total + n_reads;  // one 'N' behind every read
-    const uint64_t passes = tbk_probe_passes(sep_total);
-    if ((rc = query_reserve(q->bases, total + 16)) || (rc = query_reserve(q->offsets, (n_reads + 1) * 8)) || (rc = query_reserve(q->sep, sep_total + 16)) ||
-        (rc = query_reserve(q->clean_bits, passes * 64 * 4)) || (rc = query_reserve(q->found_bits, passes * 64 * 4)) ||
-        (rc = query_reserve(q->evidence, n_reads * sizeof(tbk_read_evidence))))
-        return rc;
+    if ((rc = query_reserve(q->evidence, n_reads * sizeof(tbk_read_evidence)))) return rc;
     for (hipEvent_t &mark : q->evidence_marks)
         if (!mark) CHIP(hipEventCreate(&mark));
-    const tbk_kmerdb *db = q->db;
-    CHIP(hipMemcpyAsync(q->bases.p, bases, total, hipMemcpyHostToDevice, nullptr));
-    CHIP(hipMemcpyAsync(q->offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, nullptr));
-    CHIP(tbk_launch_separate(q->bases.as<uint8_t>(), q->offsets.as<uint64_t>(), n_reads, q->sep.as<uint8_t>(), nullptr));
+    uint64_t sep_total, passes;
+    if ((rc = query_stage_batch(q, bases, offsets, n_reads, &sep_total, &passes))) return rc;
     CHIP(hipEventRecord(q->evidence_marks[0], nullptr));
-    CHIP(tbk_launch_screen_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, db->n ? db->d_keys : (const uint64_t *)q->d_pad,
-                                  db->n ? db->d_counts : (const uint8_t *)q->d_pad, q->d_dir, db->n, q->prefix_bits, std::max<uint32_t>(db->floor, min_count),
-                                  max_count, q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(), q->wave_slots, nullptr));
+    CHIP(tbk_launch_screen_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, q->view(), std::max<uint32_t>(q->db->floor, min_count), max_count,
+                                  q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(), q->wave_slots, nullptr));
     CHIP(hipEventRecord(q->evidence_marks[1], nullptr));
     CHIP(tbk_launch_screen_evidence(q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(), q->offsets.as<uint64_t>(), n_reads, q->k,
                                     q->evidence.as<tbk_read_evidence>(), q->wave_slots, nullptr));

@@ -10,17 +10,7 @@
 
 #include "../../include/tbk.h"
 #include "tbk_common.h"
-#include "tbk_device.h"
-
-// What the lookup reads of a session (tbk_query.hip's TbkQueryDb, and the copy counters beside the counters)
-struct TbkDepthDb {
-    const uint64_t *keys;
-    const uint8_t *counts;
-    const uint32_t *copies;
-    const uint32_t *dir;
-    uint32_t n;
-    int prefix_bits;
-};
+#include "tbk_lookup.h"
 
 // What the lookup pass leaves for the bin pass.  The bitmaps hold one bit per stream position, 64 words per pass, like the
 // query's: clean, present (c >= 1), saturated (c == 255) and the two verdicts.  c and min(a, 255) are one byte per stream
@@ -30,100 +20,32 @@ struct TbkDepthMarks {
     uint8_t *c, *a;
 };
 
-constexpr int TBK_D_GROUP = 4;  // windows of a lane whose searches are in flight together (one 32-bit word of bytes)
-
-// One wave per pass of TBK_PASS window starts of the separated stream, staged and rolled as tbk_query_lookup_kernel does
-// it: lane l holds the 64 bases from P0 + 32 l on and rolls its 32 windows out of registers, TBK_D_GROUP at a time; every
-// step of a group's searches - the two directory offsets, one rank per bisection step, the counter, the copy counter - is
-// issued for all of its windows before any answer is used, and a lane whose search is over reads entry 0 again, so no
-// load is under a branch.  Nothing of the session is written: no atomic, no histogram.
+// One wave per pass of TBK_PASS window starts of the separated stream: staging, roll and the grouped search are lookup_pass's
+// (tbk_lookup.h).  The session's copy counter a of an entry (copies, beside the view's counters) is read as the search reads
+// the counter: for all of a group's windows before any is used, a miss reading entry 0.  Nothing of the session is written:
+// no atomic, no histogram.
 // The verdicts are drawn here, where the full 32-bit a is at hand, in 64-bit integers: for a present window with
 // c < 255, collapsed is 2c > (2a + 1) peak and expanded is a >= 1 and 2c < (2a - 1) peak.  The host passes
 // min(peak, 509): 2c <= 508, so every peak above 508 answers as 509 does, and (2a + 1) 509 < 2^42 cannot wrap.
 __global__ void __launch_bounds__(64)
-tbk_depth_lookup_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_t n_passes, int k, TbkDepthDb db, uint32_t peak, TbkDepthMarks out) {
+tbk_depth_lookup_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_t n_passes, int k, TbkDbView db, const uint32_t *__restrict__ copies,
+                        uint32_t peak, TbkDepthMarks out) {
     __shared__ uint64_t stage[TBK_CHUNKS + 2];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    const uint32_t badk = k == 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);
-    const int shift = 2 * k - db.prefix_bits;  // (64 only when prefix_bits is 0: not used then)
     for (uint64_t pass = blockIdx.x; pass < n_passes; pass += gridDim.x) {
-        const uint64_t P0 = pass * TBK_PASS;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        stage[lane] = load_chunk(sep, P0 + (uint64_t)lane * 16, total);
-        stage[64 + lane] = load_chunk(sep, P0 + (uint64_t)(64 + lane) * 16, total);
-        if (lane < 2) stage[128 + lane] = load_chunk(sep, P0 + (uint64_t)(128 + lane) * 16, total);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const uint64_t e0 = stage[2 * lane], e1 = stage[2 * lane + 1], e2 = stage[2 * lane + 2], e3 = stage[2 * lane + 3];
-        uint32_t s0 = (uint32_t)e0, s1 = (uint32_t)e1, s2 = (uint32_t)e2, s3 = (uint32_t)e3;
-        const unsigned __int128 R128 = (unsigned __int128)rev_pairs(~s3) | ((unsigned __int128)rev_pairs(~s2) << 32) |
-                                       ((unsigned __int128)rev_pairs(~s1) << 64) | ((unsigned __int128)rev_pairs(~s0) << 96);
-        const unsigned __int128 Rs = R128 >> (64 - 2 * k);
-        uint32_t t0 = (uint32_t)Rs, t1 = (uint32_t)(Rs >> 32), t2 = (uint32_t)(Rs >> 64), t3 = (uint32_t)(Rs >> 96);
-        uint32_t bad_lo = (uint32_t)(e0 >> 32) | ((uint32_t)(e1 >> 32) << 16);
-        uint32_t bad_hi = (uint32_t)(e2 >> 32) | ((uint32_t)(e3 >> 32) << 16);
-        const uint64_t p_lane = P0 + (uint64_t)lane * TBK_WPL;
+        const uint64_t p_lane = pass * TBK_PASS + (uint64_t)lane * TBK_WPL;
         uint32_t w_clean = 0, w_present = 0, w_saturated = 0, w_collapsed = 0, w_expanded = 0;
-#pragma unroll 1
-        for (int j0 = 0; j0 < TBK_WPL; j0 += TBK_D_GROUP) {
-            uint64_t rank[TBK_D_GROUP];
-            uint32_t lo[TBK_D_GROUP], hi[TBK_D_GROUP];
-            bool ok[TBK_D_GROUP], hit[TBK_D_GROUP];
+        lookup_pass(stage, sep, total, pass, k, db, [&](int j0, const LookupGroup &w) {
+            uint32_t a[TBK_GROUP];
 #pragma unroll
-            for (int g = 0; g < TBK_D_GROUP; g++) {
-                const uint64_t fwd = ((uint64_t)s0 | ((uint64_t)s1 << 32)) & kmask;
-                const uint64_t rc = ((uint64_t)t2 | ((uint64_t)t3 << 32)) & kmask;
-                rank[g] = lex_rank(fwd < rc ? fwd : rc, k);
-                ok[g] = (bad_lo & badk) == 0 && p_lane + (uint64_t)(j0 + g) + (uint64_t)k <= total;
-                s0 = (s0 >> 2) | (s1 << 30); s1 = (s1 >> 2) | (s2 << 30); s2 = (s2 >> 2) | (s3 << 30); s3 >>= 2;
-                t3 = (t3 << 2) | (t2 >> 30); t2 = (t2 << 2) | (t1 >> 30); t1 = (t1 << 2) | (t0 >> 30); t0 <<= 2;
-                bad_lo = (bad_lo >> 1) | (bad_hi << 31); bad_hi >>= 1;
-            }
-#pragma unroll
-            for (int g = 0; g < TBK_D_GROUP; g++) {
-                const uint64_t p = ok[g] && db.prefix_bits ? rank[g] >> shift : 0;
-                lo[g] = db.dir[p];
-                hi[g] = db.dir[p + 1];
-            }
-#pragma unroll
-            for (int g = 0; g < TBK_D_GROUP; g++) {
-                if (!ok[g]) hi[g] = lo[g];
-                hit[g] = false;
-            }
-            for (;;) {
-                bool more = false;
-#pragma unroll
-                for (int g = 0; g < TBK_D_GROUP; g++) more = more || lo[g] < hi[g];
-                if (!more) break;
-                uint64_t v[TBK_D_GROUP];
-                uint32_t mid[TBK_D_GROUP];
-#pragma unroll
-                for (int g = 0; g < TBK_D_GROUP; g++) {
-                    mid[g] = lo[g] + (hi[g] - lo[g]) / 2;
-                    v[g] = db.keys[lo[g] < hi[g] ? mid[g] : 0];
-                }
-#pragma unroll
-                for (int g = 0; g < TBK_D_GROUP; g++) {
-                    if (lo[g] < hi[g]) {
-                        if (v[g] == rank[g]) { hit[g] = true; lo[g] = hi[g] = mid[g]; }
-                        else if (v[g] < rank[g]) lo[g] = mid[g] + 1;
-                        else hi[g] = mid[g];
-                    }
-                }
-            }
-            uint32_t c[TBK_D_GROUP], a[TBK_D_GROUP];
-#pragma unroll
-            for (int g = 0; g < TBK_D_GROUP; g++) {
-                c[g] = db.counts[hit[g] ? lo[g] : 0];
-                a[g] = db.copies[hit[g] ? lo[g] : 0];
-            }
+            for (int g = 0; g < TBK_GROUP; g++) a[g] = copies[w.hit[g] ? w.at[g] : 0];
             uint32_t word_c = 0, word_a = 0;
 #pragma unroll
-            for (int g = 0; g < TBK_D_GROUP; g++) {
-                const uint32_t cg = hit[g] ? c[g] : 0, bit = 1u << (j0 + g);
+            for (int g = 0; g < TBK_GROUP; g++) {
+                const uint32_t cg = w.c[g], bit = 1u << (j0 + g);
                 const uint64_t twice_c = 2ull * cg, twice_a = 2ull * a[g];
                 const bool verdict = cg != 0 && cg < 255u;
-                if (ok[g]) w_clean |= bit;
+                if (w.ok[g]) w_clean |= bit;
                 if (cg) w_present |= bit;
                 if (cg == 255u) w_saturated |= bit;
                 if (verdict && twice_c > (twice_a + 1ull) * peak) w_collapsed |= bit;
@@ -133,7 +55,7 @@ tbk_depth_lookup_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_
             }
             *reinterpret_cast<uint32_t *>(out.c + p_lane + j0) = word_c;
             *reinterpret_cast<uint32_t *>(out.a + p_lane + j0) = word_a;
-        }
+        });
         out.clean[pass * 64 + lane] = w_clean;
         out.present[pass * 64 + lane] = w_present;
         out.saturated[pass * 64 + lane] = w_saturated;
@@ -141,7 +63,7 @@ tbk_depth_lookup_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_
         out.expanded[pass * 64 + lane] = w_expanded;
     }
 }
-static_assert(TBK_D_GROUP == 4 && TBK_WPL % TBK_D_GROUP == 0, "a group's bytes are one 32-bit store");
+static_assert(TBK_GROUP == 4, "a group's bytes are one 32-bit store");
 
 // the lower median of a 256-row histogram of m >= 1 values, lane l holding the sum of rows 4 l .. 4 l + 3 in `mine`: an
 // inclusive wave scan of the lanes' sums finds the lane whose rows hold sorted value (m - 1) / 2, and that lane walks its four rows
@@ -192,9 +114,7 @@ tbk_depth_bin_kernel(TbkDepthMarks in, const uint64_t *__restrict__ offsets, con
         const uint64_t w_first = p0 >> 5, w_last = (p1 - 1) >> 5;
 #pragma unroll 1
         for (uint64_t w = w_first + lane; w <= w_last; w += 64) {
-            uint32_t mask = 0xFFFFFFFFu;
-            if (w == w_first) mask &= 0xFFFFFFFFu << (p0 & 31u);
-            if (w == w_last) mask &= 0xFFFFFFFFu >> (31u - (uint32_t)((p1 - 1) & 31u));
+            const uint32_t mask = range_word_mask(w, w_first, w_last, p0, p1);
             n_clean += (uint32_t)__popc(in.clean[w] & mask);
             n_present += (uint32_t)__popc(in.present[w] & mask);
             n_saturated += (uint32_t)__popc(in.saturated[w] & mask);
@@ -243,23 +163,19 @@ tbk_depth_bin_kernel(TbkDepthMarks in, const uint64_t *__restrict__ offsets, con
 static_assert(sizeof(tbk_depth_bin) == 24, "a bin is six 32-bit words: five counts, then depth, copies and two zero bytes");
 
 // =======================================================================================
-// launchers (called from tbk_count.cpp)
+// launchers (called from tbk_count.cpp; what the arguments hold: tbk_lookup_host.h)
 // =======================================================================================
-// bitmaps: 64 words per pass each; d_c and d_a: TBK_PASS bytes per pass each; peak: at most 509 (the kernel's comment)
-extern "C" hipError_t tbk_launch_depth_lookup(const uint8_t *d_sep, uint64_t total, uint64_t n_passes, int k, const uint64_t *d_keys,
-                                              const uint8_t *d_counts, const uint32_t *d_copies, const uint32_t *d_dir, uint64_t n, int prefix_bits,
+extern "C" hipError_t tbk_launch_depth_lookup(const uint8_t *d_sep, uint64_t total, uint64_t n_passes, int k, TbkDbView db, const uint32_t *d_copies,
                                               uint32_t peak, uint32_t *d_clean, uint32_t *d_present, uint32_t *d_saturated, uint32_t *d_collapsed,
                                               uint32_t *d_expanded, uint8_t *d_c, uint8_t *d_a, uint64_t wave_slots, hipStream_t stream) {
     if (!n_passes) return hipSuccess;
-    if (k < 1 || k > 32 || prefix_bits < 0 || prefix_bits > 2 * k || n > 0xFFFFFFFFull || peak < 1 || peak > 509) return hipErrorInvalidValue;
+    if (!tbk_db_view_ok(db, k) || peak < 1 || peak > 509) return hipErrorInvalidValue;
     const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n_passes, wave_slots))), block(64);
-    const TbkDepthDb db{d_keys, d_counts, d_copies, d_dir, (uint32_t)n, prefix_bits};
     const TbkDepthMarks out{d_clean, d_present, d_saturated, d_collapsed, d_expanded, d_c, d_a};
-    hipLaunchKernelGGL(tbk_depth_lookup_kernel, grid, block, 0, stream, d_sep, total, n_passes, k, db, peak, out);
+    hipLaunchKernelGGL(tbk_depth_lookup_kernel, grid, block, 0, stream, d_sep, total, n_passes, k, db, d_copies, peak, out);
     return hipGetLastError();
 }
 
-// d_prefix: n_reads + 1 running sums of bins, d_prefix[n_reads] = n_bins; d_bins: n_bins x 24 bytes
 extern "C" hipError_t tbk_launch_depth_bins(uint32_t *d_clean, uint32_t *d_present, uint32_t *d_saturated, uint32_t *d_collapsed, uint32_t *d_expanded,
                                             uint8_t *d_c, uint8_t *d_a, const uint64_t *d_offsets, const uint64_t *d_prefix, uint64_t n_reads,
                                             uint64_t n_bins, int k, uint32_t window, tbk_depth_bin *d_bins, uint64_t wave_slots, hipStream_t stream) {

@@ -14,16 +14,13 @@
 
 #include "../../include/tbk.h"
 #include "tbk_compact.h"
-#include "tbk_device.h"
+#include "tbk_lookup.h"
 
-// What a lookup reads: the database's ranks and counters, the directory over the top prefix_bits bits of the 2k-bit rank
-// (dir[p]: the first entry whose rank has prefix >= p, dir[2^prefix_bits] = n) and the candidates' counter range.
+// What a lookup reads: the database behind its directory (n >= 1 wherever a kernel runs: a lane whose search is over reads
+// entry 0), its k and the candidates' counter range.
 struct HetDb {
-    const uint64_t *keys;
-    const uint8_t *counts;
-    const uint32_t *dir;
-    uint32_t n;  // (>= 1 wherever a kernel runs: a lane whose search is over reads entry 0)
-    int k, prefix_bits;
+    TbkDbView view;
+    int k;
     uint32_t c_min, c_max;
 };
 
@@ -43,16 +40,13 @@ __device__ __forceinline__ uint64_t het_revcomp(uint64_t rank, int k) { return l
 // complement maps to itself) that are candidates too: their number, 0..3, and - meaningful when that is 1 - the one's
 // entry and counter.  The three variants x ^ (d << 2m) are made canonical and treated as a SET: one that is x itself (AAT ->
 // ATT = its reverse complement) or equals an earlier one (AAT: ACT and AGT are one k-mer) is dropped before anything is
-// searched.  The three searches are independent, so each step is issued for all of them before any answer is used: the two
-// directory offsets, one rank per bisection step, the counter - tbk_query_lookup_kernel's group of four, here of three.  A
-// search that is over, or never began (`live` false: not a candidate; a dropped variant), reads entry 0 again, so no load is
-// under a branch.  Nothing crosses lanes here: a wave may call it with some lanes only (the scatter does).
+// searched.  The three are then searched side by side (db_search_group, tbk_lookup.h: no load under a branch); one that never
+// began (`live` false: not a candidate; a dropped variant) reads entry 0 like one that is over.  Nothing crosses lanes here: a
+// wave may call it with some lanes only (the scatter does).
 __device__ __forceinline__ uint32_t het_partners_in_range(const HetDb &db, bool live, uint64_t x, uint32_t &partner, uint32_t &c_partner) {
     const int mid_bit = db.k - 1;  // 2m
-    const int shift = 2 * db.k - db.prefix_bits;  // (<= 62: k is odd, so at most 31)
-    (void)shift;
     uint64_t want[3];
-    uint32_t lo[3], hi[3];
+    uint32_t at[3], c[3];
     bool ok[3], hit[3];
 #pragma unroll
     for (int d = 0; d < 3; d++) {
@@ -62,52 +56,14 @@ __device__ __forceinline__ uint32_t het_partners_in_range(const HetDb &db, bool 
         ok[d] = live && want[d] != x;
 #pragma unroll
         for (int e = 0; e < d; e++) ok[d] = ok[d] && want[d] != want[e];  // (an earlier variant that was x itself is no partner either)
-        hit[d] = false;
     }
-#ifdef TBK_HETMER_NO_DIRECTORY  // (measurement only, tools/build_variant.sh with VARIANT_SRC=tbk_hetmer: every lookup bisects the whole database)
-#pragma unroll
-    for (int d = 0; d < 3; d++) { lo[d] = 0; hi[d] = ok[d] ? db.n : 0; }
-#else
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        const uint64_t p = ok[d] && db.prefix_bits ? want[d] >> shift : 0;
-        lo[d] = db.dir[p];
-        hi[d] = db.dir[p + 1];
-    }
-#pragma unroll
-    for (int d = 0; d < 3; d++)
-        if (!ok[d]) hi[d] = lo[d];
-#endif
-    for (;;) {
-        bool more = false;
-#pragma unroll
-        for (int d = 0; d < 3; d++) more = more || lo[d] < hi[d];
-        if (!more) break;
-        uint64_t v[3];
-        uint32_t mid[3];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            mid[d] = lo[d] + (hi[d] - lo[d]) / 2;  // (< hi <= n)
-            v[d] = db.keys[lo[d] < hi[d] ? mid[d] : 0];
-        }
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            if (lo[d] < hi[d]) {
-                if (v[d] == want[d]) { hit[d] = true; lo[d] = hi[d] = mid[d]; }
-                else if (v[d] < want[d]) lo[d] = mid[d] + 1;
-                else hi[d] = mid[d];
-            }
-        }
-    }
-    uint32_t c[3];
-#pragma unroll
-    for (int d = 0; d < 3; d++) c[d] = db.counts[hit[d] ? lo[d] : 0];
+    db_search_group<3>(db.view, db.k, want, ok, at, hit, c);  // (the directory's shift is <= 62: k is odd, so at most 31)
     uint32_t found = 0;
 #pragma unroll
     for (int d = 0; d < 3; d++) {
         if (hit[d] && c[d] >= db.c_min && c[d] <= db.c_max) {
             found++;
-            partner = lo[d];
+            partner = at[d];
             c_partner = c[d];
         }
     }
@@ -118,9 +74,9 @@ __device__ __forceinline__ uint32_t het_partners_in_range(const HetDb &db, bool 
 // pair is found once, from there (the partner then has exactly one partner too, i itself: classes are equivalence classes).
 __device__ __forceinline__ bool het_founds_pair(const HetDb &db, uint64_t i, bool in_n, uint32_t &c, uint32_t &partner, uint32_t &c_partner,
                                                 uint32_t &found, bool &candidate) {
-    c = in_n ? db.counts[i] : 0u;
+    c = in_n ? db.view.counts[i] : 0u;
     candidate = in_n && c >= db.c_min && c <= db.c_max;
-    const uint64_t x = db.keys[in_n ? i : 0];
+    const uint64_t x = db.view.keys[in_n ? i : 0];
     partner = 0;
     c_partner = 0;
     found = het_partners_in_range(db, candidate, x, partner, c_partner);
@@ -198,15 +154,15 @@ tbk_hetmer_tally_kernel(HetDb db, HetPartner y, HetPartner z, uint64_t tiles, un
     __shared__ uint32_t sums[HETMER_SUMS];
     __shared__ uint64_t bound[4];  // y: first, last; z: first, last
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t n = db.n;
+    const uint64_t n = db.view.n;
     for (uint32_t i = threadIdx.x; i < HCORNER * HCORNER; i += 256) tally[i] = 0;
     if (threadIdx.x < HETMER_SUMS) sums[threadIdx.x] = 0;
     __syncthreads();
     uint32_t by_partners[4] = {0, 0, 0, 0}, n_pairs = 0;  // (the same in every lane of a wave)
     for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const uint64_t first = tile * TBK_DBT_TILE;  // (< n)
-        compact_tile_bounds(db.keys, n, first, y.keys, y.n, bound, 0);
-        compact_tile_bounds(db.keys, n, first, z.keys, z.n, bound + 2, 64);
+        compact_tile_bounds(db.view.keys, n, first, y.keys, y.n, bound, 0);
+        compact_tile_bounds(db.view.keys, n, first, z.keys, z.n, bound + 2, 64);
         __syncthreads();
         for (uint32_t r = 0; r < TBK_DBT_TILE / 256; r++) {
             const uint64_t i = first + (uint64_t)r * 256 + threadIdx.x;
@@ -224,7 +180,7 @@ tbk_hetmer_tally_kernel(HetDb db, HetPartner y, HetPartner z, uint64_t tiles, un
                 else
                     atomicAdd(&spec[c_minor * 256 + c_major], 1ull);
                 uint32_t cls_i, cls_p;
-                het_classes(y, z, bound, db.keys[i], db.keys[partner], cls_i, cls_p);
+                het_classes(y, z, bound, db.view.keys[i], db.view.keys[partner], cls_i, cls_p);
                 atomicAdd(&sums[6 + (first_minor ? cls_i * 4 + cls_p : cls_p * 4 + cls_i)], 1u);
             }
         }
@@ -252,7 +208,7 @@ tbk_hetmer_tally_kernel(HetDb db, HetPartner y, HetPartner z, uint64_t tiles, un
 // flag: the entries that found a pair, one bit each, one count per tile; one block per tile of 1024 entries
 __global__ void __launch_bounds__(256)
 tbk_hetmer_flag_kernel(HetDb db, uint64_t *__restrict__ flags, unsigned long long *__restrict__ tile_counts) {
-    const uint64_t n = db.n;
+    const uint64_t n = db.view.n;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     __shared__ uint32_t tile_sum;
     const uint64_t tile = blockIdx.x;
@@ -285,16 +241,16 @@ __global__ void __launch_bounds__(256)
 tbk_hetmer_scatter_kernel(HetDb db, HetPartner y, HetPartner z, const uint64_t *__restrict__ flags, const unsigned long long *__restrict__ tile_offsets,
                           tbk_hetmer_pair *__restrict__ out, uint64_t n_out) {
     __shared__ uint64_t bound[4];  // y: first, last; z: first, last
-    const uint64_t n = db.n;
+    const uint64_t n = db.view.n;
     const uint64_t first = (uint64_t)blockIdx.x * TBK_DBT_TILE;  // (< n)
-    compact_tile_bounds(db.keys, n, first, y.keys, y.n, bound, 0);
-    compact_tile_bounds(db.keys, n, first, z.keys, z.n, bound + 2, 64);
+    compact_tile_bounds(db.view.keys, n, first, y.keys, y.n, bound, 0);
+    compact_tile_bounds(db.view.keys, n, first, z.keys, z.n, bound + 2, 64);
     compact_scatter_tile_dense(n, flags, tile_offsets, [=](uint64_t i, uint64_t at) {  // (its barriers publish the bounds)
         if (at >= n_out) return;
         uint32_t c, partner, c_partner, found;
         bool candidate;
         if (!het_founds_pair(db, i, true, c, partner, c_partner, found, candidate)) return;  // (flags that are not this database's: nothing written)
-        const uint64_t x = db.keys[i], px = db.keys[partner];
+        const uint64_t x = db.view.keys[i], px = db.view.keys[partner];
         uint32_t cls_i, cls_p;
         het_classes(y, z, bound, x, px, cls_i, cls_p);
         const bool first_minor = het_first_is_minor(c, c_partner);
@@ -327,7 +283,7 @@ extern "C" hipError_t tbk_launch_hetmer_tally(const uint64_t *d_keys, const uint
     const uint64_t tiles = tbk_kmerdb_table_tiles(n);
     const unsigned grid = tbk_count_entry_grid_(tiles < HETMER_GRID ? tiles : HETMER_GRID);
     if ((tiles + grid - 1) / grid > HETMER_MAX_TILES_PER_BLOCK) return hipErrorInvalidValue;
-    const HetDb db{d_keys, d_counts, d_dir, (uint32_t)n, k, prefix_bits, c_min, c_max};
+    const HetDb db{{d_keys, d_counts, d_dir, (uint32_t)n, prefix_bits}, k, c_min, c_max};
     hipLaunchKernelGGL(tbk_hetmer_tally_kernel, dim3(grid), dim3(256), 0, stream, db, hetmer_partner(y), hetmer_partner(z), tiles, d_sums, d_spec);
     return hipGetLastError();
 }
@@ -337,7 +293,7 @@ extern "C" hipError_t tbk_launch_hetmer_flag(const uint64_t *d_keys, const uint8
     const TbkHetmerPartner none = {nullptr, nullptr, 0, 1, 255};
     if (!n) return hipSuccess;
     if (!hetmer_args(n, k, prefix_bits, &none, &none)) return hipErrorInvalidValue;
-    const HetDb db{d_keys, d_counts, d_dir, (uint32_t)n, k, prefix_bits, c_min, c_max};
+    const HetDb db{{d_keys, d_counts, d_dir, (uint32_t)n, prefix_bits}, k, c_min, c_max};
     return compact_launch_tiles(n, stream, tbk_hetmer_flag_kernel, db, d_flags, d_tile_counts);
 }
 
@@ -347,6 +303,6 @@ extern "C" hipError_t tbk_launch_hetmer_scatter(const uint64_t *d_keys, const ui
                                                 hipStream_t stream) {
     if (!n) return hipSuccess;
     if (!hetmer_args(n, k, prefix_bits, y, z)) return hipErrorInvalidValue;
-    const HetDb db{d_keys, d_counts, d_dir, (uint32_t)n, k, prefix_bits, c_min, c_max};
+    const HetDb db{{d_keys, d_counts, d_dir, (uint32_t)n, prefix_bits}, k, c_min, c_max};
     return compact_launch_tiles(n, stream, tbk_hetmer_scatter_kernel, db, hetmer_partner(y), hetmer_partner(z), d_flags, d_tile_offsets, d_out, n_out);
 }

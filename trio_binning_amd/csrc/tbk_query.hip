@@ -9,19 +9,9 @@
 #include "../../include/tbk.h"
 #include "tbk_common.h"
 #include "tbk_compact_host.h"  // (the one declaration of tbk_launch_query_directory)
-#include "tbk_device.h"
+#include "tbk_lookup.h"
 
-// What the lookup reads of a session: the database's ranks and counters (borrowed) and the directory over the top
-// prefix_bits bits of the 2k-bit rank - dir[p] is the first entry whose rank has prefix >= p, dir[2^prefix_bits] = n.
-struct TbkQueryDb {
-    const uint64_t *keys;
-    const uint8_t *counts;
-    const uint32_t *dir;
-    uint32_t n;
-    int prefix_bits;
-};
-
-// One thread per prefix bisects the whole database once (db_lower_bound): 2^prefix_bits + 1 offsets, no atomic, no scan.
+// The directory of a TbkDbView (tbk_lookup_host.h).  One thread per prefix bisects the whole database once (db_lower_bound): 2^prefix_bits + 1 offsets, no atomic, no scan.
 __global__ void __launch_bounds__(256)
 tbk_query_directory_kernel(const uint64_t *__restrict__ keys, uint32_t n, int k, int prefix_bits, uint32_t *__restrict__ dir) {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, top = 1ull << prefix_bits;
@@ -31,121 +21,41 @@ tbk_query_directory_kernel(const uint64_t *__restrict__ keys, uint32_t n, int k,
     dir[p] = (uint32_t)db_lower_bound(keys, 0, n, first);
 }
 
-constexpr int TBK_Q_GROUP = 4;  // windows of a lane whose searches are in flight together (one 32-bit word of counter bytes)
-
-// One wave per pass of TBK_PASS window starts of the separated stream, staged and rolled like tbk_track_mark_kernel's:
-// lane l holds the 64 bases from P0 + 32 l on and rolls its 32 windows out of registers, TBK_Q_GROUP at a time.  The
-// windows of a group are independent, so each step of their searches is issued for all of them before any answer is
-// used: the two directory offsets, then one rank per bisection step of the bucket, then the counter.  A lane whose
-// search is over reads entry 0 again (the host gives an empty database one entry of padding), so no load is under a
-// branch.  A clean window's canonical k-mer is the counter's - min(forward, reverse complement) in the table's form,
-// which is the lexicographic minimum - brought into rank form (lex_rank).
-// Per window: bit j of the lane's clean word and of its found word (c >= min_count), indexed by stream position like the
-// tracker's bitmaps; the wave's histogram of c in LDS, flushed once per block; the entry's seen bit and, with COPIES,
-// its 32-bit copy counter (the host keeps a session below 2^32 window starts); with BYTES, c at the window's stream
-// position.  A window over a separator or past `total` is not clean and stays 0 everywhere.
+// One wave per pass of TBK_PASS window starts of the separated stream: staging, roll and the grouped search are lookup_pass's
+// (tbk_lookup.h).  Per window: bit j of the lane's clean word and of its found word (c >= min_count), indexed by stream
+// position like the tracker's bitmaps; the wave's histogram of c in LDS, flushed once per block; the entry's seen bit and,
+// with COPIES, its 32-bit copy counter (the host keeps a session below 2^32 window starts); with BYTES, c at the window's
+// stream position.  A window over a separator or past `total` is not clean and stays 0 everywhere.
 template <bool BYTES, bool COPIES>
 __global__ void __launch_bounds__(64)
-tbk_query_lookup_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_t n_passes, int k, TbkQueryDb db, uint32_t min_count,
+tbk_query_lookup_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_t n_passes, int k, TbkDbView db, uint32_t min_count,
                         uint32_t *__restrict__ clean_bits, uint32_t *__restrict__ found_bits, uint8_t *__restrict__ bytes,
                         unsigned long long *__restrict__ hist, uint32_t *__restrict__ seen, uint32_t *__restrict__ copies) {
     __shared__ uint64_t stage[TBK_CHUNKS + 2];
     __shared__ uint32_t tally[256];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    const uint32_t badk = k == 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);
-    const int shift = 2 * k - db.prefix_bits;  // (64 only when prefix_bits is 0: not used then)
-    (void)shift;
     for (uint32_t i = lane; i < 256; i += 64) tally[i] = 0;
     for (uint64_t pass = blockIdx.x; pass < n_passes; pass += gridDim.x) {
-        const uint64_t P0 = pass * TBK_PASS;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        stage[lane] = load_chunk(sep, P0 + (uint64_t)lane * 16, total);
-        stage[64 + lane] = load_chunk(sep, P0 + (uint64_t)(64 + lane) * 16, total);
-        if (lane < 2) stage[128 + lane] = load_chunk(sep, P0 + (uint64_t)(128 + lane) * 16, total);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const uint64_t e0 = stage[2 * lane], e1 = stage[2 * lane + 1], e2 = stage[2 * lane + 2], e3 = stage[2 * lane + 3];
-        uint32_t s0 = (uint32_t)e0, s1 = (uint32_t)e1, s2 = (uint32_t)e2, s3 = (uint32_t)e3;
-        const unsigned __int128 R128 = (unsigned __int128)rev_pairs(~s3) | ((unsigned __int128)rev_pairs(~s2) << 32) |
-                                       ((unsigned __int128)rev_pairs(~s1) << 64) | ((unsigned __int128)rev_pairs(~s0) << 96);
-        const unsigned __int128 Rs = R128 >> (64 - 2 * k);
-        uint32_t t0 = (uint32_t)Rs, t1 = (uint32_t)(Rs >> 32), t2 = (uint32_t)(Rs >> 64), t3 = (uint32_t)(Rs >> 96);
-        uint32_t bad_lo = (uint32_t)(e0 >> 32) | ((uint32_t)(e1 >> 32) << 16);
-        uint32_t bad_hi = (uint32_t)(e2 >> 32) | ((uint32_t)(e3 >> 32) << 16);
-        const uint64_t p_lane = P0 + (uint64_t)lane * TBK_WPL;
+        const uint64_t p_lane = pass * TBK_PASS + (uint64_t)lane * TBK_WPL;
         uint32_t word_clean = 0, word_found = 0;
-#pragma unroll 1
-        for (int j0 = 0; j0 < TBK_WPL; j0 += TBK_Q_GROUP) {
-            uint64_t rank[TBK_Q_GROUP];
-            uint32_t lo[TBK_Q_GROUP], hi[TBK_Q_GROUP];
-            bool ok[TBK_Q_GROUP], hit[TBK_Q_GROUP];
-#pragma unroll
-            for (int g = 0; g < TBK_Q_GROUP; g++) {
-                const uint64_t fwd = ((uint64_t)s0 | ((uint64_t)s1 << 32)) & kmask;
-                const uint64_t rc = ((uint64_t)t2 | ((uint64_t)t3 << 32)) & kmask;
-                rank[g] = lex_rank(fwd < rc ? fwd : rc, k);
-                ok[g] = (bad_lo & badk) == 0 && p_lane + (uint64_t)(j0 + g) + (uint64_t)k <= total;
-                s0 = (s0 >> 2) | (s1 << 30); s1 = (s1 >> 2) | (s2 << 30); s2 = (s2 >> 2) | (s3 << 30); s3 >>= 2;
-                t3 = (t3 << 2) | (t2 >> 30); t2 = (t2 << 2) | (t1 >> 30); t1 = (t1 << 2) | (t0 >> 30); t0 <<= 2;
-                bad_lo = (bad_lo >> 1) | (bad_hi << 31); bad_hi >>= 1;
-            }
-#ifdef TBK_QUERY_NO_DIRECTORY  // (measurement only, tools/build_variant.sh: every window bisects the whole database)
-#pragma unroll
-            for (int g = 0; g < TBK_Q_GROUP; g++) { lo[g] = 0; hi[g] = ok[g] ? db.n : 0; hit[g] = false; }
-#else
-#pragma unroll
-            for (int g = 0; g < TBK_Q_GROUP; g++) {
-                const uint64_t p = ok[g] && db.prefix_bits ? rank[g] >> shift : 0;
-                lo[g] = db.dir[p];
-                hi[g] = db.dir[p + 1];
-            }
-#pragma unroll
-            for (int g = 0; g < TBK_Q_GROUP; g++) {
-                if (!ok[g]) hi[g] = lo[g];
-                hit[g] = false;
-            }
-#endif
-            for (;;) {
-                bool more = false;
-#pragma unroll
-                for (int g = 0; g < TBK_Q_GROUP; g++) more = more || lo[g] < hi[g];
-                if (!more) break;
-                uint64_t v[TBK_Q_GROUP];
-                uint32_t mid[TBK_Q_GROUP];
-#pragma unroll
-                for (int g = 0; g < TBK_Q_GROUP; g++) {
-                    mid[g] = lo[g] + (hi[g] - lo[g]) / 2;
-                    v[g] = db.keys[lo[g] < hi[g] ? mid[g] : 0];
-                }
-#pragma unroll
-                for (int g = 0; g < TBK_Q_GROUP; g++) {
-                    if (lo[g] < hi[g]) {
-                        if (v[g] == rank[g]) { hit[g] = true; lo[g] = hi[g] = mid[g]; }
-                        else if (v[g] < rank[g]) lo[g] = mid[g] + 1;
-                        else hi[g] = mid[g];
-                    }
-                }
-            }
-            uint32_t c[TBK_Q_GROUP];
-#pragma unroll
-            for (int g = 0; g < TBK_Q_GROUP; g++) c[g] = db.counts[hit[g] ? lo[g] : 0];
+        lookup_pass(stage, sep, total, pass, k, db, [&](int j0, const LookupGroup &w) {
             uint32_t word = 0;
 #pragma unroll
-            for (int g = 0; g < TBK_Q_GROUP; g++) {
-                const uint32_t cg = hit[g] ? c[g] : 0;
-                if (ok[g]) {
+            for (int g = 0; g < TBK_GROUP; g++) {
+                const uint32_t cg = w.c[g];
+                if (w.ok[g]) {
                     word_clean |= 1u << (j0 + g);
                     atomicAdd(&tally[cg], 1u);
                 }
                 if (cg >= min_count) word_found |= 1u << (j0 + g);  // (min_count >= 2: never an absent window)
                 if (cg) {
-                    atomicOr(&seen[lo[g] >> 5], 1u << (lo[g] & 31u));
-                    if (COPIES) atomicAdd(&copies[lo[g]], 1u);
+                    atomicOr(&seen[w.at[g] >> 5], 1u << (w.at[g] & 31u));
+                    if (COPIES) atomicAdd(&copies[w.at[g]], 1u);
                 }
                 word |= cg << (8 * g);
             }
             if (BYTES) *reinterpret_cast<uint32_t *>(bytes + p_lane + j0) = word;
-        }
+        });
         clean_bits[pass * 64 + lane] = word_clean;
         found_bits[pass * 64 + lane] = word_found;
     }
@@ -155,7 +65,7 @@ tbk_query_lookup_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_
         if (v) atomicAdd(&hist[i], (unsigned long long)v);
     }
 }
-static_assert(TBK_Q_GROUP == 4 && TBK_WPL % TBK_Q_GROUP == 0, "a group's counters are one 32-bit store");
+static_assert(TBK_GROUP == 4, "a group's counters are one 32-bit store");
 
 // Sequence r lies at stream positions offsets[r] + r .. offsets[r + 1] + r: its clean and its found windows are the set
 // bits of the two bitmaps in that range (its last k - 1 window starts hold the separator and are clear).  One wave per
@@ -171,9 +81,7 @@ tbk_query_totals_kernel(const uint32_t *__restrict__ clean_bits, const uint32_t 
         if (b > a) {
             const uint64_t w_first = a >> 5, w_last = (b - 1) >> 5;
             for (uint64_t w = w_first + lane; w <= w_last; w += 64) {
-                uint32_t mask = 0xFFFFFFFFu;
-                if (w == w_first) mask &= 0xFFFFFFFFu << (a & 31u);
-                if (w == w_last) mask &= 0xFFFFFFFFu >> (31u - (uint32_t)((b - 1) & 31u));
+                const uint32_t mask = range_word_mask(w, w_first, w_last, a, b);
                 clean += (uint32_t)__popc(clean_bits[w] & mask);
                 found += (uint32_t)__popc(found_bits[w] & mask);
             }
@@ -266,15 +174,13 @@ extern "C" hipError_t tbk_launch_query_directory(const uint64_t *d_keys, uint64_
     return hipGetLastError();
 }
 
-// bitmaps: 64 words per pass each; d_bytes (NULL: not asked for): TBK_PASS bytes per pass; d_copies may be NULL
-extern "C" hipError_t tbk_launch_query_lookup(const uint8_t *d_sep, uint64_t total, uint64_t n_passes, int k, const uint64_t *d_keys,
-                                              const uint8_t *d_counts, const uint32_t *d_dir, uint64_t n, int prefix_bits, uint32_t min_count,
+// (what the arguments of this and the following launchers hold: tbk_lookup_host.h)
+extern "C" hipError_t tbk_launch_query_lookup(const uint8_t *d_sep, uint64_t total, uint64_t n_passes, int k, TbkDbView db, uint32_t min_count,
                                               uint32_t *d_clean, uint32_t *d_found, uint8_t *d_bytes, unsigned long long *d_hist, uint32_t *d_seen,
                                               uint32_t *d_copies, uint64_t wave_slots, hipStream_t stream) {
     if (!n_passes) return hipSuccess;
-    if (k < 1 || k > 32 || prefix_bits < 0 || prefix_bits > 2 * k || n > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (!tbk_db_view_ok(db, k)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n_passes, wave_slots))), block(64);
-    const TbkQueryDb db{d_keys, d_counts, d_dir, (uint32_t)n, prefix_bits};
 #define TBK_QUERY_LAUNCH(B, C) hipLaunchKernelGGL((tbk_query_lookup_kernel<B, C>), grid, block, 0, stream, d_sep, total, n_passes, k, db, min_count, d_clean, d_found, d_bytes, d_hist, d_seen, d_copies)
     if (d_bytes && d_copies) TBK_QUERY_LAUNCH(true, true);
     else if (d_bytes) TBK_QUERY_LAUNCH(true, false);
@@ -302,7 +208,6 @@ extern "C" hipError_t tbk_launch_query_counts(const uint8_t *d_bytes, const uint
 
 static unsigned query_tile_blocks(uint64_t n) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + TBK_Q_TILE - 1) / TBK_Q_TILE, 2048)); }
 
-// d_out: 2 sums, zeroed by the caller (seen and solid, solid)
 extern "C" hipError_t tbk_launch_query_completeness(const uint8_t *d_counts, const uint32_t *d_seen, uint64_t n, uint32_t ci, uint32_t cx,
                                                     unsigned long long *d_out, hipStream_t stream) {
     if (!n) return hipSuccess;
@@ -311,7 +216,6 @@ extern "C" hipError_t tbk_launch_query_completeness(const uint8_t *d_counts, con
     return hipGetLastError();
 }
 
-// d_spec: 6 x 256 sums, zeroed by the caller
 extern "C" hipError_t tbk_launch_query_spectrum(const uint8_t *d_counts, const uint32_t *d_copies, uint64_t n, unsigned long long *d_spec,
                                                 hipStream_t stream) {
     if (!n) return hipSuccess;

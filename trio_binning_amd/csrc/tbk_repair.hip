@@ -11,127 +11,35 @@
 #include "../../include/tbk.h"
 #include "tbk_common.h"
 #include "tbk_compact.h"
-#include "tbk_device.h"
+#include "tbk_lookup.h"
 
-// What the kernels read of a session (tbk_query.hip's TbkQueryDb)
-struct TbkRepairDb {
-    const uint64_t *keys;
-    const uint8_t *counts;
-    const uint32_t *dir;
-    uint32_t n;
-    int prefix_bits;
-};
-
-constexpr int TBK_R_GROUP = 4;  // windows of a lane whose searches are in flight together, as in tbk_depth.hip
-
-// One wave per pass of TBK_PASS window starts of the separated stream, staged and rolled as tbk_depth_lookup_kernel does
-// it: lane l holds the 64 bases from P0 + 32 l on and rolls its 32 windows out of registers, TBK_R_GROUP at a time, every
-// step of a group's searches issued for all of its windows before any answer is used; a lane whose search is over reads
-// entry 0 again.  What is left is one bit per stream position in each of two bitmaps, 64 words per pass: clean, and
+// One wave per pass of TBK_PASS window starts of the separated stream: staging, roll and the grouped search are lookup_pass's
+// (tbk_lookup.h).  What is left is one bit per stream position in each of two bitmaps, 64 words per pass: clean, and
 // broken - clean with c < m.  No atomic, nothing of the session written.
 __global__ void __launch_bounds__(64)
-tbk_repair_lookup_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_t n_passes, int k, TbkRepairDb db, uint32_t m,
+tbk_repair_lookup_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_t n_passes, int k, TbkDbView db, uint32_t m,
                          uint32_t *__restrict__ clean, uint32_t *__restrict__ broken) {
     __shared__ uint64_t stage[TBK_CHUNKS + 2];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    const uint32_t badk = k == 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);
-    const int shift = 2 * k - db.prefix_bits;  // (64 only when prefix_bits is 0: not used then)
     for (uint64_t pass = blockIdx.x; pass < n_passes; pass += gridDim.x) {
-        const uint64_t P0 = pass * TBK_PASS;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        stage[lane] = load_chunk(sep, P0 + (uint64_t)lane * 16, total);
-        stage[64 + lane] = load_chunk(sep, P0 + (uint64_t)(64 + lane) * 16, total);
-        if (lane < 2) stage[128 + lane] = load_chunk(sep, P0 + (uint64_t)(128 + lane) * 16, total);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const uint64_t e0 = stage[2 * lane], e1 = stage[2 * lane + 1], e2 = stage[2 * lane + 2], e3 = stage[2 * lane + 3];
-        uint32_t s0 = (uint32_t)e0, s1 = (uint32_t)e1, s2 = (uint32_t)e2, s3 = (uint32_t)e3;
-        const unsigned __int128 R128 = (unsigned __int128)rev_pairs(~s3) | ((unsigned __int128)rev_pairs(~s2) << 32) |
-                                       ((unsigned __int128)rev_pairs(~s1) << 64) | ((unsigned __int128)rev_pairs(~s0) << 96);
-        const unsigned __int128 Rs = R128 >> (64 - 2 * k);
-        uint32_t t0 = (uint32_t)Rs, t1 = (uint32_t)(Rs >> 32), t2 = (uint32_t)(Rs >> 64), t3 = (uint32_t)(Rs >> 96);
-        uint32_t bad_lo = (uint32_t)(e0 >> 32) | ((uint32_t)(e1 >> 32) << 16);
-        uint32_t bad_hi = (uint32_t)(e2 >> 32) | ((uint32_t)(e3 >> 32) << 16);
-        const uint64_t p_lane = P0 + (uint64_t)lane * TBK_WPL;
         uint32_t w_clean = 0, w_broken = 0;
-#pragma unroll 1
-        for (int j0 = 0; j0 < TBK_WPL; j0 += TBK_R_GROUP) {
-            uint64_t rank[TBK_R_GROUP];
-            uint32_t lo[TBK_R_GROUP], hi[TBK_R_GROUP];
-            bool ok[TBK_R_GROUP], hit[TBK_R_GROUP];
+        lookup_pass(stage, sep, total, pass, k, db, [&](int j0, const LookupGroup &w) {
 #pragma unroll
-            for (int g = 0; g < TBK_R_GROUP; g++) {
-                const uint64_t fwd = ((uint64_t)s0 | ((uint64_t)s1 << 32)) & kmask;
-                const uint64_t rc = ((uint64_t)t2 | ((uint64_t)t3 << 32)) & kmask;
-                rank[g] = lex_rank(fwd < rc ? fwd : rc, k);
-                ok[g] = (bad_lo & badk) == 0 && p_lane + (uint64_t)(j0 + g) + (uint64_t)k <= total;
-                s0 = (s0 >> 2) | (s1 << 30); s1 = (s1 >> 2) | (s2 << 30); s2 = (s2 >> 2) | (s3 << 30); s3 >>= 2;
-                t3 = (t3 << 2) | (t2 >> 30); t2 = (t2 << 2) | (t1 >> 30); t1 = (t1 << 2) | (t0 >> 30); t0 <<= 2;
-                bad_lo = (bad_lo >> 1) | (bad_hi << 31); bad_hi >>= 1;
+            for (int g = 0; g < TBK_GROUP; g++) {
+                const uint32_t bit = 1u << (j0 + g);
+                if (w.ok[g]) w_clean |= bit;
+                if (w.ok[g] && w.c[g] < m) w_broken |= bit;
             }
-#pragma unroll
-            for (int g = 0; g < TBK_R_GROUP; g++) {
-                const uint64_t p = ok[g] && db.prefix_bits ? rank[g] >> shift : 0;
-                lo[g] = db.dir[p];
-                hi[g] = db.dir[p + 1];
-            }
-#pragma unroll
-            for (int g = 0; g < TBK_R_GROUP; g++) {
-                if (!ok[g]) hi[g] = lo[g];
-                hit[g] = false;
-            }
-            for (;;) {
-                bool more = false;
-#pragma unroll
-                for (int g = 0; g < TBK_R_GROUP; g++) more = more || lo[g] < hi[g];
-                if (!more) break;
-                uint64_t v[TBK_R_GROUP];
-                uint32_t mid[TBK_R_GROUP];
-#pragma unroll
-                for (int g = 0; g < TBK_R_GROUP; g++) {
-                    mid[g] = lo[g] + (hi[g] - lo[g]) / 2;
-                    v[g] = db.keys[lo[g] < hi[g] ? mid[g] : 0];
-                }
-#pragma unroll
-                for (int g = 0; g < TBK_R_GROUP; g++) {
-                    if (lo[g] < hi[g]) {
-                        if (v[g] == rank[g]) { hit[g] = true; lo[g] = hi[g] = mid[g]; }
-                        else if (v[g] < rank[g]) lo[g] = mid[g] + 1;
-                        else hi[g] = mid[g];
-                    }
-                }
-            }
-            uint32_t c[TBK_R_GROUP];
-#pragma unroll
-            for (int g = 0; g < TBK_R_GROUP; g++) c[g] = db.counts[hit[g] ? lo[g] : 0];
-#pragma unroll
-            for (int g = 0; g < TBK_R_GROUP; g++) {
-                const uint32_t cg = hit[g] ? c[g] : 0, bit = 1u << (j0 + g);
-                if (ok[g]) w_clean |= bit;
-                if (ok[g] && cg < m) w_broken |= bit;
-            }
-        }
+        });
         clean[pass * 64 + lane] = w_clean;
         broken[pass * 64 + lane] = w_broken;
     }
 }
-static_assert(TBK_WPL % TBK_R_GROUP == 0, "a lane's windows are whole groups");
 
 // ---- the stretches: flag the heads, scan (the host), scatter them into records ------------------------------------------------
 // Bit p of the broken bitmap, read as 64-bit words, is stream position p.  The separator behind every sequence is never clean,
 // so a run of broken bits lies inside one sequence.
 __device__ __forceinline__ bool repair_bit(const uint64_t *__restrict__ bits, uint64_t p) { return (bits[p >> 6] >> (p & 63u)) & 1ull; }
-
-// The read of stream position p (never a separator's), as the hit tracker's run heads find it: the last r with
-// offsets[r] + r <= p - offsets[r] + r rises strictly, so empty reads are stepped over.
-__device__ __forceinline__ uint64_t repair_read_of(const uint64_t *__restrict__ offsets, uint64_t n_reads, uint64_t p) {
-    uint64_t lo = 0, hi = n_reads;  // first r with offsets[r] + r > p
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (offsets[mid] + mid <= p) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1;
-}
 
 // A broken position whose predecessor is not broken is a stretch's head; n = 2048 positions per pass.
 __global__ void __launch_bounds__(256)
@@ -152,7 +60,7 @@ tbk_repair_stretches_kernel(const uint64_t *__restrict__ broken, uint64_t n, con
         uint64_t open = ~broken[word] & (~0ull << (p & 63u));  // the positions from p on that are not broken
         while (!open && (word + 1) * 64 < n) open = ~broken[++word];
         const uint64_t end = open ? word * 64 + (uint64_t)__builtin_ctzll(open) : n;  // one past the stretch's last window
-        const uint64_t read = repair_read_of(offsets, n_reads, p);
+        const uint64_t read = read_of_position(offsets, n_reads, p);
         const uint64_t r = end - p;
         records[5 * at] = read;
         records[5 * at + 1] = p - (offsets[read] + read);
@@ -186,18 +94,17 @@ __device__ __forceinline__ uint64_t repair_spread(uint32_t x) {
 // three 128-bit planes that every lane holds: the two bits of the code and the not-ACGT mask, bit i = base lo + i.
 // The work items (candidate, one of k window starts of the edited sequence) are laid flat over the lanes, 64 a step: a lane
 // edits the planes by masks and shifts, cuts its window out of them, interleaves the two code planes into the
-// reverse complement's rank and takes the forward rank from that, reads the two directory offsets and bisects - one load per
-// step for all 64 lanes, a finished or idle lane reading entry 0.  A left-aligned duplicate, a window past the ends and a
+// reverse complement's rank and takes the forward rank from that, and searches it (db_search_group at width 1, the loop's
+// branch the wave's: one load per step for all 64 lanes, a finished or idle lane reading entry 0).  A left-aligned duplicate, a window past the ends and a
 // window that is not clean tally nothing.  The verdicts are gathered per candidate in LDS - support in the low byte, the
 // windows below m above it, and the smallest counter - and reduced across the wave; lane 0 stores the record.
 __global__ void __launch_bounds__(64)
-tbk_repair_kernel(const uint8_t *__restrict__ sep, const uint64_t *__restrict__ offsets, int k, TbkRepairDb db, uint32_t m, uint32_t min_support,
+tbk_repair_kernel(const uint8_t *__restrict__ sep, const uint64_t *__restrict__ offsets, int k, TbkDbView db, uint32_t m, uint32_t min_support,
                   uint64_t *__restrict__ records, uint64_t n_records) {
     __shared__ uint32_t tally[TBK_R_CANDS], depth[TBK_R_CANDS];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t km = k == 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);
     const uint64_t kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    const int shift = 2 * k - db.prefix_bits;  // (64 only when prefix_bits is 0: not used then)
     const uint32_t uk = (uint32_t)k;
     for (uint64_t g = blockIdx.x; g < n_records; g += gridDim.x) {
         const uint64_t read = records[5 * g], f = records[5 * g + 1];
@@ -280,25 +187,14 @@ tbk_repair_kernel(const uint8_t *__restrict__ sep, const uint64_t *__restrict__ 
             const bool ok = valid && ((uint32_t)(xb >> j) & km) == 0;
             const uint64_t rc = repair_spread(~a0 & km) | (repair_spread(~a1 & km) << 1);  // the reverse complement's rank: 3 - code i at bits 2 i
             const uint64_t fwd = lex_rank(~rc & kmask, k);                                // the window's own: code i at bits 2 (k - 1 - i)
-            const uint64_t rank = fwd < rc ? fwd : rc;
-            const uint64_t pre = ok && db.prefix_bits ? rank >> shift : 0;
-            uint32_t s_lo = db.dir[pre], s_hi = db.dir[pre + 1];
-            if (!ok) s_hi = s_lo;
-            bool hit = false;
-            while (__builtin_amdgcn_ballot_w64(s_lo < s_hi)) {
-                const uint32_t mid = s_lo + (s_hi - s_lo) / 2;
-                const uint64_t v = db.keys[s_lo < s_hi ? mid : 0];
-                if (s_lo < s_hi) {
-                    if (v == rank) { hit = true; s_lo = s_hi = mid; }
-                    else if (v < rank) s_lo = mid + 1;
-                    else s_hi = mid;
-                }
-            }
-            const uint32_t c = db.counts[hit ? s_lo : 0];
+            const uint64_t rank[1] = {fwd < rc ? fwd : rc};
+            const bool oks[1] = {ok};
+            uint32_t entry[1], cw[1];
+            bool hit[1];
+            db_search_group<1, true>(db, k, rank, oks, entry, hit, cw);  // (every lane of the wave is here)
             if (ok) {
-                const uint32_t cw = hit ? c : 0u;
-                atomicAdd(&tally[cand], cw >= m ? 1u : 257u);
-                atomicMin(&depth[cand], cw);
+                atomicAdd(&tally[cand], cw[0] >= m ? 1u : 257u);
+                atomicMin(&depth[cand], cw[0]);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -341,28 +237,23 @@ static_assert(sizeof(tbk_repair) == 40, "a record is five 64-bit words: read, fi
 static_assert(8 * 32 - 4 <= TBK_R_CANDS, "the candidates of a stretch have a row each");
 
 // =======================================================================================
-// launchers (called from tbk_count.cpp)
+// launchers (called from tbk_count.cpp; what the arguments hold: tbk_lookup_host.h)
 // =======================================================================================
-// bitmaps: 64 words per pass each; m: the threshold, 1..255
-extern "C" hipError_t tbk_launch_repair_lookup(const uint8_t *d_sep, uint64_t total, uint64_t n_passes, int k, const uint64_t *d_keys,
-                                               const uint8_t *d_counts, const uint32_t *d_dir, uint64_t n, int prefix_bits, uint32_t m,
+extern "C" hipError_t tbk_launch_repair_lookup(const uint8_t *d_sep, uint64_t total, uint64_t n_passes, int k, TbkDbView db, uint32_t m,
                                                uint32_t *d_clean, uint32_t *d_broken, uint64_t wave_slots, hipStream_t stream) {
     if (!n_passes) return hipSuccess;
-    if (k < 1 || k > 32 || prefix_bits < 0 || prefix_bits > 2 * k || n > 0xFFFFFFFFull || m < 1 || m > 255) return hipErrorInvalidValue;
+    if (!tbk_db_view_ok(db, k) || m < 1 || m > 255) return hipErrorInvalidValue;
     const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n_passes, wave_slots))), block(64);
-    const TbkRepairDb db{d_keys, d_counts, d_dir, (uint32_t)n, prefix_bits};
     hipLaunchKernelGGL(tbk_repair_lookup_kernel, grid, block, 0, stream, d_sep, total, n_passes, k, db, m, d_clean, d_broken);
     return hipGetLastError();
 }
 
-// the heads among the n_passes * 2048 stream positions of d_broken: d_flags and d_tile_counts as Compaction holds them for that many
 extern "C" hipError_t tbk_launch_repair_heads(const uint32_t *d_broken, uint64_t n_passes, uint64_t *d_flags, unsigned long long *d_tile_counts,
                                               hipStream_t stream) {
     return compact_launch_tiles(n_passes * TBK_PASS, stream, tbk_repair_heads_kernel, reinterpret_cast<const uint64_t *>(d_broken), n_passes * TBK_PASS,
                                 d_flags, d_tile_counts);
 }
 
-// d_records: n_records x 40 bytes, read, first and windows of every stretch, in order
 extern "C" hipError_t tbk_launch_repair_stretches(const uint32_t *d_broken, uint64_t n_passes, const uint64_t *d_offsets, uint64_t n_reads,
                                                   const uint64_t *d_flags, const unsigned long long *d_tile_offsets, tbk_repair *d_records,
                                                   uint64_t n_records, hipStream_t stream) {
@@ -372,15 +263,11 @@ extern "C" hipError_t tbk_launch_repair_stretches(const uint32_t *d_broken, uint
                                 n_passes * TBK_PASS, d_offsets, n_reads, d_flags, d_tile_offsets, reinterpret_cast<uint64_t *>(d_records), n_records);
 }
 
-// the records completed in place
-extern "C" hipError_t tbk_launch_repair(const uint8_t *d_sep, const uint64_t *d_offsets, int k, const uint64_t *d_keys, const uint8_t *d_counts,
-                                        const uint32_t *d_dir, uint64_t n, int prefix_bits, uint32_t m, uint32_t min_support, tbk_repair *d_records,
-                                        uint64_t n_records, uint64_t wave_slots, hipStream_t stream) {
+extern "C" hipError_t tbk_launch_repair(const uint8_t *d_sep, const uint64_t *d_offsets, int k, TbkDbView db, uint32_t m, uint32_t min_support,
+                                        tbk_repair *d_records, uint64_t n_records, uint64_t wave_slots, hipStream_t stream) {
     if (!n_records) return hipSuccess;
-    if (k < 1 || k > 32 || prefix_bits < 0 || prefix_bits > 2 * k || n > 0xFFFFFFFFull || m < 1 || m > 255 || min_support < 1 || min_support > 32)
-        return hipErrorInvalidValue;
+    if (!tbk_db_view_ok(db, k) || m < 1 || m > 255 || min_support < 1 || min_support > 32) return hipErrorInvalidValue;
     const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n_records, wave_slots))), block(64);
-    const TbkRepairDb db{d_keys, d_counts, d_dir, (uint32_t)n, prefix_bits};
     hipLaunchKernelGGL(tbk_repair_kernel, grid, block, 0, stream, d_sep, d_offsets, k, db, m, min_support, reinterpret_cast<uint64_t *>(d_records),
                        n_records);
     return hipGetLastError();

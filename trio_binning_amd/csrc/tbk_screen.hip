@@ -9,111 +9,30 @@
 
 #include "../../include/tbk.h"
 #include "tbk_common.h"
-#include "tbk_device.h"
+#include "tbk_lookup.h"
 
-// What the kernels read of a session (tbk_query.hip's TbkQueryDb)
-struct TbkScreenDb {
-    const uint64_t *keys;
-    const uint8_t *counts;
-    const uint32_t *dir;
-    uint32_t n;
-    int prefix_bits;
-};
-
-constexpr int TBK_S_GROUP = 4;  // windows of a lane whose searches are in flight together, as in tbk_repair.hip
-
-// One wave per pass of TBK_PASS window starts of the separated stream, staged and rolled as tbk_repair_lookup_kernel does
-// it: lane l holds the 64 bases from P0 + 32 l on and rolls its 32 windows out of registers, TBK_S_GROUP at a time, every
-// step of a group's searches issued for all of its windows before any answer is used; a lane whose search is over reads
-// entry 0 again.  What is left is one bit per stream position in each of two bitmaps, 64 words per pass: clean, and
+// One wave per pass of TBK_PASS window starts of the separated stream: staging, roll and the grouped search are lookup_pass's
+// (tbk_lookup.h).  What is left is one bit per stream position in each of two bitmaps, 64 words per pass: clean, and
 // held - clean with c_lo <= c <= c_hi (c_lo > c_hi: nothing is held).  No atomic, nothing of the session written.
 __global__ void __launch_bounds__(64)
-tbk_screen_lookup_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_t n_passes, int k, TbkScreenDb db, uint32_t c_lo, uint32_t c_hi,
+tbk_screen_lookup_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_t n_passes, int k, TbkDbView db, uint32_t c_lo, uint32_t c_hi,
                          uint32_t *__restrict__ clean, uint32_t *__restrict__ held) {
     __shared__ uint64_t stage[TBK_CHUNKS + 2];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    const uint32_t badk = k == 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);
-    const int shift = 2 * k - db.prefix_bits;  // (64 only when prefix_bits is 0: not used then)
     for (uint64_t pass = blockIdx.x; pass < n_passes; pass += gridDim.x) {
-        const uint64_t P0 = pass * TBK_PASS;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        stage[lane] = load_chunk(sep, P0 + (uint64_t)lane * 16, total);
-        stage[64 + lane] = load_chunk(sep, P0 + (uint64_t)(64 + lane) * 16, total);
-        if (lane < 2) stage[128 + lane] = load_chunk(sep, P0 + (uint64_t)(128 + lane) * 16, total);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const uint64_t e0 = stage[2 * lane], e1 = stage[2 * lane + 1], e2 = stage[2 * lane + 2], e3 = stage[2 * lane + 3];
-        uint32_t s0 = (uint32_t)e0, s1 = (uint32_t)e1, s2 = (uint32_t)e2, s3 = (uint32_t)e3;
-        const unsigned __int128 R128 = (unsigned __int128)rev_pairs(~s3) | ((unsigned __int128)rev_pairs(~s2) << 32) |
-                                       ((unsigned __int128)rev_pairs(~s1) << 64) | ((unsigned __int128)rev_pairs(~s0) << 96);
-        const unsigned __int128 Rs = R128 >> (64 - 2 * k);
-        uint32_t t0 = (uint32_t)Rs, t1 = (uint32_t)(Rs >> 32), t2 = (uint32_t)(Rs >> 64), t3 = (uint32_t)(Rs >> 96);
-        uint32_t bad_lo = (uint32_t)(e0 >> 32) | ((uint32_t)(e1 >> 32) << 16);
-        uint32_t bad_hi = (uint32_t)(e2 >> 32) | ((uint32_t)(e3 >> 32) << 16);
-        const uint64_t p_lane = P0 + (uint64_t)lane * TBK_WPL;
         uint32_t w_clean = 0, w_held = 0;
-#pragma unroll 1
-        for (int j0 = 0; j0 < TBK_WPL; j0 += TBK_S_GROUP) {
-            uint64_t rank[TBK_S_GROUP];
-            uint32_t lo[TBK_S_GROUP], hi[TBK_S_GROUP];
-            bool ok[TBK_S_GROUP], hit[TBK_S_GROUP];
+        lookup_pass(stage, sep, total, pass, k, db, [&](int j0, const LookupGroup &w) {
 #pragma unroll
-            for (int g = 0; g < TBK_S_GROUP; g++) {
-                const uint64_t fwd = ((uint64_t)s0 | ((uint64_t)s1 << 32)) & kmask;
-                const uint64_t rc = ((uint64_t)t2 | ((uint64_t)t3 << 32)) & kmask;
-                rank[g] = lex_rank(fwd < rc ? fwd : rc, k);
-                ok[g] = (bad_lo & badk) == 0 && p_lane + (uint64_t)(j0 + g) + (uint64_t)k <= total;
-                s0 = (s0 >> 2) | (s1 << 30); s1 = (s1 >> 2) | (s2 << 30); s2 = (s2 >> 2) | (s3 << 30); s3 >>= 2;
-                t3 = (t3 << 2) | (t2 >> 30); t2 = (t2 << 2) | (t1 >> 30); t1 = (t1 << 2) | (t0 >> 30); t0 <<= 2;
-                bad_lo = (bad_lo >> 1) | (bad_hi << 31); bad_hi >>= 1;
+            for (int g = 0; g < TBK_GROUP; g++) {
+                const uint32_t bit = 1u << (j0 + g);
+                if (w.ok[g]) w_clean |= bit;
+                if (w.ok[g] && w.c[g] >= c_lo && w.c[g] <= c_hi) w_held |= bit;
             }
-#pragma unroll
-            for (int g = 0; g < TBK_S_GROUP; g++) {
-                const uint64_t p = ok[g] && db.prefix_bits ? rank[g] >> shift : 0;
-                lo[g] = db.dir[p];
-                hi[g] = db.dir[p + 1];
-            }
-#pragma unroll
-            for (int g = 0; g < TBK_S_GROUP; g++) {
-                if (!ok[g]) hi[g] = lo[g];
-                hit[g] = false;
-            }
-            for (;;) {
-                bool more = false;
-#pragma unroll
-                for (int g = 0; g < TBK_S_GROUP; g++) more = more || lo[g] < hi[g];
-                if (!more) break;
-                uint64_t v[TBK_S_GROUP];
-                uint32_t mid[TBK_S_GROUP];
-#pragma unroll
-                for (int g = 0; g < TBK_S_GROUP; g++) {
-                    mid[g] = lo[g] + (hi[g] - lo[g]) / 2;
-                    v[g] = db.keys[lo[g] < hi[g] ? mid[g] : 0];
-                }
-#pragma unroll
-                for (int g = 0; g < TBK_S_GROUP; g++) {
-                    if (lo[g] < hi[g]) {
-                        if (v[g] == rank[g]) { hit[g] = true; lo[g] = hi[g] = mid[g]; }
-                        else if (v[g] < rank[g]) lo[g] = mid[g] + 1;
-                        else hi[g] = mid[g];
-                    }
-                }
-            }
-            uint32_t c[TBK_S_GROUP];
-#pragma unroll
-            for (int g = 0; g < TBK_S_GROUP; g++) c[g] = db.counts[hit[g] ? lo[g] : 0];
-#pragma unroll
-            for (int g = 0; g < TBK_S_GROUP; g++) {
-                const uint32_t cg = hit[g] ? c[g] : 0, bit = 1u << (j0 + g);
-                if (ok[g]) w_clean |= bit;
-                if (ok[g] && cg >= c_lo && cg <= c_hi) w_held |= bit;
-            }
-        }
+        });
         clean[pass * 64 + lane] = w_clean;
         held[pass * 64 + lane] = w_held;
     }
 }
-static_assert(TBK_WPL % TBK_S_GROUP == 0, "a lane's windows are whole groups");
 
 // ---- the evidence: one record per sequence from the two bitmaps ----------------------------------------------------------------
 // The covered positions of a stretch of positions as a segment of a segmented max-run: the run of covered positions it begins
@@ -133,7 +52,7 @@ __device__ __forceinline__ ScreenRuns screen_join(const ScreenRuns &a, const Scr
 }
 
 // Sequence r lies at stream positions [a, b) = [offsets[r] + r, offsets[r + 1] + r), as tbk_query_totals_kernel reads it: its
-// clean and its held windows are the set bits of the two bitmaps there, and the edge words are masked as that kernel masks them.
+// clean and its held windows are the set bits of the two bitmaps there, and the edge words are masked (range_word_mask).
 // The COVERED bitmap is the held one dilated by k - 1 positions upward: k <= 32, so a 32-bit word needs only its predecessor as
 // halo, and the dilation is floor(log2 k) + 1 shift-and-ors of the two words side by side in one 64-bit register.  A held window starts at L - k
 // at most, so the dilation ends at the sequence's last base, b - 1: the covered words need no mask of their own and the word
@@ -158,15 +77,12 @@ tbk_screen_evidence_kernel(const uint32_t *__restrict__ clean_bits, const uint32
         unsigned long long trail = 0, best = 0;  // the words of the trips so far, joined: the run they end with and their longest
         if (b > a) {  // (the same in every lane)
             const uint64_t w_first = a >> 5, w_last = (b - 1) >> 5;
-            const uint32_t m_first = 0xFFFFFFFFu << (a & 31u), m_last = 0xFFFFFFFFu >> (31u - (uint32_t)((b - 1) & 31u));
             for (uint64_t w0 = w_first; w0 <= w_last; w0 += 64) {
                 const uint64_t w = w0 + lane;
                 const bool mine = w <= w_last, halo = mine && w > w_first;
                 const uint64_t at = mine ? w : w_last, below = halo ? w - 1 : w_first;  // (no load under a branch: an idle lane reads a word of the sequence)
-                uint32_t mask = mine ? 0xFFFFFFFFu : 0u, mask_below = halo ? 0xFFFFFFFFu : 0u;
-                if (w == w_first) mask &= m_first;
-                if (w == w_last) mask &= m_last;
-                if (below == w_first) mask_below &= m_first;  // (below < w_last)
+                const uint32_t mask = mine ? range_word_mask(w, w_first, w_last, a, b) : 0u;
+                const uint32_t mask_below = halo ? range_word_mask(below, w_first, w_last, a, b) : 0u;
                 const uint32_t c = clean_bits[at] & mask, h = held_bits[at] & mask, hb = held_bits[below] & mask_below;
                 uint64_t x = ((uint64_t)h << 32) | hb;  // shifts 0 .. n - 1 of the held bits so far; n doubles up to k
                 int n = 1;
@@ -220,19 +136,17 @@ static_assert(sizeof(tbk_read_evidence) == 40, "a record is five 64-bit words: c
 // =======================================================================================
 // launchers (called from tbk_count.cpp)
 // =======================================================================================
-// bitmaps: 64 words per pass each; [c_lo, c_hi]: the counters that hold a window, c_lo >= 1; empty when c_lo > c_hi
-extern "C" hipError_t tbk_launch_screen_lookup(const uint8_t *d_sep, uint64_t total, uint64_t n_passes, int k, const uint64_t *d_keys,
-                                               const uint8_t *d_counts, const uint32_t *d_dir, uint64_t n, int prefix_bits, uint32_t c_lo, uint32_t c_hi,
+// (what the arguments hold: tbk_lookup_host.h)
+extern "C" hipError_t tbk_launch_screen_lookup(const uint8_t *d_sep, uint64_t total, uint64_t n_passes, int k, TbkDbView db, uint32_t c_lo, uint32_t c_hi,
                                                uint32_t *d_clean, uint32_t *d_held, uint64_t wave_slots, hipStream_t stream) {
     if (!n_passes) return hipSuccess;
-    if (k < 1 || k > 32 || prefix_bits < 0 || prefix_bits > 2 * k || n > 0xFFFFFFFFull || c_lo < 1 || c_lo > 255 || c_hi > 255) return hipErrorInvalidValue;
+    if (!tbk_db_view_ok(db, k) || c_lo < 1 || c_lo > 255 || c_hi > 255) return hipErrorInvalidValue;
     const dim3 grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n_passes, wave_slots))), block(64);
-    const TbkScreenDb db{d_keys, d_counts, d_dir, (uint32_t)n, prefix_bits};
     hipLaunchKernelGGL(tbk_screen_lookup_kernel, grid, block, 0, stream, d_sep, total, n_passes, k, db, c_lo, c_hi, d_clean, d_held);
     return hipGetLastError();
 }
 
-// d_records: n_reads x 40 bytes.  Four sequences to a block: the grid-stride loop takes a second trip from 4 wave_slots + 1 sequences on.
+// Four sequences to a block: the grid-stride loop takes a second trip from 4 wave_slots + 1 sequences on.
 extern "C" hipError_t tbk_launch_screen_evidence(const uint32_t *d_clean, const uint32_t *d_held, const uint64_t *d_offsets, uint64_t n_reads, int k,
                                                  tbk_read_evidence *d_records, uint64_t wave_slots, hipStream_t stream) {
     if (!n_reads) return hipSuccess;

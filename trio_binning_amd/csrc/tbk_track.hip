@@ -8,7 +8,7 @@
 
 #include "../../include/tbk.h"
 #include "tbk_common.h"
-#include "tbk_device.h"
+#include "tbk_lookup.h"
 
 // tbk_separate_kernel (tbk_count_kernels.hip) with the upper-casing as a switch: every read is followed by one 'N',
 // so no window spans two reads and validity is the not-ACGT mask alone.  With ignore_case, clearing bit 5 turns
@@ -45,9 +45,9 @@ __device__ __forceinline__ bool track_lookup(const uint64_t *__restrict__ slots,
     return false;
 }
 
-// One wave per pass of TBK_PASS window starts of the separated stream, staged and rolled like tbk_count_kernel's:
-// lane l holds the 64 bases from P0 + 32 l on and rolls its 32 windows out of registers.  A clean window asks A's
-// table, and B's only if A missed (count_kmers_in_read, c/kmers.c:291-294): two dependent random lines at the most.
+// One wave per pass of TBK_PASS window starts of the separated stream, staged and rolled by LaneWindows (tbk_lookup.h):
+// lane l holds the 64 bases from P0 + 32 l on and rolls its 32 windows out of registers.  A clean window asks A's table,
+// and B's only if A missed (count_kmers_in_read, c/kmers.c:291-294): two dependent random lines at the most.
 // The lane's answers are one word of A-bits and one of B-bits - bit j = the window at P0 + 32 l + j - so the two
 // bitmaps are indexed by stream position, a wave writes 256 contiguous bytes of each, and windows over a separator
 // or past `total` are clear because the 'N' (or the zero load_chunk reads past the end) is in them.  pass_count gets
@@ -58,37 +58,19 @@ tbk_track_mark_kernel(const uint8_t *__restrict__ sep, uint64_t total, uint64_t 
                       uint32_t *__restrict__ bits_b, unsigned long long *__restrict__ pass_count) {
     __shared__ uint64_t stage[TBK_CHUNKS + 2];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    const uint32_t badk = k == 32 ? 0xFFFFFFFFu : ((1u << k) - 1u);
+    LaneWindows win(k);
     for (uint64_t pass = blockIdx.x; pass < n_passes; pass += gridDim.x) {
         const uint64_t P0 = pass * TBK_PASS;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        stage[lane] = load_chunk(sep, P0 + (uint64_t)lane * 16, total);
-        stage[64 + lane] = load_chunk(sep, P0 + (uint64_t)(64 + lane) * 16, total);
-        if (lane < 2) stage[128 + lane] = load_chunk(sep, P0 + (uint64_t)(128 + lane) * 16, total);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const uint64_t e0 = stage[2 * lane], e1 = stage[2 * lane + 1], e2 = stage[2 * lane + 2], e3 = stage[2 * lane + 3];
-        uint32_t s0 = (uint32_t)e0, s1 = (uint32_t)e1, s2 = (uint32_t)e2, s3 = (uint32_t)e3;
-        const unsigned __int128 R128 = (unsigned __int128)rev_pairs(~s3) | ((unsigned __int128)rev_pairs(~s2) << 32) |
-                                       ((unsigned __int128)rev_pairs(~s1) << 64) | ((unsigned __int128)rev_pairs(~s0) << 96);
-        const unsigned __int128 Rs = R128 >> (64 - 2 * k);
-        uint32_t t0 = (uint32_t)Rs, t1 = (uint32_t)(Rs >> 32), t2 = (uint32_t)(Rs >> 64), t3 = (uint32_t)(Rs >> 96);
-        uint32_t bad_lo = (uint32_t)(e0 >> 32) | ((uint32_t)(e1 >> 32) << 16);
-        uint32_t bad_hi = (uint32_t)(e2 >> 32) | ((uint32_t)(e3 >> 32) << 16);
+        win.load(stage, sep, P0, total, lane);
         uint32_t word_a = 0, word_b = 0;
 #pragma unroll 2
         for (int j = 0; j < TBK_WPL; j++) {
-            const uint64_t fwd = ((uint64_t)s0 | ((uint64_t)s1 << 32)) & kmask;
-            const uint64_t rc = ((uint64_t)t2 | ((uint64_t)t3 << 32)) & kmask;
-            const uint64_t key = fwd < rc ? fwd : rc;
-            const bool ok = (bad_lo & badk) == 0 && P0 + (uint64_t)lane * TBK_WPL + (uint64_t)j + (uint64_t)k <= total;
-            if (ok) {
+            const uint64_t key = win.key();
+            if (win.clean(P0 + (uint64_t)lane * TBK_WPL + (uint64_t)j, total)) {
                 if (track_lookup(slots_a, buckets_a, key)) word_a |= 1u << j;
                 else if (track_lookup(slots_b, buckets_b, key)) word_b |= 1u << j;
             }
-            s0 = (s0 >> 2) | (s1 << 30); s1 = (s1 >> 2) | (s2 << 30); s2 = (s2 >> 2) | (s3 << 30); s3 >>= 2;
-            t3 = (t3 << 2) | (t2 >> 30); t2 = (t2 << 2) | (t1 >> 30); t1 = (t1 << 2) | (t0 >> 30); t0 <<= 2;
-            bad_lo = (bad_lo >> 1) | (bad_hi << 31); bad_hi >>= 1;
+            win.roll();
         }
         bits_a[pass * 64 + lane] = word_a;
         bits_b[pass * 64 + lane] = word_b;
@@ -146,17 +128,6 @@ tbk_track_markers_kernel(const uint32_t *__restrict__ bits_a, const uint32_t *__
     }
 }
 
-// The read of stream position p (never a separator's): the last r with offsets[r] + r <= p - the separators before
-// read r are r, and offsets[r] + r rises strictly, so empty reads are stepped over.
-__device__ __forceinline__ uint64_t track_read_of(const uint64_t *__restrict__ offsets, uint64_t n_reads, uint64_t p) {
-    uint64_t lo = 0, hi = n_reads;  // first r with offsets[r] + r > p
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (offsets[mid] + mid <= p) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1;
-}
-
 constexpr uint32_t TBK_TRK_TILE = 1024;               // markers per tile of the run stage: 4 rounds of a 256-thread block
 constexpr uint32_t TBK_TRK_WORDS = TBK_TRK_TILE / 64;  // flag words per tile
 
@@ -178,14 +149,14 @@ tbk_track_heads_kernel(const uint64_t *__restrict__ markers, uint64_t n_markers,
         unsigned long long m = 0, read = 0;
         if (i < n_markers) {
             m = markers[i];
-            read = track_read_of(offsets, n_reads, m >> 1);
+            read = read_of_position(offsets, n_reads, m >> 1);
         }
         unsigned long long pm = __shfl_up(m, 1), pread = __shfl_up(read, 1);
         bool head = false;
         if (i < n_markers) {
             if (lane == 0 && i > 0) {
                 pm = markers[i - 1];
-                pread = track_read_of(offsets, n_reads, pm >> 1);
+                pread = read_of_position(offsets, n_reads, pm >> 1);
             }
             head = i == 0 || ((pm ^ m) & 1ull) || pread != read;
         }
@@ -227,7 +198,7 @@ tbk_track_runs_kernel(const uint64_t *__restrict__ markers, uint64_t n_markers, 
             const uint64_t at = base + word_before[word] + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
             if (at < n_runs) {
                 const uint64_t m = markers[i], p = m >> 1;
-                const uint64_t read = track_read_of(offsets, n_reads, p);
+                const uint64_t read = read_of_position(offsets, n_reads, p);
                 tbk_hit_run run;
                 run.read = read;
                 run.first = p - (offsets[read] + read);
