@@ -58,7 +58,8 @@ def test_members_inflate_to_their_text(gpu):
         (b">r\n" + b"ACGT" * 20 + b"\n") * 2000,                          # FASTA, very regular
         b"".join(bytes([65 + (i % 7)]) * (i % 300 + 1) for i in range(2000)),   # runs of every length up to 300
     ]
-    # a geometric frequency profile deep enough that a Huffman tree passes 15 levels (Fibonacci-like counts): the length limit
+    # runs of one byte each, Fibonacci-like in length: the blocks are coded with runs, so what is counted is a literal and a few matches
+    # per run and the trees are 7 and 4 levels deep - no length limit is reached (tests/test_gpu_deflate_limits.py reaches both)
     fib = [1, 1]
     while len(fib) < 24:
         fib.append(fib[-1] + fib[-2])
