@@ -1409,6 +1409,47 @@ typedef struct tbk_read_evidence { uint64_t clean, held, covered, longest, stret
 int tbk_kmerdb_query_evidence(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
                               uint32_t min_count, uint32_t max_count, tbk_read_evidence *out /* n_reads */);
 
+/* ---- read depth: how often did the library see a read's k-mers? --------------------------------------------------- */
+/* A pass over reads that brings home, per sequence, a five-number summary of the counters of its windows: what kat sect,
+ * BBNorm and khmer's normalize-by-median and filter-abund compute before they keep, drop or thin reads.  q is a session
+ * with or without copies, k its database's k, min_count in 1..255.  The lower bound is m = max(floor, min_count), floor 2
+ * for a solid database and 1 for a full one, as the read evidence has it.
+ * WINDOWS AND DEPTHS.  A sequence of length L has nw = max(L - k + 1, 0) window starts.  Clean windows (ACGT only, either
+ * case), canonical k-mers and the counter c are exactly those of tbk_kmerdb_query_add.  The DEPTH d of a clean window is c
+ * when c >= m and 0 otherwise: an absent k-mer and a counter below m both read as depth 0.
+ * PER SEQUENCE:
+ *   clean           clean windows;
+ *   present         clean windows with d >= 1;
+ *   saturated       clean windows with d == 255: the counter stops there, so their true depth is 255 or more;
+ *   sum             the sum of d over the clean windows - the mean depth is sum / clean, and no float is computed anywhere;
+ *   lowest, q1, median, q3, highest
+ *                   with the depths of the clean windows sorted ascending as v[0 .. clean - 1], these are
+ *                   v[floor(j (clean - 1) / 4)] for j = 0 .. 4, the arithmetic in 64-bit integers: the minimum, the lower
+ *                   quartile, the LOWER median (as tbk_depth_bin's depth is per bin), the upper quartile and the maximum;
+ *   present_median  the same rank rule with j = 2 over the present windows only - v'[floor((present - 1) / 2)] of their sorted
+ *                   depths - and 0 when there are none: the read's copy depth when most of its k-mers carry a sequencing
+ *                   error and the median itself is 0;
+ *   pad             two zero bytes.
+ * A sequence without a clean window - an empty one, one shorter than k, one with an N in every window - gets an all-zero
+ * record.
+ * out is host memory, one record per sequence in the batch's order.  TBK_ERR_INVALID, with a message, before anything runs
+ * and with nothing written, for min_count outside 1..255, for a NULL q or out, and for a sequence of 2^32 or more window
+ * starts (the per-read kernel counts a sequence's depths in 32-bit rows); the session stays usable.  n_reads == 0 is valid
+ * and writes nothing.  An empty database is valid: every depth is 0.
+ * The call only reads the session: the histogram, the seen bits, the copies and the window total are as they were, and
+ * the batch does not count towards the limit of 2^32 - 1 window starts.
+ * The call uses the session's batch buffers and grows them as needed.  On the device it takes, per base of the batch
+ * (rounded up to passes of 2048 stream positions, one position more per sequence): the bases and their separated copy
+ * (2 bytes), the depth byte (1 byte) and the clean bitmap (1 bit) - 3.125 bytes, all in buffers that
+ * tbk_kmerdb_query_add grows as well (the depth bytes in the one of its per-base counters) - and 8 bytes per sequence for
+ * the offsets and 40 for its record beside them.  No byte per base comes home. */
+typedef struct tbk_read_depth {
+    uint64_t clean, present, saturated, sum;
+    uint8_t  lowest, q1, median, q3, highest, present_median, pad[2];   /* pad 0 */
+} tbk_read_depth;                                                        /* 40 bytes */
+int tbk_kmerdb_query_read_depth(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets,
+                                uint64_t n_reads, uint32_t min_count, tbk_read_depth *out /* n_reads */);
+
 /* Host threads the library starts for its own host-side work (list parsing, gzip members,
  * scoring): hardware threads limited by the CPU affinity mask and the cgroup CPU quota, divided by the
  * number of ranks the launcher started on this node (LOCAL_WORLD_SIZE, or TBK_LOCAL_RANKS): one process per GPU

@@ -315,6 +315,10 @@ HAS_DB_EVIDENCE = hasattr(lib, "tbk_kmerdb_query_evidence")  # (variant builds m
 if HAS_DB_EVIDENCE:
     _sig("tbk_kmerdb_query_evidence", C.c_int, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, _vp)
     _sig("tbk_kmerdb_query_evidence_times_", C.c_int, _vp, _vp)  # (measuring hook: the last call's two kernel times, ms)
+HAS_DB_READ_DEPTH = hasattr(lib, "tbk_kmerdb_query_read_depth")  # (variant builds may predate the read depth)
+if HAS_DB_READ_DEPTH:
+    _sig("tbk_kmerdb_query_read_depth", C.c_int, _vp, _vp, _vp, _u64, C.c_uint32, _vp)
+    _sig("tbk_kmerdb_query_read_depth_times_", C.c_int, _vp, _vp)  # (measuring hook: the last call's two kernel times, ms)
 
 class DumpOptions(C.Structure):
     """tbk_dump_options (include/tbk.h)."""

@@ -1701,7 +1701,7 @@ extern "C" int tbk_kmerdb_hetmers(const tbk_kmerdb *db, const tbk_hetmer_options
 // Database query (tbk_kmerdb_query; kernels: tbk_query.hip): the counter the database holds for every window of a
 // batch of sequences - per-sequence totals, a histogram, the entries seen, their copies.  include/tbk.h has the rules.
 // =====================================================================================================================
-// (the launchers of its kernel files - tbk_query.hip, tbk_depth.hip, tbk_repair.hip, tbk_screen.hip: tbk_lookup_host.h)
+// (the launchers of its kernel files - tbk_query.hip, tbk_depth.hip, tbk_repair.hip, tbk_screen.hip, tbk_read_depth.hip: tbk_lookup_host.h)
 constexpr uint64_t TBK_QUERY_MAX_WINDOWS = 0xFFFFFFFFull;  // window starts of a session: a 32-bit copy counter cannot wrap
 constexpr int TBK_QUERY_MAX_PREFIX_BITS = 28;              // a directory of at most 1 GiB + 4 bytes
 
@@ -1728,6 +1728,9 @@ struct tbk_kmerdb_query {
     QueryBuf evidence;                                                                     // (the read evidence's records)
     hipEvent_t evidence_marks[3] = {nullptr, nullptr, nullptr};  // around the evidence's two kernels, made by its first call
     double evidence_ms[2] = {0, 0};                              // (tbk_kmerdb_query_evidence_times_)
+    QueryBuf read_depth;                                                                   // (the read depth's records)
+    hipEvent_t read_depth_marks[3] = {nullptr, nullptr, nullptr};  // around the read depth's two kernels, made by its first call
+    double read_depth_ms[2] = {0, 0};                              // (tbk_kmerdb_query_read_depth_times_)
     size_t seen_bytes() const { return (size_t)((db->n + 31) / 32 + 1) * 4; }
     // what the kernels search; an empty database's arrays are the one entry of padding
     TbkDbView view() const {
@@ -1763,9 +1766,12 @@ extern "C" void tbk_kmerdb_query_destroy(tbk_kmerdb_query *q) {
         for (void *p : {(void *)q->d_dir, (void *)q->d_seen, (void *)q->d_copies, (void *)q->d_sums, q->d_pad})
             if (p) (void)hipFree(p);
         for (QueryBuf *b : {&q->bases, &q->offsets, &q->sep, &q->clean_bits, &q->found_bits, &q->bytes, &q->totals, &q->counts, &q->copy_bytes,
-                            &q->saturated_bits, &q->collapsed_bits, &q->expanded_bits, &q->bin_prefix, &q->bins, &q->repairs, &q->evidence})
+                            &q->saturated_bits, &q->collapsed_bits, &q->expanded_bits, &q->bin_prefix, &q->bins, &q->repairs, &q->evidence,
+                            &q->read_depth})
             if (b->p) (void)hipFree(b->p);
         for (hipEvent_t mark : q->evidence_marks)
+            if (mark) (void)hipEventDestroy(mark);
+        for (hipEvent_t mark : q->read_depth_marks)
             if (mark) (void)hipEventDestroy(mark);
     }
     delete q;
@@ -2096,5 +2102,55 @@ extern "C" int tbk_kmerdb_query_evidence_times_(tbk_kmerdb_query *q, double ms[2
     if (!q || !ms) return cfail(TBK_ERR_INVALID, "NULL argument");
     ms[0] = q->evidence_ms[0];
     ms[1] = q->evidence_ms[1];
+    return TBK_OK;
+}
+
+// The read depth (include/tbk.h has the rule; kernels: tbk_read_depth.hip): the batch is separated and looked up again without a
+// write to the session, and the clean bitmap and the depth bytes are reduced to one record per sequence.  The bitmap and the
+// bytes reuse the buffers of tbk_kmerdb_query_add; the records are the call's own and stay with the session.
+extern "C" int tbk_kmerdb_query_read_depth(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t min_count,
+                                           tbk_read_depth *out) {
+    if (!q) return cfail(TBK_ERR_INVALID, "tbk_kmerdb_query_read_depth: query is NULL");
+    if (min_count < 1 || min_count > 255) return cfail(TBK_ERR_INVALID, "read depth: min_count %u: need 1 <= min_count <= 255", min_count);
+    if (!n_reads) return TBK_OK;
+    if (!out) return cfail(TBK_ERR_INVALID, "tbk_kmerdb_query_read_depth: out is NULL");
+    int rc = tbk_check_offsets_(offsets, n_reads);
+    if (rc) return rc;
+    const uint64_t total = offsets[n_reads];
+    if (total && !bases) return cfail(TBK_ERR_INVALID, "bases is NULL");
+    for (uint64_t r = 0; r < n_reads; r++)
+        if (offsets[r + 1] - offsets[r] >= (uint64_t)q->k + 0xFFFFFFFFull)
+            return cfail(TBK_ERR_INVALID, "read depth: sequence %llu has %llu window starts: the per-read kernel counts in 32-bit rows, need fewer than 2^32",
+                         (unsigned long long)r, (unsigned long long)(offsets[r + 1] - offsets[r] - (uint64_t)q->k + 1));
+    memset(out, 0, n_reads * sizeof(tbk_read_depth));
+    if (!query_count_windows(offsets, n_reads, q->k)) return TBK_OK;
+    if ((rc = kmerdb_device(q->device))) return rc;
+    if ((rc = query_reserve(q->read_depth, n_reads * sizeof(tbk_read_depth)))) return rc;
+    for (hipEvent_t &mark : q->read_depth_marks)
+        if (!mark) CHIP(hipEventCreate(&mark));
+    uint64_t sep_total, passes;
+    if ((rc = query_stage_batch(q, bases, offsets, n_reads, &sep_total, &passes)) || (rc = query_reserve(q->bytes, passes * 2048))) return rc;
+    CHIP(hipEventRecord(q->read_depth_marks[0], nullptr));
+    CHIP(tbk_launch_read_depth_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, q->view(), std::max<uint32_t>(q->db->floor, min_count),
+                                      q->clean_bits.as<uint32_t>(), q->bytes.as<uint8_t>(), q->wave_slots, nullptr));
+    CHIP(hipEventRecord(q->read_depth_marks[1], nullptr));
+    CHIP(tbk_launch_read_depth(q->clean_bits.as<uint32_t>(), q->bytes.as<uint8_t>(), q->offsets.as<uint64_t>(), n_reads,
+                               q->read_depth.as<tbk_read_depth>(), q->wave_slots, nullptr));
+    CHIP(hipEventRecord(q->read_depth_marks[2], nullptr));
+    CHIP(hipMemcpy(out, q->read_depth.p, n_reads * sizeof(tbk_read_depth), hipMemcpyDeviceToHost));
+    float ms[2] = {0, 0};
+    CHIP(hipEventElapsedTime(&ms[0], q->read_depth_marks[0], q->read_depth_marks[1]));
+    CHIP(hipEventElapsedTime(&ms[1], q->read_depth_marks[1], q->read_depth_marks[2]));
+    q->read_depth_ms[0] = ms[0];
+    q->read_depth_ms[1] = ms[1];
+    return TBK_OK;
+}
+
+// (measuring hook, not in tbk.h: the device's clock over the two kernels of the last call that had a window - the lookup pass,
+// then the per-read kernel; tools/measure_read_depth.py)
+extern "C" int tbk_kmerdb_query_read_depth_times_(tbk_kmerdb_query *q, double ms[2]) {
+    if (!q || !ms) return cfail(TBK_ERR_INVALID, "NULL argument");
+    ms[0] = q->read_depth_ms[0];
+    ms[1] = q->read_depth_ms[1];
     return TBK_OK;
 }

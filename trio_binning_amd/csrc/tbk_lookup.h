@@ -1,5 +1,5 @@
 // tbk_lookup.h — the one window lookup of the count-database query kernels (tbk_query.hip, tbk_depth.hip, tbk_repair.hip,
-// tbk_screen.hip; the het-mer partners of tbk_hetmer.hip; the staging and the roll also in tbk_track.hip).  Three parts, each
+// tbk_screen.hip, tbk_read_depth.hip; the het-mer partners of tbk_hetmer.hip; the staging and the roll also in tbk_track.hip).  Three parts, each
 // written once here: a wave's windows (LaneWindows), the grouped search of a sorted database behind its directory
 // (db_search_group), and the body of the loop over passes that joins the two (lookup_pass).  The kernels keep their
 // accumulators, what they do with a group's answers, and their stores.  The host's side: tbk_lookup_host.h.

@@ -1,5 +1,5 @@
 // tbk_lookup_host.h — the window lookup of a query session as the host sees it: what the kernels read of a count database
-// (TbkDbView) and the one declaration of every launcher of tbk_query.hip, tbk_depth.hip, tbk_repair.hip and tbk_screen.hip;
+// (TbkDbView) and the one declaration of every launcher of tbk_query.hip, tbk_depth.hip, tbk_repair.hip, tbk_screen.hip and tbk_read_depth.hip;
 // included by the .hip files that define the launchers (a signature that drifts is a compile error) and by tbk_count.cpp, which
 // calls them.  The kernels' side: tbk_lookup.h.
 #pragma once
@@ -69,4 +69,12 @@ hipError_t tbk_launch_screen_lookup(const uint8_t *d_sep, uint64_t total, uint64
 // d_records: n_reads x 40 bytes.  Four sequences to a block: the grid-stride loop takes a second trip from 4 wave_slots + 1 sequences on.
 hipError_t tbk_launch_screen_evidence(const uint32_t *d_clean, const uint32_t *d_held, const uint64_t *d_offsets, uint64_t n_reads, int k,
                                       tbk_read_evidence *d_records, uint64_t wave_slots, hipStream_t stream);
+
+// ---- tbk_read_depth.hip: the read depth ----
+// d_clean: 64 words per pass; d_depth: TBK_PASS bytes per pass, every one written; m: the threshold, 1..255
+hipError_t tbk_launch_read_depth_lookup(const uint8_t *d_sep, uint64_t total, uint64_t n_passes, int k, TbkDbView db, uint32_t m, uint32_t *d_clean,
+                                        uint8_t *d_depth, uint64_t wave_slots, hipStream_t stream);
+// d_records: n_reads x 40 bytes; no sequence has 2^32 window starts or more.  Four sequences to a block, as the evidence has them.
+hipError_t tbk_launch_read_depth(const uint32_t *d_clean, const uint8_t *d_depth, const uint64_t *d_offsets, uint64_t n_reads, tbk_read_depth *d_records,
+                                 uint64_t wave_slots, hipStream_t stream);
 }

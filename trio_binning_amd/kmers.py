@@ -1416,6 +1416,11 @@ REPAIR_NONE, REPAIR_SUB, REPAIR_DEL, REPAIR_INS, REPAIR_LONG = range(5)
 READ_EVIDENCE = np.dtype([("clean", "<u8"), ("held", "<u8"), ("covered", "<u8"), ("longest", "<u8"), ("stretches", "<u8")])
 assert READ_EVIDENCE.itemsize == 40
 
+# one sequence's k-mer depth (``tbk_read_depth``, 40 bytes)
+READ_DEPTH = np.dtype([("clean", "<u8"), ("present", "<u8"), ("saturated", "<u8"), ("sum", "<u8"), ("lowest", "u1"), ("q1", "u1"), ("median", "u1"),
+                       ("q3", "u1"), ("highest", "u1"), ("present_median", "u1"), ("pad", "u1", (2,))])
+assert READ_DEPTH.itemsize == 40
+
 
 class DatabaseQuery:
     """How often did the reads see the k-mers of these sequences?  (``tbk_kmerdb_query``, include/tbk.h.)
@@ -1537,6 +1542,26 @@ class DatabaseQuery:
             raise ValueError("evidence: min_count {} must lie in 1 .. 255 and max_count {} in min_count .. 255".format(min_count, max_count))
         records = np.zeros(n, dtype=READ_EVIDENCE)
         check(lib.tbk_kmerdb_query_evidence(self._h, bases.ctypes.data, offsets.ctypes.data, n, min_count, max_count, records.ctypes.data))
+        return records
+
+    def read_depth(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 1) -> np.ndarray:
+        """The k-mer depth of a batch of reads (``tbk_kmerdb_query_read_depth``, include/tbk.h): one ``READ_DEPTH`` record per
+        sequence.  The depth of a clean window is its counter when that is ``max(floor, min_count)`` or more, else 0.  ``clean``
+        counts the clean windows, ``present`` those of depth 1 or more and ``saturated`` those of depth 255; ``sum`` is the sum of
+        the depths, and ``lowest``, ``q1``, ``median``, ``q3`` and ``highest`` are the sorted depths at the ranks
+        ``j * (clean - 1) // 4``, ``j`` = 0..4 - the median is the lower one; ``present_median`` is the lower median of the present
+        windows' depths, 0 when there are none.  A sequence without a clean window gets an all-zero record.  The session is only
+        read.  ``ValueError`` for a ``min_count`` outside 1..255."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.size - 1, 0)
+        min_count = int(min_count)
+        if not 0 <= min_count < 1 << 32:
+            # the library's own refusal and message, for the values a C uint32_t can carry
+            check(lib.tbk_kmerdb_query_read_depth(self._h, None, None, 0, min(max(min_count, 0), 0xFFFFFFFF), None))
+            raise ValueError("read_depth: min_count {} must lie in 1 .. 255".format(min_count))
+        records = np.zeros(n, dtype=READ_DEPTH)
+        check(lib.tbk_kmerdb_query_read_depth(self._h, bases.ctypes.data, offsets.ctypes.data, n, min_count, records.ctypes.data))
         return records
 
     def reset(self) -> None:
