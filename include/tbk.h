@@ -1450,6 +1450,67 @@ typedef struct tbk_read_depth {
 int tbk_kmerdb_query_read_depth(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets,
                                 uint64_t n_reads, uint32_t min_count, tbk_read_depth *out /* n_reads */);
 
+/* ---- read pieces: where along a read do the database's k-mers lie, and where do they not? ------------------------- */
+/* The read evidence says how much of a sequence the held windows cover; this says where: the maximal runs of covered - or
+ * of uncovered - positions as intervals, what khmer's trim-low-abund and BBDuk's ktrim and kmask work with.  q is a session
+ * with or without copies, k its database's k, min_count in 1..255, max_count in min_count..255, side TBK_PIECES_COVERED or
+ * _UNCOVERED, which TBK_PIECES_ALL or _LONGEST.
+ * WINDOWS, HELD, COVERED.  Exactly as the read evidence defines them: clean windows (ACGT only, either case), canonical
+ * k-mers, the counter c, the lower bound m = max(floor, min_count), a window HELD when it is clean and m <= c <= max_count,
+ * a position p in [0, L) COVERED when some held window w has w <= p <= w + k - 1.  A base that is not ACGT lies in no clean
+ * window and is therefore never covered.
+ * SIDE.  Position p in [0, L) of a sequence is ON THE SIDE when it is covered (TBK_PIECES_COVERED) or when it is not
+ * (TBK_PIECES_UNCOVERED).
+ * PIECE.  A piece is a maximal run [first, end) of consecutive on-side positions of one sequence.  Pieces never join across
+ * sequences.  An empty sequence has no piece.  A sequence shorter than k has none on the covered side and exactly one,
+ * [0, L), on the uncovered side.
+ * MIN_LENGTH.  Pieces with end - first < min_length are left out; 0 and 1 mean the same.
+ * WHICH.  With TBK_PIECES_LONGEST only the longest of a sequence's pieces that passed min_length is returned; among equals
+ * the one with the smallest first.
+ * RESULT.  The records are ordered by (read, first), in memory of tbk_host_alloc: *pieces is the caller's to tbk_host_free
+ * (NULL when there is no piece), as tbk_kmerdb_query_repairs returns its list.
+ * EVIDENCE.  When evidence is not NULL it takes n_reads records, byte for byte what tbk_kmerdb_query_evidence writes for the
+ * same arguments; they come from the same lookup pass, there is no second lookup.
+ * The call only reads the session: the histogram, the seen bits, the copies and the window total are as they were, and the
+ * batch does not count towards the limit of 2^32 - 1 window starts.  n_reads == 0 is valid and gives no piece.  An empty
+ * database is valid: nothing is covered.  A range that is empty after the floor - (1, 1) on a solid database - is valid and
+ * covers nothing.
+ * TBK_ERR_INVALID, with a message, before anything runs and with nothing written - not *pieces, *n_pieces or evidence - for
+ * min_count outside 1..255, max_count outside min_count..255, side > 1, which > 1, a NULL q, pieces or n_pieces, and a
+ * sequence of 2^32 or more bases (the longest piece of a read is chosen by a 64-bit key of its length and its first
+ * position, 32 bits each); the session stays usable.
+ * The call uses the session's batch buffers and grows them as needed.  On the device it takes, per base of the batch
+ * (rounded up to passes of 2048 stream positions, one position more per sequence): the bases and their separated copy
+ * (2 bytes), the clean and the held bitmap (2 bits), the side bitmap (1 bit) and, until the call returns, the flags of the
+ * two compactions of starts and ends (2 bits and 32 bytes per 1024 positions) - 2.66 bytes, of which
+ * tbk_kmerdb_query_add's own buffers already hold 2.25.  Per sequence: 8 bytes for the offsets, 40 for the evidence record
+ * when it is asked for and 8 for the key with TBK_PIECES_LONGEST.  Per piece of the batch before min_length and which are
+ * applied: 24 bytes, and, when either leaves pieces out, 1 bit of flags and 24 bytes for every piece that stays.  A batch has
+ * at most (bases + n_reads) / 2 pieces - a piece is one position at least and so is the gap behind it - and at most n_reads
+ * come home with TBK_PIECES_LONGEST. */
+enum { TBK_PIECES_COVERED = 0, TBK_PIECES_UNCOVERED = 1 };   /* side  */
+enum { TBK_PIECES_ALL = 0, TBK_PIECES_LONGEST = 1 };         /* which */
+typedef struct tbk_read_piece { uint64_t read, first, end; } tbk_read_piece;   /* 24 bytes; [first, end) */
+int tbk_kmerdb_query_pieces(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads,
+                            uint32_t min_count, uint32_t max_count, uint32_t side, uint32_t which, uint64_t min_length,
+                            tbk_read_evidence *evidence /* n_reads, may be NULL */,
+                            tbk_read_piece **pieces, uint64_t *n_pieces);
+/* The writer's side: a batch's records cut to their pieces.  Per read of the batch, in input order: bins[i] == 'A' sends
+ * the read's pieces, in their order, to the first file - a read without a piece writes nothing; 'B' sends the read whole to
+ * the second file and anything else sends it whole to the third, with the bytes tbk_bin_writer_write writes.
+ * A piece [f, e) is written in the form tbk_bin_writer_write gives a record: FASTQ when the record has a non-empty quality
+ * string, sequence and quality both cut to [f, e), else FASTA; the name is the header up to the first space.  With
+ * suffix != 0 a piece that is not the whole record is renamed name:F-E, F = f + 1 and E = e (1-based and closed, as
+ * samtools faidx names a region); a piece that is the whole record keeps the name, so a read that is kept untouched is the
+ * same bytes as tbk_bin_writer_write's.  The text goes through the bins' buffers; gzip members are coded as for any bin,
+ * by the host or the device.
+ * TBK_ERR_INVALID for pieces that are not ordered by (read, first), that overlap, that are empty, that name a read the batch
+ * does not have or that reach past a record's end; TBK_ERR_STATE for a BAM-bin or a haplotag writer and for a borrowed
+ * batch.  Nothing is written in any of these cases.  The cut is the host's: the text of a record is gathered by the host for
+ * every bin, and a device that rewrote record bytes lost to the host once the copy home was counted. */
+int tbk_bin_writer_write_pieces(tbk_bin_writer *w, const tbk_fastx_batch *b, const tbk_read_piece *pieces, uint64_t n_pieces,
+                                const char *bins /* per READ */, int suffix);
+
 /* Host threads the library starts for its own host-side work (list parsing, gzip members,
  * scoring): hardware threads limited by the CPU affinity mask and the cgroup CPU quota, divided by the
  * number of ranks the launcher started on this node (LOCAL_WORLD_SIZE, or TBK_LOCAL_RANKS): one process per GPU

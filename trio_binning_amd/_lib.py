@@ -319,6 +319,10 @@ HAS_DB_READ_DEPTH = hasattr(lib, "tbk_kmerdb_query_read_depth")  # (variant buil
 if HAS_DB_READ_DEPTH:
     _sig("tbk_kmerdb_query_read_depth", C.c_int, _vp, _vp, _vp, _u64, C.c_uint32, _vp)
     _sig("tbk_kmerdb_query_read_depth_times_", C.c_int, _vp, _vp)  # (measuring hook: the last call's two kernel times, ms)
+HAS_DB_PIECES = hasattr(lib, "tbk_kmerdb_query_pieces")  # (variant builds may predate the read pieces)
+if HAS_DB_PIECES:
+    _sig("tbk_kmerdb_query_pieces", C.c_int, _vp, _vp, _vp, _u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64, _vp, C.POINTER(_vp), _u64p)
+    _sig("tbk_kmerdb_query_pieces_times_", C.c_int, _vp, _vp)  # (measuring hook: the last call's lookup, evidence and piece times, ms)
 
 class DumpOptions(C.Structure):
     """tbk_dump_options (include/tbk.h)."""
@@ -354,6 +358,8 @@ _sig("tbk_fastx_batch_view", C.c_int, _vp, _u64p, C.POINTER(_vp), C.POINTER(_vp)
 _sig("tbk_bin_writer_open", C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(_vp))
 _sig("tbk_bin_writer_write", C.c_int, _vp, _vp, C.c_char_p)
 _sig("tbk_bin_writer_close", C.c_int, _vp)
+if hasattr(lib, "tbk_bin_writer_write_pieces"):  # (variant builds may predate the read pieces)
+    _sig("tbk_bin_writer_write_pieces", C.c_int, _vp, _vp, _vp, _u64, C.c_char_p, C.c_int)
 if hasattr(lib, "tbk_gzip_members_device"):
     _sig("tbk_bin_writer_use_device", C.c_int, _vp, C.c_int)
     _sig("tbk_bin_writer_encoder", C.c_int, _vp)

@@ -1701,7 +1701,7 @@ extern "C" int tbk_kmerdb_hetmers(const tbk_kmerdb *db, const tbk_hetmer_options
 // Database query (tbk_kmerdb_query; kernels: tbk_query.hip): the counter the database holds for every window of a
 // batch of sequences - per-sequence totals, a histogram, the entries seen, their copies.  include/tbk.h has the rules.
 // =====================================================================================================================
-// (the launchers of its kernel files - tbk_query.hip, tbk_depth.hip, tbk_repair.hip, tbk_screen.hip, tbk_read_depth.hip: tbk_lookup_host.h)
+// (the launchers of its kernel files - tbk_query.hip, tbk_depth.hip, tbk_repair.hip, tbk_screen.hip, tbk_read_depth.hip, tbk_pieces.hip: tbk_lookup_host.h)
 constexpr uint64_t TBK_QUERY_MAX_WINDOWS = 0xFFFFFFFFull;  // window starts of a session: a 32-bit copy counter cannot wrap
 constexpr int TBK_QUERY_MAX_PREFIX_BITS = 28;              // a directory of at most 1 GiB + 4 bytes
 
@@ -1731,6 +1731,9 @@ struct tbk_kmerdb_query {
     QueryBuf read_depth;                                                                   // (the read depth's records)
     hipEvent_t read_depth_marks[3] = {nullptr, nullptr, nullptr};  // around the read depth's two kernels, made by its first call
     double read_depth_ms[2] = {0, 0};                              // (tbk_kmerdb_query_read_depth_times_)
+    QueryBuf side, pieces, kept_pieces, piece_keys;                // (the read pieces' side bitmap, records and per-read keys)
+    hipEvent_t pieces_marks[4] = {nullptr, nullptr, nullptr, nullptr};  // around the lookup, the evidence and the piece kernels, made by the first call
+    double pieces_ms[3] = {0, 0, 0};                                    // (tbk_kmerdb_query_pieces_times_)
     size_t seen_bytes() const { return (size_t)((db->n + 31) / 32 + 1) * 4; }
     // what the kernels search; an empty database's arrays are the one entry of padding
     TbkDbView view() const {
@@ -1767,11 +1770,13 @@ extern "C" void tbk_kmerdb_query_destroy(tbk_kmerdb_query *q) {
             if (p) (void)hipFree(p);
         for (QueryBuf *b : {&q->bases, &q->offsets, &q->sep, &q->clean_bits, &q->found_bits, &q->bytes, &q->totals, &q->counts, &q->copy_bytes,
                             &q->saturated_bits, &q->collapsed_bits, &q->expanded_bits, &q->bin_prefix, &q->bins, &q->repairs, &q->evidence,
-                            &q->read_depth})
+                            &q->read_depth, &q->side, &q->pieces, &q->kept_pieces, &q->piece_keys})
             if (b->p) (void)hipFree(b->p);
         for (hipEvent_t mark : q->evidence_marks)
             if (mark) (void)hipEventDestroy(mark);
         for (hipEvent_t mark : q->read_depth_marks)
+            if (mark) (void)hipEventDestroy(mark);
+        for (hipEvent_t mark : q->pieces_marks)
             if (mark) (void)hipEventDestroy(mark);
     }
     delete q;
@@ -2152,5 +2157,121 @@ extern "C" int tbk_kmerdb_query_read_depth_times_(tbk_kmerdb_query *q, double ms
     if (!q || !ms) return cfail(TBK_ERR_INVALID, "NULL argument");
     ms[0] = q->read_depth_ms[0];
     ms[1] = q->read_depth_ms[1];
+    return TBK_OK;
+}
+
+// The read pieces (include/tbk.h has the rule; kernels: tbk_pieces.hip, and tbk_screen.hip for the lookup and the evidence):
+// the batch is separated and looked up again without a write to the session; the held bitmap becomes the side bitmap, the
+// starts and the ends of its runs are compacted into records at their exact number, and min_length and TBK_PIECES_LONGEST
+// filter the records in a third compaction.  The two bitmaps reuse the buffers of tbk_kmerdb_query_add; the compactions' flags
+// are the call's own and freed on return; the side bitmap, the records and the keys stay with the session.
+extern "C" int tbk_kmerdb_query_pieces(tbk_kmerdb_query *q, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, uint32_t min_count,
+                                       uint32_t max_count, uint32_t side, uint32_t which, uint64_t min_length, tbk_read_evidence *evidence,
+                                       tbk_read_piece **pieces, uint64_t *n_pieces) {
+    if (!q || !pieces || !n_pieces) return cfail(TBK_ERR_INVALID, "tbk_kmerdb_query_pieces: NULL argument");
+    if (min_count < 1 || min_count > 255) return cfail(TBK_ERR_INVALID, "pieces: min_count %u: need 1 <= min_count <= 255", min_count);
+    if (max_count < min_count || max_count > 255)
+        return cfail(TBK_ERR_INVALID, "pieces: max_count %u: need min_count (%u) <= max_count <= 255", max_count, min_count);
+    if (side > 1) return cfail(TBK_ERR_INVALID, "pieces: side %u: need TBK_PIECES_COVERED (0) or TBK_PIECES_UNCOVERED (1)", side);
+    if (which > 1) return cfail(TBK_ERR_INVALID, "pieces: which %u: need TBK_PIECES_ALL (0) or TBK_PIECES_LONGEST (1)", which);
+    int rc = n_reads ? tbk_check_offsets_(offsets, n_reads) : TBK_OK;
+    if (rc) return rc;
+    const uint64_t total = n_reads ? offsets[n_reads] : 0;
+    if (total && !bases) return cfail(TBK_ERR_INVALID, "bases is NULL");
+    for (uint64_t r = 0; r < n_reads; r++)
+        if (offsets[r + 1] - offsets[r] >= (1ull << 32))
+            return cfail(TBK_ERR_INVALID, "pieces: sequence %llu has %llu bases: a read's longest piece is chosen by 32 bits of length and 32 of position, need fewer than 2^32",
+                         (unsigned long long)r, (unsigned long long)(offsets[r + 1] - offsets[r]));
+    *pieces = nullptr;
+    *n_pieces = 0;
+    if (evidence && n_reads) memset(evidence, 0, n_reads * sizeof(tbk_read_evidence));
+    if (!total) return TBK_OK;  // (no read, or empty ones only)
+    if ((rc = kmerdb_device(q->device))) return rc;
+    for (hipEvent_t &mark : q->pieces_marks)
+        if (!mark) CHIP(hipEventCreate(&mark));
+    uint64_t sep_total, passes;
+    if ((rc = query_stage_batch(q, bases, offsets, n_reads, &sep_total, &passes)) || (rc = query_reserve(q->side, passes * 64 * 4)) ||
+        (evidence && (rc = query_reserve(q->evidence, n_reads * sizeof(tbk_read_evidence)))))
+        return rc;
+    const uint32_t *d_held = q->found_bits.as<uint32_t>();
+    uint32_t *d_side = q->side.as<uint32_t>();
+    CHIP(hipEventRecord(q->pieces_marks[0], nullptr));
+    CHIP(tbk_launch_screen_lookup(q->sep.as<uint8_t>(), sep_total, passes, q->k, q->view(), std::max<uint32_t>(q->db->floor, min_count), max_count,
+                                  q->clean_bits.as<uint32_t>(), q->found_bits.as<uint32_t>(), q->wave_slots, nullptr));
+    CHIP(hipEventRecord(q->pieces_marks[1], nullptr));
+    if (evidence)
+        CHIP(tbk_launch_screen_evidence(q->clean_bits.as<uint32_t>(), d_held, q->offsets.as<uint64_t>(), n_reads, q->k, q->evidence.as<tbk_read_evidence>(),
+                                        q->wave_slots, nullptr));
+    CHIP(hipEventRecord(q->pieces_marks[2], nullptr));
+    if (side == TBK_PIECES_UNCOVERED) CHIP(hipMemsetAsync(d_side, 0, passes * 64 * 4, nullptr));
+    CHIP(tbk_launch_pieces_side(d_held, q->offsets.as<uint64_t>(), n_reads, sep_total, passes, q->k, side == TBK_PIECES_UNCOVERED, d_side, q->wave_slots, nullptr));
+    Compaction starts, ends, keep;
+    unsigned long long found = 0, found_ends = 0, kept = 0;
+    CHIP(starts.reserve(passes * 2048, nullptr));
+    CHIP(ends.reserve(passes * 2048, nullptr));
+    CHIP(tbk_launch_pieces_flag(d_side, passes, 0, starts.d_flags, starts.counts(), nullptr));
+    CHIP(tbk_launch_pieces_flag(d_side, passes, 1, ends.d_flags, ends.counts(), nullptr));
+    CHIP(starts.total(&found));
+    CHIP(ends.total(&found_ends));
+    if (found != found_ends || found > sep_total / 2)  // (nothing is allocated or written by a count that cannot be)
+        return cfail(TBK_ERR_HIP, "tbk_kmerdb_query_pieces: %llu starts and %llu ends among %llu positions", found, found_ends, (unsigned long long)sep_total);
+    const tbk_read_piece *d_result = nullptr;
+    if (found) {
+        if ((rc = query_reserve(q->pieces, found * sizeof(tbk_read_piece)))) return rc;
+        CHIP(tbk_launch_pieces_ends(passes, ends.d_flags, ends.offsets(), q->pieces.as<tbk_read_piece>(), found, nullptr));
+        CHIP(tbk_launch_pieces_starts(passes, q->offsets.as<uint64_t>(), n_reads, starts.d_flags, starts.offsets(), q->pieces.as<tbk_read_piece>(), found,
+                                      nullptr));
+        d_result = q->pieces.as<tbk_read_piece>();
+        kept = found;
+    }
+    if (found && (min_length > 1 || which == TBK_PIECES_LONGEST)) {
+        const unsigned long long *d_keys = nullptr;
+        if (which == TBK_PIECES_LONGEST) {
+            if ((rc = query_reserve(q->piece_keys, n_reads * 8))) return rc;
+            CHIP(hipMemsetAsync(q->piece_keys.p, 0, n_reads * 8, nullptr));
+            CHIP(tbk_launch_pieces_best(q->pieces.as<tbk_read_piece>(), found, min_length, q->piece_keys.as<unsigned long long>(), q->wave_slots, nullptr));
+            d_keys = q->piece_keys.as<unsigned long long>();
+        }
+        CHIP(keep.reserve(found, nullptr));
+        CHIP(tbk_launch_pieces_keep_flag(q->pieces.as<tbk_read_piece>(), found, min_length, d_keys, keep.d_flags, keep.counts(), nullptr));
+        CHIP(keep.total(&kept));
+        if (kept > found) return cfail(TBK_ERR_HIP, "tbk_kmerdb_query_pieces: %llu of %llu pieces kept", kept, found);
+        if (kept) {
+            if ((rc = query_reserve(q->kept_pieces, kept * sizeof(tbk_read_piece)))) return rc;
+            CHIP(tbk_launch_pieces_keep(q->pieces.as<tbk_read_piece>(), found, keep.d_flags, keep.offsets(), q->kept_pieces.as<tbk_read_piece>(), kept, nullptr));
+        }
+        d_result = q->kept_pieces.as<tbk_read_piece>();
+    }
+    CHIP(hipEventRecord(q->pieces_marks[3], nullptr));
+    tbk_read_piece *home = nullptr;
+    if (kept) {
+        if (!(home = (tbk_read_piece *)tbk_host_alloc(kept * sizeof(tbk_read_piece)))) return TBK_ERR_NOMEM;  // (tbk_host_alloc has left the reason)
+        const hipError_t e = hipMemcpy(home, d_result, kept * sizeof(tbk_read_piece), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            tbk_host_free(home);
+            (void)hipGetLastError();
+            return cfail(TBK_ERR_HIP, "tbk_kmerdb_query_pieces (%llu pieces): %s", kept, hipGetErrorString(e));
+        }
+    }
+    hipError_t e = evidence ? hipMemcpy(evidence, q->evidence.p, n_reads * sizeof(tbk_read_evidence), hipMemcpyDeviceToHost) : hipStreamSynchronize(nullptr);
+    float ms[3] = {0, 0, 0};
+    for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipEventElapsedTime(&ms[i], q->pieces_marks[i], q->pieces_marks[i + 1]);
+    if (e != hipSuccess) {
+        tbk_host_free(home);
+        (void)hipGetLastError();
+        return cfail(TBK_ERR_HIP, "tbk_kmerdb_query_pieces (%llu bases): %s", (unsigned long long)total, hipGetErrorString(e));
+    }
+    for (int i = 0; i < 3; i++) q->pieces_ms[i] = ms[i];
+    *pieces = home;
+    *n_pieces = kept;
+    return TBK_OK;
+}
+
+// (measuring hook, not in tbk.h: the device's clock over the last call that had a base - the lookup pass, the evidence kernel
+// (next to nothing when no evidence was asked for), then everything between the evidence and the last piece kernel, the
+// host's waits for the compactions' totals included; tools/measure_pieces.py)
+extern "C" int tbk_kmerdb_query_pieces_times_(tbk_kmerdb_query *q, double ms[3]) {
+    if (!q || !ms) return cfail(TBK_ERR_INVALID, "NULL argument");
+    for (int i = 0; i < 3; i++) ms[i] = q->pieces_ms[i];
     return TBK_OK;
 }

@@ -2856,6 +2856,104 @@ extern "C" int tbk_bin_writer_write(tbk_bin_writer *w, const tbk_fastx_batch *b,
     return flush_bins(w, false);
 }
 
+// A batch's records cut to their pieces (include/tbk.h, "read pieces"): an 'A' read's pieces go to the first bin, every other
+// read goes whole to its bin as tbk_bin_writer_write sends it.  One serial pass checks the pieces and sizes the text, a second
+// one puts it into the bins' buffers: the cut is a handful of memcpys per piece, and the members are coded as for any bin.
+extern "C" int tbk_bin_writer_write_pieces(tbk_bin_writer *w, const tbk_fastx_batch *b, const tbk_read_piece *pieces, uint64_t n_pieces, const char *bins,
+                                           int suffix) {
+    if (!w || !b || (b->n_reads() && !bins) || (n_pieces && !pieces)) return ffail(TBK_ERR_INVALID, "NULL argument");
+    if (w->tag) return ffail(TBK_ERR_STATE, "tbk_bin_writer_write_pieces: a haplotag writer holds records whole (tbk_bin_writer_write_counts)");
+    if (w->bam) return ffail(TBK_ERR_STATE, "tbk_bin_writer_write_pieces: BAM bins hold records whole: a piece of a BAM record is not defined");
+    if (b->borrowed) return ffail(TBK_ERR_STATE, "tbk_bin_writer_write_pieces: a borrowed batch has no sequence and quality arrays to cut (tbk_fastx_set_borrowing)");
+    const uint64_t n = b->n_reads();
+    for (uint64_t j = 0; j < n_pieces; j++) {
+        const tbk_read_piece &pc = pieces[j];
+        if (pc.read >= n) return ffail(TBK_ERR_INVALID, "tbk_bin_writer_write_pieces: piece %llu names read %llu of a batch of %llu", (unsigned long long)j,
+                                       (unsigned long long)pc.read, (unsigned long long)n);
+        const uint64_t len = b->base_off[pc.read + 1] - b->base_off[pc.read];
+        if (pc.first >= pc.end || pc.end > len)
+            return ffail(TBK_ERR_INVALID, "tbk_bin_writer_write_pieces: piece %llu, [%llu, %llu) of read %llu, is empty or reaches past the record's %llu bases",
+                         (unsigned long long)j, (unsigned long long)pc.first, (unsigned long long)pc.end, (unsigned long long)pc.read, (unsigned long long)len);
+        if (j && (pieces[j - 1].read > pc.read || (pieces[j - 1].read == pc.read && pieces[j - 1].end > pc.first)))
+            return ffail(TBK_ERR_INVALID, "tbk_bin_writer_write_pieces: piece %llu is not behind piece %llu: the pieces are ordered by (read, first) and do not overlap",
+                         (unsigned long long)j, (unsigned long long)(j - 1));
+    }
+    // the name of a piece that is not its whole record: name:F-E
+    auto tail = [](const tbk_read_piece &pc, char *out) { return (size_t)snprintf(out, 48, ":%llu-%llu", (unsigned long long)pc.first + 1, (unsigned long long)pc.end); };
+    auto piece_bytes = [&](uint64_t i, const tbk_read_piece &pc) {
+        const size_t nn = b->name_off[i + 1] - b->name_off[i], ns = b->base_off[i + 1] - b->base_off[i], nq = b->qual_off[i + 1] - b->qual_off[i];
+        const bool fq = b->has_qual[i] && nq > 0;
+        const size_t cut = (size_t)(pc.end - pc.first);
+        char name_tail[48];
+        const size_t nt = suffix && cut != ns ? tail(pc, name_tail) : 0;
+        return 1 + nn + nt + 1 + cut + 1 + (fq ? 2 + cut + 1 : 0);
+    };
+    uint64_t at[3] = {w->bin[0].text.size(), w->bin[1].text.size(), w->bin[2].text.size()};
+    {
+        uint64_t j = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            const int which = bins[i] == 'A' ? 0 : bins[i] == 'B' ? 1 : 2;
+            const uint64_t j0 = j;
+            while (j < n_pieces && pieces[j].read == i) j++;
+            if (which == 0) {
+                for (uint64_t t = j0; t < j; t++) {
+                    const uint64_t nq = b->qual_off[i + 1] - b->qual_off[i];
+                    if (b->has_qual[i] && nq > 0 && nq < pieces[t].end)
+                        return ffail(TBK_ERR_INVALID, "tbk_bin_writer_write_pieces: piece %llu reaches past the %llu quality values of read %llu",
+                                     (unsigned long long)t, (unsigned long long)nq, (unsigned long long)i);
+                    at[0] += piece_bytes(i, pieces[t]);
+                }
+                continue;
+            }
+            const size_t nn = b->name_off[i + 1] - b->name_off[i], ns = b->base_off[i + 1] - b->base_off[i], nq = b->qual_off[i + 1] - b->qual_off[i];
+            at[which] += 1 + nn + 1 + ns + 1 + (b->has_qual[i] && nq > 0 ? 2 + nq + 1 : 0);
+        }
+    }
+    char *out[3];
+    for (int k = 0; k < 3; k++) {
+        const size_t before = w->bin[k].text.size();
+        if (!w->bin[k].text.grow_to((size_t)at[k])) return ffail(TBK_ERR_NOMEM, "out of memory buffering a bin");
+        out[k] = w->bin[k].text.data() + before;
+    }
+    for (int k = 0; k < 3; k++) w->bin[k].text.n = (size_t)at[k];
+    const double t0 = wall_now();
+    uint64_t j = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const int which = bins[i] == 'A' ? 0 : bins[i] == 'B' ? 1 : 2;
+        const uint64_t j0 = j;
+        while (j < n_pieces && pieces[j].read == i) j++;
+        char *&p = out[which];
+        if (which != 0) {
+            struct iovec pc[7];
+            const int np = record_pieces(b, (size_t)i, pc);
+            for (int c = 0; c < np; c++) { memcpy(p, pc[c].iov_base, pc[c].iov_len); p += pc[c].iov_len; }
+            continue;
+        }
+        const size_t nn = b->name_off[i + 1] - b->name_off[i], ns = b->base_off[i + 1] - b->base_off[i], nq = b->qual_off[i + 1] - b->qual_off[i];
+        const bool fq = b->has_qual[i] && nq > 0;
+        for (uint64_t t = j0; t < j; t++) {
+            const tbk_read_piece &pc = pieces[t];
+            const size_t cut = (size_t)(pc.end - pc.first);
+            *p++ = fq ? '@' : '>';
+            if (nn) { memcpy(p, b->names.data() + b->name_off[i], nn); p += nn; }
+            if (suffix && cut != ns) {
+                char name_tail[48];
+                const size_t nt = tail(pc, name_tail);
+                memcpy(p, name_tail, nt); p += nt;
+            }
+            *p++ = '\n';
+            memcpy(p, b->bases + b->base_off[i] + pc.first, cut); p += cut;
+            if (fq) {
+                *p++ = '\n'; *p++ = '+'; *p++ = '\n';
+                memcpy(p, b->quals.data() + b->qual_off[i] + pc.first, cut); p += cut;
+            }
+            *p++ = '\n';
+        }
+    }
+    w->fill_s += wall_now() - t0;
+    return flush_bins(w, false);
+}
+
 // Who rewrites a haplotag writer's records once a device is there: TBK_HAPLOTAG_REWRITE=gpu / cpu, else the default the
 // measurement set.
 static bool tag_rewrites_on_device() {

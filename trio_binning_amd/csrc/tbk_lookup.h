@@ -1,5 +1,5 @@
 // tbk_lookup.h — the one window lookup of the count-database query kernels (tbk_query.hip, tbk_depth.hip, tbk_repair.hip,
-// tbk_screen.hip, tbk_read_depth.hip; the het-mer partners of tbk_hetmer.hip; the staging and the roll also in tbk_track.hip).  Three parts, each
+// tbk_screen.hip, tbk_read_depth.hip, tbk_pieces.hip; the het-mer partners of tbk_hetmer.hip; the staging and the roll also in tbk_track.hip).  Three parts, each
 // written once here: a wave's windows (LaneWindows), the grouped search of a sorted database behind its directory
 // (db_search_group), and the body of the loop over passes that joins the two (lookup_pass).  The kernels keep their
 // accumulators, what they do with a group's answers, and their stores.  The host's side: tbk_lookup_host.h.
@@ -184,4 +184,15 @@ __device__ __forceinline__ uint32_t range_word_mask(uint64_t w, uint64_t w_first
     if (w == w_first) mask &= 0xFFFFFFFFu << (a & 31u);
     if (w == w_last) mask &= 0xFFFFFFFFu >> (31u - (uint32_t)((b - 1) & 31u));
     return mask;
+}
+
+// The COVERED word of bitmap word w from the held words w (h) and w - 1 (hb; 0 for word 0): the held bits dilated by k - 1
+// positions upward.  k <= 32, so a 32-bit word needs only its predecessor as halo, and the dilation is floor(log2 k) + 1
+// shift-and-ors of the two words side by side in one 64-bit register.  (tbk_screen.hip, tbk_pieces.hip)
+__device__ __forceinline__ uint32_t covered_word(uint32_t h, uint32_t hb, int k) {
+    uint64_t x = ((uint64_t)h << 32) | hb;  // shifts 0 .. n - 1 of the held bits so far; n doubles up to k
+    int n = 1;
+    while (2 * n <= k) { x |= x << n; n *= 2; }
+    x |= x << (k - n);  // (k - n < n)
+    return (uint32_t)(x >> 32);
 }

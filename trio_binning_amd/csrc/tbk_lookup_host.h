@@ -1,5 +1,5 @@
 // tbk_lookup_host.h — the window lookup of a query session as the host sees it: what the kernels read of a count database
-// (TbkDbView) and the one declaration of every launcher of tbk_query.hip, tbk_depth.hip, tbk_repair.hip, tbk_screen.hip and tbk_read_depth.hip;
+// (TbkDbView) and the one declaration of every launcher of tbk_query.hip, tbk_depth.hip, tbk_repair.hip, tbk_screen.hip, tbk_read_depth.hip and tbk_pieces.hip;
 // included by the .hip files that define the launchers (a signature that drifts is a compile error) and by tbk_count.cpp, which
 // calls them.  The kernels' side: tbk_lookup.h.
 #pragma once
@@ -77,4 +77,28 @@ hipError_t tbk_launch_read_depth_lookup(const uint8_t *d_sep, uint64_t total, ui
 // d_records: n_reads x 40 bytes; no sequence has 2^32 window starts or more.  Four sequences to a block, as the evidence has them.
 hipError_t tbk_launch_read_depth(const uint32_t *d_clean, const uint8_t *d_depth, const uint64_t *d_offsets, uint64_t n_reads, tbk_read_depth *d_records,
                                  uint64_t wave_slots, hipStream_t stream);
+
+// ---- tbk_pieces.hip: the read pieces (the lookup and the evidence are tbk_screen.hip's) ----
+// d_side: 64 words per pass, one bit per stream position.  The covered side (uncovered 0) overwrites every word; the uncovered
+// side wants the words zeroed by the caller: the separators are scattered into them first and the side replaces them in place.
+hipError_t tbk_launch_pieces_side(const uint32_t *d_held, const uint64_t *d_offsets, uint64_t n_reads, uint64_t total, uint64_t n_passes, int k,
+                                  int uncovered, uint32_t *d_side, uint64_t wave_slots, hipStream_t stream);
+// the starts (end 0) or the last positions (end 1) of the runs among the n_passes * 2048 positions of d_side: d_flags and
+// d_tile_counts as Compaction holds them for that many
+hipError_t tbk_launch_pieces_flag(const uint32_t *d_side, uint64_t n_passes, int end, uint64_t *d_flags, unsigned long long *d_tile_counts,
+                                  hipStream_t stream);
+// d_pieces: n_pieces x 24 bytes, in stream order.  The ends first - every record's `end` as a stream position - then the starts,
+// which find the record's read, write read and first and bring `end` into the read's coordinates.
+hipError_t tbk_launch_pieces_ends(uint64_t n_passes, const uint64_t *d_flags, const unsigned long long *d_tile_offsets, tbk_read_piece *d_pieces,
+                                  uint64_t n_pieces, hipStream_t stream);
+hipError_t tbk_launch_pieces_starts(uint64_t n_passes, const uint64_t *d_offsets, uint64_t n_reads, const uint64_t *d_flags,
+                                    const unsigned long long *d_tile_offsets, tbk_read_piece *d_pieces, uint64_t n_pieces, hipStream_t stream);
+// d_keys: n_reads words, zeroed by the caller: per read the largest (length << 32 | ~first) of its pieces of min_length or more
+hipError_t tbk_launch_pieces_best(const tbk_read_piece *d_pieces, uint64_t n_pieces, uint64_t min_length, unsigned long long *d_keys,
+                                  uint64_t wave_slots, hipStream_t stream);
+// the pieces of min_length or more and, with d_keys (NULL: all of them), those that are their read's best: flag, then scatter
+hipError_t tbk_launch_pieces_keep_flag(const tbk_read_piece *d_pieces, uint64_t n_pieces, uint64_t min_length, const unsigned long long *d_keys,
+                                       uint64_t *d_flags, unsigned long long *d_tile_counts, hipStream_t stream);
+hipError_t tbk_launch_pieces_keep(const tbk_read_piece *d_pieces, uint64_t n_pieces, const uint64_t *d_flags, const unsigned long long *d_tile_offsets,
+                                  tbk_read_piece *d_out, uint64_t n_out, hipStream_t stream);
 }

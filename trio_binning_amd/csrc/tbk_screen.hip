@@ -84,11 +84,7 @@ tbk_screen_evidence_kernel(const uint32_t *__restrict__ clean_bits, const uint32
                 const uint32_t mask = mine ? range_word_mask(w, w_first, w_last, a, b) : 0u;
                 const uint32_t mask_below = halo ? range_word_mask(below, w_first, w_last, a, b) : 0u;
                 const uint32_t c = clean_bits[at] & mask, h = held_bits[at] & mask, hb = held_bits[below] & mask_below;
-                uint64_t x = ((uint64_t)h << 32) | hb;  // shifts 0 .. n - 1 of the held bits so far; n doubles up to k
-                int n = 1;
-                while (2 * n <= k) { x |= x << n; n *= 2; }
-                x |= x << (k - n);  // (k - n < n)
-                const uint32_t cov = (uint32_t)(x >> 32);
+                const uint32_t cov = covered_word(h, hb, k);  // (tbk_lookup.h: the ladder of shift-and-ors)
                 const uint32_t under = (k == 32 ? hb : hb >> (32 - k)) != 0;  // position 32 w - 1 is covered
                 clean += (uint32_t)__popc(c);
                 held += (uint32_t)__popc(h);

@@ -1421,6 +1421,12 @@ READ_DEPTH = np.dtype([("clean", "<u8"), ("present", "<u8"), ("saturated", "<u8"
                        ("q3", "u1"), ("highest", "u1"), ("present_median", "u1"), ("pad", "u1", (2,))])
 assert READ_DEPTH.itemsize == 40
 
+# one piece of a sequence (``tbk_read_piece``, 24 bytes): the positions [first, end) of sequence ``read``
+READ_PIECE = np.dtype([("read", "<u8"), ("first", "<u8"), ("end", "<u8")])
+assert READ_PIECE.itemsize == 24
+PIECES_SIDES = {"covered": 0, "uncovered": 1}
+PIECES_WHICH = {"all": 0, "longest": 1}
+
 
 class DatabaseQuery:
     """How often did the reads see the k-mers of these sequences?  (``tbk_kmerdb_query``, include/tbk.h.)
@@ -1543,6 +1549,38 @@ class DatabaseQuery:
         records = np.zeros(n, dtype=READ_EVIDENCE)
         check(lib.tbk_kmerdb_query_evidence(self._h, bases.ctypes.data, offsets.ctypes.data, n, min_count, max_count, records.ctypes.data))
         return records
+
+    def pieces(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 1, max_count: int = 255, side: str = "covered", which: str = "all",
+               min_length: int = 1, evidence: bool = False):
+        """The pieces of a batch of reads (``tbk_kmerdb_query_pieces``, include/tbk.h): the maximal runs ``[first, end)`` of
+        consecutive positions of one sequence that are covered (``side="covered"``) or are not (``"uncovered"``), as a
+        ``READ_PIECE`` array ordered by (read, first).  Covered is the read evidence's: a position in a clean window whose counter
+        lies in ``[max(floor, min_count), max_count]``.  Pieces shorter than ``min_length`` are left out; with ``which="longest"``
+        only the longest of a sequence's remaining pieces comes home, the first among equals.  With ``evidence`` the pair (pieces,
+        the ``READ_EVIDENCE`` records of ``evidence()`` for the same arguments) from one lookup.  The session is only read.
+        ``ValueError`` for a ``min_count`` outside 1..255, a ``max_count`` outside ``min_count``..255, a ``min_length`` outside
+        0..2^64 - 1 and a ``side`` or ``which`` that is not one of the words."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.size - 1, 0)
+        min_count, max_count, min_length = int(min_count), int(max_count), int(min_length)
+        if side not in PIECES_SIDES or which not in PIECES_WHICH:
+            raise ValueError("pieces: side {!r} must be one of {} and which {!r} one of {}".format(side, sorted(PIECES_SIDES), which, sorted(PIECES_WHICH)))
+        if not 1 <= min_count <= 255 or not min_count <= max_count <= 255:
+            raise ValueError("pieces: min_count {} must lie in 1 .. 255 and max_count {} in min_count .. 255".format(min_count, max_count))
+        if not 0 <= min_length < 1 << 64:
+            raise ValueError("pieces: min_length {} must lie in 0 .. 2^64 - 1".format(min_length))
+        records = np.zeros(n, dtype=READ_EVIDENCE) if evidence else None
+        ptr, count = C.c_void_p(), C.c_uint64()
+        check(lib.tbk_kmerdb_query_pieces(self._h, bases.ctypes.data, offsets.ctypes.data, n, min_count, max_count, PIECES_SIDES[side], PIECES_WHICH[which],
+                                          min_length, records.ctypes.data if evidence else None, C.byref(ptr), C.byref(count)))
+        try:
+            pieces = np.zeros(count.value, dtype=READ_PIECE)
+            if count.value:
+                C.memmove(pieces.ctypes.data, ptr, count.value * READ_PIECE.itemsize)
+        finally:
+            lib.tbk_host_free(ptr)
+        return (pieces, records) if evidence else pieces
 
     def read_depth(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 1) -> np.ndarray:
         """The k-mer depth of a batch of reads (``tbk_kmerdb_query_read_depth``, include/tbk.h): one ``READ_DEPTH`` record per

@@ -428,6 +428,20 @@ class BinWriter:
 
         check(lib.tbk_bin_writer_write(self._h, batch._h, bins))
 
+    def write_pieces(self, batch: Batch, pieces, bins: bytes, suffix: bool = False) -> None:
+        """The batch's records cut to their pieces (``tbk_bin_writer_write_pieces``, include/tbk.h "read pieces"): ``pieces`` is a
+        ``kmers.READ_PIECE`` array ordered by (read, first), ``bins`` one byte per READ - an ``A`` read's pieces go to the first file
+        (none: nothing is written), a ``B`` read goes whole to the second and any other whole to the third.  With ``suffix`` a piece
+        ``[f, e)`` that is not its whole record is named ``name:f+1-e``."""
+        import numpy as np
+
+        from ._lib import check, lib
+
+        pieces = np.ascontiguousarray(pieces)
+        if pieces.dtype.itemsize != 24 or pieces.ndim != 1:
+            raise ValueError("write_pieces: pieces must be a one-dimensional array of 24-byte records (kmers.READ_PIECE)")
+        check(lib.tbk_bin_writer_write_pieces(self._h, batch._h, pieces.ctypes.data if pieces.size else None, pieces.size, bins, int(bool(suffix))))
+
     def write_counts(self, batch: Batch, bins: bytes, counts) -> None:
         """The haplotag form's ``write``: ``counts`` is the batch's (n_reads, 2) int32 array, as ``Classifier.wait`` returns it."""
         import numpy as np
